@@ -16,7 +16,13 @@ scaling, 32 channels per GPU, no collective on the data path.  torch.distributed
 the barrier, the max-over-ranks time and the sum of the ranks' channel-sample counts.  `value` is
 (channel-samples of ALL ranks / 32) / time: the job's throughput in the metric's unit.
 
+A plain run measures the headline figure alone: set-up, warm-up, the timed steps, the line.  `--full` adds every other leg
+and check (the one-launch plan and its bitwise check, the cross-rank verification, CPU baselines, acquisition, closed loop,
+host-fed, rates, per-tick, ref_config, multignss).  `--dump-outputs DIR` writes what the last timed step computed
+(DIR/<name>.npy, float64); the inputs are the same from run to run, so two builds can be compared output for output.
+
     python bench.py --gpus 1 --steps 60 --warmup 2
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \\
         --master-port 29500 bench.py --gpus 8 --steps 60 --warmup 2
 """
@@ -39,6 +45,34 @@ CODE_RATE = 1.023e6
 L1 = 1575.42e6
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 VERIFY_PER_RANK = 4     # N > 1: channels of every other rank that rank 0 recomputes on its own GPU and compares bitwise
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: what all files of one run may hold together
+DUMP_SAMPLE_ROWS = 1 << 19  # ... of which the headline pass's sampled rows (25 MB in float64)
+DUMP_SEED = 20260017
+
+
+def epl_dump(got, n_ch, prefix="epl"):
+    """The arrays a caller of an E/P/L pass receives -- one row [I, Q] x taps per channel-epoch, epoch-major over n_ch
+    channels -- as named float64 arrays for --dump-outputs: every channel's sum over the pass (all rows take part), and a
+    fixed, seeded sample of the rows with their item indices (every row where the pass is small enough)."""
+    got = np.asarray(got, dtype=np.float64)
+    n = len(got)
+    if n > DUMP_SAMPLE_ROWS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=DUMP_SAMPLE_ROWS, replace=False))
+    else:
+        idx = np.arange(n)
+    return {f"{prefix}_rows": got[idx], f"{prefix}_row_index": idx.astype(np.float64),
+            f"{prefix}_channel_sums": got.reshape(-1, n_ch, got.shape[1]).sum(axis=0)}
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each array as out_dir/<name>.npy in float64; refuses (before writing anything) more than DUMP_MAX_BYTES."""
+    arrays = {name: np.ascontiguousarray(a, dtype=np.float64) for name, a in arrays.items()}
+    size = sum(a.nbytes for a in arrays.values())
+    if size > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {size} bytes of outputs exceed the budget of {DUMP_MAX_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def satellites(n_total=N_CH, seed=20260003):
@@ -684,8 +718,9 @@ def closed_loop_leg(eng, items, n_epochs, n_ch=N_CH, fs=None):
 
 def multignss_workload(args, rank, local_rank, world, torch, dist, eng=None, emit=True):
     """BASELINE configs 4-5: per GPU 32 GPS L1 C/A + 32 E1-like (seeded 4092-chip codes, BOC(1,1)) channels,
-    5 taps VE/E/P/L/VL, fs = 50 MHz, 4 ms epochs.  Selected with --workload multignss; the default run carries a
-    short version of it as the `multignss` key.  """
+    5 taps VE/E/P/L/VL, fs = 50 MHz, 4 ms epochs.  Selected with --workload multignss; a --full run of the default
+    workload carries a short version of it as the `multignss` key.  Its CPU baseline, acquisition and closed-loop legs
+    run with --full only."""
     from sydr_amd.engine import FMT_CI8, Engine, make_items
     fs, n_gps, n_e1, taps = 50e6, 32, 32, (-1.0, -0.5, 0.0, 0.5, 1.0)
     own_engine = eng is None
@@ -822,7 +857,12 @@ def multignss_workload(args, rank, local_rank, world, torch, dist, eng=None, emi
                                                       f"this run launched {ran!r}: no traffic figure")
         except Exception:
             pass
-    if rank == 0 and world == 1:
+    if args.dump_outputs is not None and rank == 0:         # what the last timed step computed: the resident plans' outputs
+        arrays = {}
+        for name, (plan, n_ch, _, _) in zip(("multignss_gps", "multignss_e1"), plans):
+            arrays.update(epl_dump(plan.fetch()[:n_avail * per_step * n_ch], n_ch, name))
+        dump_outputs(args.dump_outputs, arrays)
+    if args.full and rank == 0 and world == 1:
         from oracle import sydr_oracle as orc
         got = plans[1][0].fetch()
         it = e1_items[0]
@@ -840,7 +880,7 @@ def multignss_workload(args, rank, local_rank, world, torch, dist, eng=None, emi
         result["cpu_baseline"] = {"value": float(it["n_samples"]) / (n_gps + n_e1) / dt / 1e6, "unit": "Msamples/s", "cores": 1,
                                   "kind": "port", "sample": "one E1-like channel-epoch (200 000 samples, 5 taps) through "
                                   "oracle/sydr_oracle.py:epl, scaled to 64 channels", "max_rel_err_gpu_vs_oracle": err}
-    if rank == 0 and world == 1 and not args.no_acquisition:
+    if args.full and rank == 0 and world == 1 and not args.no_acquisition:
         # PCPS at this configuration's rate (N = 50 000 = 200 x 250: the general four-step kernels), the 32 GPS PRNs
         from oracle import sydr_oracle as orc
         slots = np.arange(n_gps)
@@ -876,7 +916,7 @@ def multignss_workload(args, rank, local_rank, world, torch, dist, eng=None, emi
                                               "algorithmic_bytes_per_call": algo}}
         if result["acquisition"]["roofline"]["traffic"]:
             result["acquisition"]["roofline"]["traffic_over_algorithmic"] = result["acquisition"]["roofline"]["traffic"] / algo
-    if rank == 0 and world == 1 and not args.no_closed_loop:
+    if args.full and rank == 0 and world == 1 and not args.no_closed_loop:
         result["closed_loop"] = closed_loop_multignss_leg(eng, gps_items[:n_gps], e1_items[:n_e1], fs, taps,
                                                           min(e_gps, e_e1, 400))
     for plan, *_ in plans:
@@ -1034,10 +1074,19 @@ def main():
                     help="if the legs AFTER the timed headline measurement have not finished by then, print the line with what "
                          "there is and exit (0: no watchdog)")
     ap.add_argument("--closed-loop-epochs", type=int, default=2000)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement, run every other leg and check as well (one-launch plan and its "
+                         "bitwise check, cross-rank verification, CPU baselines, acquisition, closed loop, host-fed, rates, "
+                         "per-tick, ref_config, multignss); a plain run measures the headline figure alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64, rank 0; a fixed, seeded "
+                         "sample where the whole output exceeds the budget of DUMP_MAX_BYTES)")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be at least 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1: ms_per_step is the time of one timed step")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # Started without a launcher: this process becomes the launcher -- it has not imported torch or touched HIP, and
         # never does -- and the N ranks are fresh children (one process per GPU).
@@ -1170,7 +1219,9 @@ def main():
     eng.prof_reset()
     eng.prof_enable(True)
     t0 = time.perf_counter()
-    pipelined_passes(args.steps)
+    # (--dump-outputs: the last step's plans are kept, not dropped, so that their outputs can be read after the timed region;
+    # their buffers then come from fresh allocations instead of the pool in that one step)
+    last_step = pipelined_passes(args.steps, keep_last=args.dump_outputs is not None)
     eng.stream_sync(batch_stream)
     torch.cuda.synchronize()
     elapsed = elapsed_own = time.perf_counter() - t0
@@ -1189,8 +1240,75 @@ def main():
     kern_ms, launches = eng.prof_read("epl_kernel")
     eng.prof_reset()
 
-    # ---- outside the timed region: ONE plan for the whole stream -- what the steps re-ran until round 5, the launch the
-    # counters of profiles/pmc_traffic.json were taken on, and the outputs every check below reads
+    stream_samples = ch_samples / N_CH                       # samples of THE stream consumed per rank (same on all)
+    value = job_ch_samples / N_CH / elapsed / 1e6            # the job's channel-samples, in units of 32-channel batches
+    avg_kernel_s = kern_ms / max(1, launches) * 1e-3
+    algo_bytes_per_launch = 2.0 * ch_samples / max(1, n_launches)  # 2 B per channel-sample (ci8)
+    achieved = algo_bytes_per_launch / avg_kernel_s / 1e9 if launches else 0.0
+    flops = (6 + 4 * len(SPACING)) * ch_samples / max(1, n_launches)
+    seg_epochs = min(seg_items, n_run) // N_CH
+
+    result = {
+        "metric": "IQ Msamples/s through 32-ch E/P/L correlators @25 MHz fs",
+        "value": value, "unit": "Msamples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        # (the driver's record keeps ~128 characters of a string: the workload first, the step's definition under its own key)
+        "config": {"workload": "GPS L1 C/A tracking, 32 channels/GPU, E/P/L (3 taps), fs=25 MHz, 1 ms integration, "
+                               f"{args.stream_seconds:g} s synthetic ci8 IQ stream",
+                   "step": f"one pass over the whole stream ({n_epochs} epochs x {N_CH} channels) in {len(seg_starts)} segments of "
+                           f"{seg_epochs} ms: per segment plan creation (items uploaded, checked, per-epoch setups), ONE launch, "
+                           "plan destruction -- all inside the timed region, a segment's plan made while the segment before runs",
+                   "channels_per_gpu": N_CH, "channels_total": n_total, "fs_hz": FS, "taps": len(SPACING), "iq_format": "ci8",
+                   "host_thread_bound_to_gpu_cpus": host_thread_bound, "plan_seconds": args.plan_seconds,
+                   "mode": f"open-loop batched (true NCO trajectory, {min(seg_items, n_run)} channel-epochs per launch)",
+                   "sharding": f"one stream of {n_total} satellites replicated on {world} GPU(s) (same seed), channels "
+                               f"sharded {N_CH} per GPU, one HIP stream per channel batch, no collective"},
+        "x_realtime": stream_samples / elapsed / FS,          # seconds of THE stream (all channels tracked) per second
+        "channel_Msamples_per_s": job_ch_samples / elapsed / 1e6,
+        "multi_gpu": None,                                    # --full, N > 1: who took part, per-rank rates, cross-rank bitwise check
+        # what the timed region contains per segment, host side: sdr_epl_plan_create (4 pooled buffers, item upload from
+        # page-locked memory, the check launch + its read-back, the setup launch, one stream synchronisation),
+        # sdr_epl_plan_run_range_on, sdr_epl_plan_destroy
+        "plan": {"first_pass_ms_in_process": first_pass_s * 1e3, "items": int(len(items)), "segments_per_pass": len(seg_starts)},
+    }
+    setup_bytes = 480 if len(SPACING) == 3 else 560
+    # (the ring is the only copy of the samples: round 5's sign-flipped image beside it -- + 2 B per sample -- is gone, a ci8
+    # ring holds that form itself; setups / items / outputs: of the segments in flight, two at most)
+    result["device_bytes"] = {"ring": int(total) * 2, "items": 2 * min(seg_items, n_run) * 48,
+                              "setups": 2 * min(seg_items, n_run) * setup_bytes, "outputs": 2 * min(seg_items, n_run) * 16 * len(SPACING),
+                              "whole_stream_plan_of_the_checks": int(len(items)) * (48 + setup_bytes + 16 * len(SPACING))}
+    result["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                          "frac": achieved / HBM_PEAK_GBS, "traffic": None, "kernel": "epl_kernel",
+                          "avg_launch_ms": avg_kernel_s * 1e3, "launches": int(launches),
+                          "algorithmic_bytes_per_launch": algo_bytes_per_launch,
+                          # `bound` names the roof SURVEY 8(d) prices the path against (the contract's "hbm" | "mfma"); what the
+                          # counters say holds the kernel is below: the 32 channels share the samples through L2 / MALL
+                          # (traffic ~0.3 x the algorithmic bytes) and the vector pipe's fp64 issue slots are ~0.9 busy
+                          "bound_by_counters": "fp64 issue (VALU): see valu_issue.busy_frac, traffic_frac_of_peak",
+                          # the same launch against the OTHER roof (SURVEY 8d: 6 + 4*taps flops per channel-sample;
+                          # fp64 vector peak 78.6 TFLOP/s): the kernel is VALU-issue-bound, not HBM-bound (DESIGN.md K1)
+                          "fp64_vector": {"achieved_tflops": flops / avg_kernel_s / 1e12 if launches else 0.0,
+                                          "peak_tflops": 78.6, "frac": flops / avg_kernel_s / 78.6e12 if launches else 0.0}}
+
+    if last_step:                                           # --dump-outputs: what the last timed step handed back
+        got_last = np.concatenate([p.fetch() for _, p in sorted(last_step, key=lambda jp: jp[0])])
+        for _, p in last_step:
+            p.close()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, epl_dump(got_last, N_CH))
+        del got_last
+    if not args.full:
+        eng.host_free(items_pinned.view(np.uint8))
+        eng.close()
+        if rank == 0:
+            print(json.dumps(flat_scalars(result)))
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    # ---- --full, outside the timed region: ONE plan for the whole stream -- what the steps re-ran until round 5, the launch
+    # the counters of profiles/pmc_traffic.json were taken on, and the outputs every check below reads
     t_plan = time.perf_counter()
     plan = eng.epl_plan(items, SPACING, FS)                 # (the process's first plan of this size: 1.1 GB of fresh allocations)
     plan_create_fresh_s = time.perf_counter() - t_plan
@@ -1224,42 +1342,9 @@ def main():
     if world > 1:
         multi_gpu = verify_across_ranks(eng, dist, torch, rank, local_rank, world, all_sats, mine, got_all, total,
                                         elapsed_own / args.steps, ch_samples / args.steps)
-
-    stream_samples = ch_samples / N_CH                       # samples of THE stream consumed per rank (same on all)
-    value = job_ch_samples / N_CH / elapsed / 1e6            # the job's channel-samples, in units of 32-channel batches
-    avg_kernel_s = kern_ms / max(1, launches) * 1e-3
-    algo_bytes_per_launch = 2.0 * ch_samples / max(1, n_launches)  # 2 B per channel-sample (ci8)
-    achieved = algo_bytes_per_launch / avg_kernel_s / 1e9 if launches else 0.0
-    flops = (6 + 4 * len(SPACING)) * ch_samples / max(1, n_launches)
-    seg_epochs = min(seg_items, n_run) // N_CH
-
-    result = {
-        "metric": "IQ Msamples/s through 32-ch E/P/L correlators @25 MHz fs",
-        "value": value, "unit": "Msamples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        # (the driver's record keeps ~128 characters of a string: the workload first, the step's definition under its own key)
-        "config": {"workload": "GPS L1 C/A tracking, 32 channels/GPU, E/P/L (3 taps), fs=25 MHz, 1 ms integration, "
-                               f"{args.stream_seconds:g} s synthetic ci8 IQ stream",
-                   "step": f"one pass over the whole stream ({n_epochs} epochs x {N_CH} channels) in {len(seg_starts)} segments of "
-                           f"{seg_epochs} ms: per segment plan creation (items uploaded, checked, per-epoch setups), ONE launch, "
-                           "plan destruction -- all inside the timed region, a segment's plan made while the segment before runs",
-                   "channels_per_gpu": N_CH, "channels_total": n_total, "fs_hz": FS, "taps": len(SPACING), "iq_format": "ci8",
-                   "host_thread_bound_to_gpu_cpus": host_thread_bound, "plan_seconds": args.plan_seconds,
-                   "mode": f"open-loop batched (true NCO trajectory, {min(seg_items, n_run)} channel-epochs per launch)",
-                   "sharding": f"one stream of {n_total} satellites replicated on {world} GPU(s) (same seed), channels "
-                               f"sharded {N_CH} per GPU, one HIP stream per channel batch, no collective"},
-        "x_realtime": stream_samples / elapsed / FS,          # seconds of THE stream (all channels tracked) per second
-        "channel_Msamples_per_s": job_ch_samples / elapsed / 1e6,
-        "multi_gpu": multi_gpu,                               # N > 1: who took part, per-rank rates, cross-rank bitwise check
-        "segments_equal_one_launch_bitwise": bool(seg_equal),
-        # what the timed region contains per segment, host side: sdr_epl_plan_create (4 pooled buffers, item upload from
-        # page-locked memory, the check launch + its read-back, the setup launch, one stream synchronisation),
-        # sdr_epl_plan_run_range_on, sdr_epl_plan_destroy
-        "plan": {"create_ms_whole_stream": plan_create_s * 1e3, "create_ms_whole_stream_fresh_allocations": plan_create_fresh_s * 1e3,
-                 "first_pass_ms_in_process": first_pass_s * 1e3,
-                 "items": int(len(items)), "segments_per_pass": len(seg_starts)},
-    }
+    result["multi_gpu"] = multi_gpu
+    result["segments_equal_one_launch_bitwise"] = bool(seg_equal)
+    result["plan"].update(create_ms_whole_stream=plan_create_s * 1e3, create_ms_whole_stream_fresh_allocations=plan_create_fresh_s * 1e3)
     # the SAME stream through ONE resident plan re-run (what `value` was until round 5: nothing but the launch in the step) --
     # the secondary figure; and a plan used once, unpipelined (its creation, then its pass)
     reuse_ch = float(pass_samples)
@@ -1271,24 +1356,6 @@ def main():
     result["single_use"] = {"plan_create_ms": plan_create_s * 1e3, "pass_ms": reuse_s * 1e3,
                             "x_realtime": args.stream_seconds / (plan_create_s + reuse_s),
                             "what": "one plan of the whole stream made, then run once: creation and pass one after the other"}
-    setup_bytes = 480 if len(SPACING) == 3 else 560
-    # (the ring is the only copy of the samples: round 5's sign-flipped image beside it -- + 2 B per sample -- is gone, a ci8
-    # ring holds that form itself; setups / items / outputs: of the segments in flight, two at most)
-    result["device_bytes"] = {"ring": int(total) * 2, "items": 2 * min(seg_items, n_run) * 48,
-                              "setups": 2 * min(seg_items, n_run) * setup_bytes, "outputs": 2 * min(seg_items, n_run) * 16 * len(SPACING),
-                              "whole_stream_plan_of_the_checks": int(len(items)) * (48 + setup_bytes + 16 * len(SPACING))}
-    result["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                          "frac": achieved / HBM_PEAK_GBS, "traffic": None, "kernel": "epl_kernel",
-                          "avg_launch_ms": avg_kernel_s * 1e3, "launches": int(launches),
-                          "algorithmic_bytes_per_launch": algo_bytes_per_launch,
-                          # `bound` names the roof SURVEY 8(d) prices the path against (the contract's "hbm" | "mfma"); what the
-                          # counters say holds the kernel is below: the 32 channels share the samples through L2 / MALL
-                          # (traffic ~0.3 x the algorithmic bytes) and the vector pipe's fp64 issue slots are ~0.9 busy
-                          "bound_by_counters": "fp64 issue (VALU): see valu_issue.busy_frac, traffic_frac_of_peak",
-                          # the same launch against the OTHER roof (SURVEY 8d: 6 + 4*taps flops per channel-sample;
-                          # fp64 vector peak 78.6 TFLOP/s): the kernel is VALU-issue-bound, not HBM-bound (DESIGN.md K1)
-                          "fp64_vector": {"achieved_tflops": flops / avg_kernel_s / 1e12 if launches else 0.0,
-                                          "peak_tflops": 78.6, "frac": flops / avg_kernel_s / 78.6e12 if launches else 0.0}}
     # The line is the contract: everything after this point is additional legs.  Should one of them never return (a stuck
     # worker process, a device call that does not come back), a watchdog thread prints the line as it stood after the last
     # leg that did finish (a serialised snapshot: the timer thread never walks the live dict) and ends the process NON-ZERO.
@@ -1439,7 +1506,7 @@ def main():
     if rank == 0 and world == 1 and not args.no_multignss:
         margs = argparse.Namespace(**vars(args))
         # (a fresh engine after seconds of CPU legs: ~40 ms of this kernel before the clocks have settled, tools/epl_ramp.py)
-        margs.stream_seconds, margs.steps, margs.warmup = 10.0, 10, 12
+        margs.stream_seconds, margs.steps, margs.warmup, margs.dump_outputs = 10.0, 10, 12, None
         m = multignss_workload(margs, rank, local_rank, world, torch, dist, emit=False)
         result["multignss"] = {k: m[k] for k in ("metric", "value", "unit", "ms_per_step", "x_realtime", "config", "roofline",
                                                   "cpu_baseline", "acquisition", "closed_loop") if k in m}

@@ -247,6 +247,22 @@ def make_epl():
     save("g5_epl.npz", **data)
 
 
+# ---------------------------------------------------------------------------------------------- G5b
+def make_ref_c():
+    """The reference's own compiled legacy C correlator (oracle/_ref/tracking.so, `make -C oracle`) on G5's inputs: its
+    outputs, so that tests/test_oracle_ref.py holds the oracle against them where that library is not built."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    from test_oracle_ref import REF_SO, ref_epl
+    assert os.path.exists(REF_SO), "build oracle/_ref first: make -C oracle"
+    g = np.load(os.path.join(HERE, "g5_epl.npz"))
+    prn, fs, f, rc, rk, step = g["fixture_params"]
+    data = {"fixture_ref_c": ref_epl(orc.iq_to_complex(g["fixture_iq"]), int(prn), fs, f, rc, rk, step, (-0.5, 0.0, 0.5))}
+    for tag in g["cases"]:
+        prn, fs, f, rc, rk, step, n = g[f"{tag}_params"]
+        data[f"{tag}_ref_c"] = ref_epl(orc.iq_to_complex(g[f"{tag}_iq"]), int(prn), fs, f, rc, rk, step, tuple(g[f"{tag}_spacing"]))
+    save("g5b_epl_ref_c.npz", stand_ins=np.array([], dtype=str), **data)
+
+
 # ---------------------------------------------------------------------------------------------- G6
 def _channel_config(path, overrides):
     cfg = configparser.ConfigParser()
@@ -472,7 +488,7 @@ def make_loopmath():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["codes", "pcps", "peaks", "epl", "traj", "loop", "serial", "decoding"]
+    which = sys.argv[1:] or ["codes", "pcps", "peaks", "epl", "ref_c", "traj", "loop", "serial", "decoding"]
     if "serial" in which:
         make_serial()
     if "codes" in which:
@@ -483,6 +499,8 @@ if __name__ == "__main__":
         make_peaks()
     if "epl" in which:
         make_epl()
+    if "ref_c" in which:
+        make_ref_c()
     if "traj" in which:
         make_trajectories()
         # strong signal, 1.5 s: drives the Kaplan plugin through PULL_IN -> WIDE -> NARROW, code lock, bit sync

@@ -107,3 +107,43 @@ def test_flat_scalars_reach_the_parts_of_the_line_the_driver_keeps():
     assert r["closed_loop_us_per_epoch"] == d["closed_loop"]["us_per_epoch"]
     assert c["reference_c_value"] == d["cpu_baseline_reference_c"]["value"] and c["mp_cores"] == d["cpu_baseline_mp"]["cores"]
     assert isinstance(d["roofline"]["fp64_vector"], dict)    # the nested forms stay
+
+
+def test_steps_must_be_at_least_one():
+    """ms_per_step is the time of one timed step: `--steps 0` is refused before anything is imported or measured."""
+    import subprocess
+    import sys
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                         timeout=120, cwd=REPO)
+    assert out.returncode != 0 and "--steps" in out.stderr and not out.stdout.strip()
+
+
+def test_dump_of_a_whole_stream_pass_fits_the_budget_and_is_seeded(tmp_path):
+    """--dump-outputs of the headline pass (60 s x 32 channels = 1 919 936 rows of 6 accumulators, 92 MB): the channel sums
+    of every row and a fixed sample of rows, float64, within DUMP_MAX_BYTES, the same sample every time."""
+    import numpy as np
+    import bench
+    n_ch, rows = bench.N_CH, 59998 * bench.N_CH
+    got = np.random.default_rng(5).standard_normal((rows, 6))
+    first = bench.epl_dump(got, n_ch)
+    again = bench.epl_dump(got.copy(), n_ch)
+    assert sorted(first) == ["epl_channel_sums", "epl_row_index", "epl_rows"]
+    assert all(np.array_equal(first[k], again[k]) for k in first)
+    idx = first["epl_row_index"].astype(np.int64)
+    assert len(idx) == bench.DUMP_SAMPLE_ROWS and np.all(np.diff(idx) > 0) and idx[-1] < rows
+    assert np.array_equal(first["epl_rows"], got[idx])
+    assert np.allclose(first["epl_channel_sums"], [got[c::n_ch].sum(axis=0) for c in range(n_ch)])
+    bench.dump_outputs(str(tmp_path / "out"), first)
+    files = sorted(os.listdir(tmp_path / "out"))
+    assert files == ["epl_channel_sums.npy", "epl_row_index.npy", "epl_rows.npy"]
+    loaded = {f[:-4]: np.load(tmp_path / "out" / f) for f in files}
+    assert all(a.dtype == np.float64 and np.array_equal(a, first[k]) for k, a in loaded.items())
+    assert sum(os.path.getsize(tmp_path / "out" / f) for f in files) <= bench.DUMP_MAX_BYTES
+    small = bench.epl_dump(got[:10 * n_ch], n_ch)          # (a pass below the sample size: every row)
+    assert np.array_equal(small["epl_rows"], got[:10 * n_ch]) and np.array_equal(small["epl_row_index"], np.arange(10 * n_ch))
+    try:
+        bench.dump_outputs(str(tmp_path / "big"), {"whole": got})
+    except SystemExit as e:
+        assert "budget" in str(e) and not os.path.exists(tmp_path / "big")
+    else:
+        raise AssertionError("a 92 MB dump was written")

@@ -12,9 +12,9 @@ cd /tmp && export TMPDIR=/tmp
 # the driver's command with short CPU legs and WITHOUT the process-per-channel CPU baseline: its 32 spawned workers each start
 # under the profiler's preloaded library, and one run of the round hung in their shutdown (the untraced run of profile_round.sh keeps it)
 # (no C per-tick leg under the profiler: gcc re-execs, and a traced child writes a second stats file; bench.py also skips the leg by itself when LD_PRELOAD / ROCP* is set)
-ARGS="--steps 20 --warmup 5 --cpu-seconds 2 --cpu-mp-seconds 0 --no-per-tick-c"
+ARGS="--steps 20 --warmup 5 --full --cpu-seconds 2 --cpu-mp-seconds 0 --no-per-tick-c"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 "$ROOT/bench.py" $ARGS > "$OUT/bench_stats.log" 2>&1
-PARGS="--steps 2 --warmup 1 --stream-seconds 6 --cpu-seconds 0.2 --cpu-mp-seconds 0 --no-closed-loop --no-per-tick --no-rates"   # (the ref_config and multignss legs run: their kernels get counters too)
+PARGS="--steps 2 --warmup 1 --full --stream-seconds 6 --cpu-seconds 0.2 --cpu-mp-seconds 0 --no-closed-loop --no-per-tick --no-rates"   # (the ref_config and multignss legs run: their kernels get counters too)
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -- python3 "$ROOT/bench.py" $PARGS > "$OUT/bench_pmc_fetch.log" 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write" -- python3 "$ROOT/bench.py" $PARGS > "$OUT/bench_pmc_write.log" 2>&1
 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE --output-format csv -d "$OUT/pmc_sq" -- python3 "$ROOT/bench.py" $PARGS > "$OUT/bench_pmc_sq.log" 2>&1
