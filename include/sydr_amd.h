@@ -122,7 +122,8 @@ int sdr_iq_alloc(sdr_engine* e, int64_t capacity_samples, int fmt);
 /* Copy n_samples host samples (in the ring's format) to ring_offset.. ,
  * wrapping at the end of the ring (CircularBuffer.shift, circularbuffer.py:54-82). */
 int sdr_iq_upload(sdr_engine* e, const void* iq, int64_t n_samples, int64_t ring_offset);
-/* Copy ring samples back to the host in the ring's format (tests / oracle). */
+/* Copy ring samples back to the host in the ring's format (tests / oracle).  Synchronises the engine's stream;
+ * a ci8 ring holds its bytes sign-flipped, and the call flips them back on the host. */
 int sdr_iq_download(sdr_engine* e, void* iq, int64_t n_samples, int64_t ring_offset);
 
 /* Synthetic multi-satellite IQ written straight into the ring:

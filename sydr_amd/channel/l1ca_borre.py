@@ -2,7 +2,7 @@
 reference's default plugin (sydr/channel/channel_l1ca_borre.py, selected at receiver_gps_l1ca.py:17) with the
 tracking state on the GPU.
 
-The per-epoch arithmetic of borre:333-451 runs in `track_kernel` (sydr_amd/csrc/track.hip, loop_kind 0; NumPy's pi
+The per-epoch arithmetic of borre:333-451 runs in `track_kernel` (sydr_amd/csrc/track_kernel.h, loop_kind 0; NumPy's pi
 in the NCO); this file maps config/channels/channel_GPS_L1CA_borre.ini onto `sdr_loop_cfg` and the
 plugin's attribute names onto the device state."""
 from __future__ import annotations

@@ -8,7 +8,7 @@ reference's receiver feeds to its ephemeris decoder (receiver_gps_l1ca.py:110-12
 same tick carries the new `tow`, `code_since_tow = 0` and the TOW_DECODED / TOW_KNOWN / EPH_DECODED / EPH_KNOWN
 flags from which the receiver forms pseudoranges.
 
-Here `decodeBit` runs on the GPU (track.hip: the bit leaves the device in the epoch record that completes it).
+Here `decodeBit` runs on the GPU (track_kernel.h: the bit leaves the device in the epoch record that completes it).
 Everything after the bit is 50 bit/s host work that BASELINE.json keeps untouched (`sydr/dsp/decoding.py` is NOT
 re-implemented in this package): a device-tracked channel hands each bit to a `NavDecoder`:
 

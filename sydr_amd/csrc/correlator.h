@@ -1,5 +1,5 @@
 // Device-side core of the E/P/L correlator, shared by the open-loop batch kernel (epl.hip)
-// and the persistent closed-loop tracking kernel (track.hip).
+// and the persistent closed-loop tracking kernel (track_kernel.h).
 //
 // Follows EPL of the reference (sydr/dsp/tracking.py:92-116):
 //   replica_i = exp(1j*(-(f*2.0*pi*(i/fs)) + rem_carrier))

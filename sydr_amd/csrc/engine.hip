@@ -193,14 +193,6 @@ __global__ __launch_bounds__(256) void ingest_kernel(const uint4* __restrict__ s
 
 static inline uint32_t ring_flip_mask(const sdr_engine* e) { return e->iq_fmt == SDR_FMT_CI8 ? 0x80808080u : 0u; }
 
-int sdr_iq_flipped(sdr_engine* e, hipStream_t stream, const void** out) {
-    // (round 6: a ci8 ring IS the sign-flipped form -- flipped where the samples enter; no second image, no refresh pass)
-    (void)stream;
-    if (e->iq_fmt != SDR_FMT_CI8 || !e->iq) return sdr_fail(SDR_ERR_STATE, "the sign-flipped sample form exists for ci8 rings only");
-    *out = e->iq;
-    return SDR_OK;
-}
-
 
 // The calling thread onto the CPUs next to the engine's GPU (its PCI function's local_cpulist in sysfs).  A receiver tick
 // is a few round trips over the link through page-locked words: from the other socket each of them crosses the sockets'

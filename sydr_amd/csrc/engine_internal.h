@@ -65,9 +65,9 @@ struct sdr_engine {
     // IQ ring
     void* iq = nullptr;
     int64_t iq_capacity = 0;  // samples
-    // ci8 rings: a second image of the ring with the sign bit of every byte flipped (x + 128 as an unsigned byte) -- what
-    // the straight-line E/P/L kernels build their doubles from (correlator_chip.h: one v_perm_b32 per component, no
-    // v_xor per dword).  Allocated when such a kernel first runs; brought up to date from the ring's dirty range.
+    // A ci8 ring holds its bytes sign-flipped (x + 128 as an unsigned byte), flipped where the samples enter: the
+    // straight-line E/P/L kernels build their doubles from that form (correlator_chip.h: one v_perm_b32 per component, no
+    // v_xor per dword), the others flip back per dword.
     int iq_fmt = SDR_FMT_CI8;
 
     // code slots: int8 chips, row stride = code_stride bytes, plus per-slot length
@@ -189,10 +189,9 @@ int sdr_tick_server_stop(sdr_engine* e);
 void sdr_tick_server_free(sdr_engine* e);
 // engine.hip: the slab waiting in a staging half (srv_slab_*) into the ring by the ingest kernel, on the engine's stream
 int sdr_iq_flush_server_slab(sdr_engine* e);
-// Ring samples [offset, offset + n) (modulo capacity) are being written on e->stream: the flipped image is stale there.
+// Ring samples [offset, offset + n) (modulo capacity) are being written on e->stream: readers on other streams are ordered
+// behind the write (sdr_iq_order_reader).
 void sdr_iq_mark_written(sdr_engine* e, int64_t ring_offset, int64_t n_samples);
-// The flipped image of a ci8 ring, up to date with everything queued on e->stream, usable from `stream`.
-int sdr_iq_flipped(sdr_engine* e, hipStream_t stream, const void** out);
 // A launch on ctx's stream that reads the ring: behind every ring write queued on the engine's own stream so far.
 int sdr_iq_order_reader(sdr_engine* e, StreamCtx* ctx);
 

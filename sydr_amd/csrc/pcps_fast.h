@@ -178,21 +178,9 @@ __global__ __launch_bounds__(kColThreads) void cols_kernel(const PassArgs a, dou
         for (int rr = 0; rr < 5; ++rr) t[rr] = lds4[((5 * s + kB) * 5 + rr) * T + c];
         ibf5(t);
         const int kp = s + 5 * kB;
-#ifdef SDR_EXP_NOSTORE
-        {   // TIMING EXPERIMENT: everything but the stores
-            const double2 z0 = cmul_conj(t[0], base[kB]);
-            if (z0.x == 1.2345e300) zt[kp * N2] = z0;
-#pragma unroll
-            for (int q = 1; q < 5; ++q) {
-                const double2 zq = cmul_conj(t[q], cmulf(base[kB], st[q]));
-                if (zq.x == 1.2345e300) zt[(kp + 25 * q) * N2] = zq;
-            }
-        }
-#else
         zt[kp * N2] = cmul_conj(t[0], base[kB]);
 #pragma unroll
         for (int q = 1; q < 5; ++q) zt[(kp + 25 * q) * N2] = cmul_conj(t[q], cmulf(base[kB], st[q]));
-#endif
     }
 }
 
@@ -201,12 +189,8 @@ __global__ __launch_bounds__(kColThreads) void cols_kernel(const PassArgs a, dou
 __global__ __launch_bounds__(kRowThreads) void rows_kernel(const PassArgs a, const double2* __restrict__ Z) {
     extern __shared__ double2 lds4[];
     constexpr int T = kRowT;
-#ifdef SDR_PCPS_ROWS_FORWARD
-    const int batch = blockIdx.y;
-#else
     // the transforms the column kernel wrote LAST are read FIRST: they are still in the 256 MB Infinity Cache
     const int batch = gridDim.y - 1 - blockIdx.y;
-#endif
     const int k1_0 = blockIdx.x * T;
     const int tid = threadIdx.x;
     const int i = tid / 10, r = tid - i * 10;

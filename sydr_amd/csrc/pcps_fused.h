@@ -39,22 +39,8 @@
 // the 50 000-sample row, 2m + p.
 #pragma once
 
-// Build-time switches of the A/B variants (tools/build_variant.sh <tag> pcps_fused -DFUSED_...=0|1); measured on one
-// box, 32 PRNs x 41 bins, ms per call: all off 0.266; buffer loads 0.267; merged Y step 0.291; twiddles a round ahead
-// 0.273; reads first 0.267 (gpurun_out/r04_fused_var9.txt) -- the defaults are the fastest (the last two switches went
-// with round 6's lane roles)
-#ifndef FUSED_BUFLOAD
-#define FUSED_BUFLOAD 0      // operand loads as buffer loads (scalar descriptor + one per-lane offset) instead of 64-bit addresses
-#endif
-#ifndef FUSED_SPLIT_S2Y
-#define FUSED_SPLIT_S2Y 0    // whole transforms: waves 0-3 do BOTH halves of a round's second row stage while waves 4-7 do the next round's Y step
-                             // (measured, same box, ms per 32 x 41 search: 0.2077 against 0.2039 at 25 MHz, 0.4514 against 0.4482 at 50 MHz --
-                             // a SIMD's one arithmetic wave issues a dependent fp64 instruction every ~7 cycles, two share the pipe at 4: the
-                             // stage wants both of a SIMD's waves in it; not kept)
-#endif
-#ifndef FUSED_MERGE_Y
-#define FUSED_MERGE_Y 0      // the next round's Y-in-place step inside this round's second row stage (3 barriers per round, not 4)
-#endif
+// (Variants built, measured against this kernel and dropped -- operand buffer loads, the next round's Y step merged into or
+// run beside the second row stage, the next unit's operands requested a unit ahead: docs/notes/next_and_tried.md)
 
 namespace fused25k {
 
@@ -66,7 +52,8 @@ constexpr int N1 = 125, N2 = 200, N = 25000;
 constexpr int kThreads = 512;
 constexpr int kWaves = kThreads / 64;
 constexpr int kBuf = 25 * N2;                 // double2 per round buffer
-constexpr int kTab = 240;                     // w125^e (e <= 96) during the column stage, w200^e (e <= 171) during the rows
+constexpr int kTab = 240;                     // w125^e (e <= 96) during the column stage; during the rows 180 entries
+                                              // w200^(e k'') at [k'' - 1][e] (k'' = 1..9, e = 0..19: exponents up to 171)
 constexpr size_t kLdsBytes = (size_t)(2 * kBuf + kTab) * sizeof(double2);
 static_assert(kLdsBytes == 160 * 1024, "the whole LDS of a CU");
 constexpr int kRecordsPerTransform = kWaves;
@@ -100,25 +87,8 @@ __device__ __forceinline__ void idft10c(double2* u) {
     }
 }
 
-// 16-byte buffer load: wave-uniform descriptor (base, bytes) + per-lane 32-bit byte offset + wave-uniform byte offset --
-// no 64-bit address per load in vector registers and no vector arithmetic for the 50 distances of an item
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-#if FUSED_BUFLOAD
-struct Operand {
-    __amdgpu_buffer_rsrc_t rs;
-};
-__device__ __forceinline__ Operand make_operand(const double2* base) { return {make_rsrc(base, N * 16)}; }
-__device__ __forceinline__ double2 ldb(const Operand& o, unsigned voff, unsigned soff) {
-    const u32x4 q = __builtin_amdgcn_raw_buffer_load_b128(o.rs, (int)voff, (int)soff, 0);
-    double2 d;
-    d.x = __hiloint2double((int)q.y, (int)q.x);
-    d.y = __hiloint2double((int)q.w, (int)q.z);
-    return d;
-}
-#else
+// 16-byte operand load: wave-uniform base + per-lane byte offset + wave-uniform byte offset (as buffer loads -- scalar
+// descriptor + offsets -- the kernel spilled 128 registers and was no faster)
 struct Operand {
     const char* base;
 };
@@ -126,7 +96,6 @@ __device__ __forceinline__ Operand make_operand(const double2* base) { return {r
 __device__ __forceinline__ double2 ldb(const Operand& o, unsigned voff, unsigned soff) {
     return *reinterpret_cast<const double2*>((o.base + soff) + voff);
 }
-#endif
 
 // One unit of work of a persistent workgroup: a whole (PRN, bin) transform, or -- for the transforms left over when the
 // search is not a whole number of rounds of 256 -- ONE of a transform's five rounds: the column stage then computes that
@@ -174,25 +143,6 @@ __device__ unsigned long long g_fused_stamps[256][8];
 #define FUSED_DFLT(x) = x
 #endif
 
-// FUSED_PREFETCH_UNIT (N = 25 000, whole transforms; round 6): the first three of item 0's five operand groups of the NEXT
-// unit are requested during THIS unit's last two rounds -- into the registers the parked rounds have left by then -- and
-// consumed by the next unit's column stage: 30 of a unit's 100 operand loads, and the ~2 k cycles until a fresh stream's
-// first load is back, move under the rounds, where the vector-memory path is idle.
-// OFF: built and measured (VERDICT r5 item 1's "operands of transform t + 1 loaded while t is in its row stages").  The
-// values cross the persistent loop's back edge, and the register allocator carries them through scratch memory there
-// (48 / 136 / 383 spilled registers for 1 / 2 / 3 groups, whatever is done to shorten their live ranges): same box, ms per
-// 32 x 41 search, 0.2034 without, 0.215 with one group, 0.220 with two.
-#ifndef FUSED_PREFETCH_UNIT
-#define FUSED_PREFETCH_UNIT 0    // groups requested a unit ahead (0: none; 1..3)
-#endif
-constexpr int kPfGroups = FUSED_PREFETCH_UNIT > 0 ? FUSED_PREFETCH_UNIT : 1;
-struct UnitPrefetch {
-    double2 x[kPfGroups][5], c[kPfGroups][5];    // item 0, groups m1 = 0 .. kPfGroups - 1 (points m1 + 5 m2), spectrum and code spectrum
-    bool have;                   // (uniform) x / c hold THIS unit's operands
-    bool next_whole;             // (uniform) the unit after this one is a whole transform: its groups are requested in round 3
-    int next_prn, next_bin;
-};
-
 // One unit of work (a whole transform, or one or two of its five rounds) by the 512 threads of the workgroup.
 // !WHOLE: `mode` = r0 | r1 << 4, the unit's rounds (r1 = 15: one round only); round r0 lives in the first LDS buffer, r1 in
 // the second -- nothing is parked in registers.
@@ -200,18 +150,15 @@ struct UnitPrefetch {
 // TwoCorrelationPeakComparison allows: [0, a1) U [b0, b1) (acquisition.py:98-111); flat index = the code phase;
 // no bound from the first sweep (the second peak lies below it).
 // TERMS = 2: the unit is one parity of a 50 000-point transform (header comment): `bin` = the real bin, `par` the parity.
-template <bool WHOLE, bool SECOND = false, int TERMS = 1, bool PF = false>
+template <bool WHOLE, bool SECOND = false, int TERMS = 1>
 __device__ __forceinline__ void one_unit(const Args& a, double2* lds4, const int tid, const int prn, const int bin, const int mode,
                                          const int rec_slot, const int a1 FUSED_DFLT(0), const int b0 FUSED_DFLT(0), const int b1 FUSED_DFLT(0),
-                                         const int par FUSED_DFLT(0), UnitPrefetch* const pf_ FUSED_DFLT(nullptr)
+                                         const int par FUSED_DFLT(0)
 #ifdef SDR_FUSED_STAMPS
                                          , unsigned long long& stamp_
 #endif
 ) {
     constexpr int NF = TERMS * N;                       // samples of the row the unit's outputs belong to
-    constexpr bool kPf = PF && FUSED_PREFETCH_UNIT > 0 && WHOLE && !SECOND && TERMS == 1;
-    UnitPrefetch dummy_pf_;                             // (!kPf: never touched)
-    UnitPrefetch* const pf = kPf ? pf_ : &dummy_pf_;     // (kPf: the kernel's own object -- never null, so that it lives in registers)
     const int r0 = mode & 15, r1 = mode >> 4;           // (!WHOLE)
     double2* const tab = lds4 + 2 * kBuf;
     // (TERMS = 2: the engine's table is exp(-2 pi i m / 50 000); the 25 000-point transform's own twiddles are its even entries)
@@ -283,20 +230,13 @@ __device__ __forceinline__ void one_unit(const Args& a, double2* lds4, const int
     const Operand xs_u = make_operand(a.spec + (a.spec_off ? (size_t)a.spec_off[bin] : (size_t)bin * NF));
     const Operand cs_u = make_operand(a.code_spec + ((size_t)prn * TERMS + par) * NF);
     const unsigned toff = (unsigned)cb * 16u;
-    long long next_spec = 0;                                // (kPf) where the NEXT unit's spectrum starts: read now, used in round 3
-    if constexpr (kPf)
-        if (pf->next_whole && a.spec_off) next_spec = a.spec_off[pf->next_bin];
-    // FUSED_EARLY_ITEM1 = 1 | 2 (N = 25 000, whole transforms): item 1's first one or two groups of operands are requested BEFORE
-    // item 0's second radix-5 stage (~600 instructions per lane with nothing in flight for this wave, then the ~2 k cycles
-    // until the first load of a fresh stream is back).  Measured, same box, ms per 32 x 41 search: off 0.2055, one group
-    // 0.2038, two 0.2066 -- the other waves cover most of that gap already.
-#ifndef FUSED_EARLY_ITEM1
-#define FUSED_EARLY_ITEM1 1
-#endif
-    constexpr bool kEarly = FUSED_EARLY_ITEM1 && TERMS == 1 && WHOLE;       // (the short units keep nothing parked, but their bodies are not where the time is)
-    constexpr int kEarlyGroups = FUSED_EARLY_ITEM1;         // 1 or 2
+    // (N = 25 000, whole transforms) item 1's first group of operands is requested BEFORE item 0's second radix-5 stage
+    // (~600 instructions per lane with nothing in flight for this wave, then the ~2 k cycles until the first load of a fresh
+    // stream is back).  Measured, same box, ms per 32 x 41 search: not early 0.2055, one group 0.2038, two 0.2066 -- the
+    // other waves cover most of that gap already.
+    constexpr bool kEarly = TERMS == 1 && WHOLE;            // (the short units keep nothing parked, but their bodies are not where the time is)
     constexpr int kRowBytes = N2 * 16;                      // one n1 step
-    double2 xe[2][5], ce[2][5];                             // (kEarly) item 1's groups 0 and 1
+    double2 xe[5], ce[5];                                   // (kEarly) item 1's group 0
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         double2* const eP = lds4 + cb + 100 * j;            // E slots of this (r, column): + 5 N2 kB; round 1: + kBuf
@@ -305,11 +245,9 @@ __device__ __forceinline__ void one_unit(const Args& a, double2* lds4, const int
             double2 xa[5], ca[5];
 #pragma unroll
             for (int m2 = 0; m2 < 5; ++m2) {
-                if (kPf && j == 0) {
-                    xa[m2] = ca[m2] = make_double2(0.0, 0.0);       // (unused: item 0 reads the prefetched groups)
-                } else if (kEarly && j == 1) {
-                    xa[m2] = xe[0][m2];
-                    ca[m2] = ce[0][m2];
+                if (kEarly && j == 1) {
+                    xa[m2] = xe[m2];
+                    ca[m2] = ce[m2];
                 } else {
                     xa[m2] = ldb(xs_u, toff, 1600 * j + kRowBytes * 25 * m2);
                     ca[m2] = ldb(cs_u, toff, 1600 * j + kRowBytes * 25 * m2);
@@ -322,59 +260,15 @@ __device__ __forceinline__ void one_unit(const Args& a, double2* lds4, const int
                     eP[kBuf + 5 * N2 * g] = park[0][5 + g];
                 }
             }
-            if (kPf && j == 0) {
-                // (FUSED_PREFETCH_UNIT) the first kPfGroups groups were requested by the unit before (or are requested now: the
-                // workgroup's first whole unit); the others a group ahead of their use, as in the plain loop
-                if (!pf->have) {
-#pragma unroll
-                    for (int g = 0; g < kPfGroups; ++g)
-#pragma unroll
-                        for (int m2 = 0; m2 < 5; ++m2) {
-                            pf->x[g][m2] = ldb(xs_u, toff, kRowBytes * 5 * (g + 5 * m2));
-                            pf->c[g][m2] = ldb(cs_u, toff, kRowBytes * 5 * (g + 5 * m2));
-                        }
-                }
-                double2 xn[5], cn[5];                        // the group after the one being multiplied
-#pragma unroll
-                for (int m1 = 0; m1 < 5; ++m1) {
-                    double2 xc[5], cc[5];
-#pragma unroll
-                    for (int m2 = 0; m2 < 5; ++m2) {
-                        xc[m2] = m1 < kPfGroups ? pf->x[m1][m2] : xn[m2];
-                        cc[m2] = m1 < kPfGroups ? pf->c[m1][m2] : cn[m2];
-                    }
-                    if (m1 + 1 < 5 && m1 + 1 >= kPfGroups) {
-#pragma unroll
-                        for (int m2 = 0; m2 < 5; ++m2) {
-                            xn[m2] = ldb(xs_u, toff, kRowBytes * 5 * (m1 + 1 + 5 * m2));
-                            cn[m2] = ldb(cs_u, toff, kRowBytes * 5 * (m1 + 1 + 5 * m2));
-                        }
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                    double2 t[5];
-#pragma unroll
-                    for (int m2 = 0; m2 < 5; ++m2) t[m2] = cmulf(xc[m2], cc[m2]);
-                    ibf5(t);
-                    v[m1] = t[0];
-#pragma unroll
-                    for (int kA = 1; kA < 5; ++kA)
-                        v[m1 + 5 * kA] = m1 ? cmul_conj(t[kA], make_double2(kW25X[m1 * kA], kW25Y[m1 * kA])) : t[kA];
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            } else if constexpr (TERMS == 1) {
+            if constexpr (TERMS == 1) {
 #pragma unroll
                 for (int m1 = 0; m1 < 5; ++m1) {
                     double2 xb[5], cb_[5];
                     if (m1 < 4) {
 #pragma unroll
                         for (int m2 = 0; m2 < 5; ++m2) {
-                            if (kEarly && kEarlyGroups > 1 && j == 1 && m1 == 0) {
-                                xb[m2] = xe[1][m2];
-                                cb_[m2] = ce[1][m2];
-                            } else {
-                                xb[m2] = ldb(xs_u, toff, 1600 * j + kRowBytes * 5 * (m1 + 1 + 5 * m2));
-                                cb_[m2] = ldb(cs_u, toff, 1600 * j + kRowBytes * 5 * (m1 + 1 + 5 * m2));
-                            }
+                            xb[m2] = ldb(xs_u, toff, 1600 * j + kRowBytes * 5 * (m1 + 1 + 5 * m2));
+                            cb_[m2] = ldb(cs_u, toff, 1600 * j + kRowBytes * 5 * (m1 + 1 + 5 * m2));
                         }
                     }
                     __builtin_amdgcn_sched_barrier(0);
@@ -445,12 +339,10 @@ __device__ __forceinline__ void one_unit(const Args& a, double2* lds4, const int
             }
             if (kEarly && j == 0) {
 #pragma unroll
-                for (int g = 0; g < kEarlyGroups; ++g)
-#pragma unroll
-                    for (int m2 = 0; m2 < 5; ++m2) {
-                        xe[g][m2] = ldb(xs_u, toff, 1600 + kRowBytes * 5 * (g + 5 * m2));
-                        ce[g][m2] = ldb(cs_u, toff, 1600 + kRowBytes * 5 * (g + 5 * m2));
-                    }
+                for (int m2 = 0; m2 < 5; ++m2) {
+                    xe[m2] = ldb(xs_u, toff, 1600 + kRowBytes * 25 * m2);
+                    ce[m2] = ldb(cs_u, toff, 1600 + kRowBytes * 25 * m2);
+                }
                 __builtin_amdgcn_sched_barrier(0);
             }
             // second stage of the 25-point transform and the twiddle between the column's two levels
@@ -493,7 +385,8 @@ __device__ __forceinline__ void one_unit(const Args& a, double2* lds4, const int
     __syncthreads();
     FUSED_STAMP(3);
 
-    // Y[k' + 25 q] = sum_r B_r[k'] w5^(r q) of one round, in place (a thread reads and writes its own five slots)
+    // Y[k' + 25 q] = sum_r B_r[k'] w5^(r q) of one round, in place (a thread reads and writes its own five slots).  A phase
+    // of its own: merged into the round before's second row stage, or run beside it by waves 4-7, it measured slower.
     auto y_in_place = [&](double2* X) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
@@ -506,37 +399,6 @@ __device__ __forceinline__ void one_unit(const Args& a, double2* lds4, const int
             for (int q = 0; q < 5; ++q) col[q * N2] = t5[q];
         }
     };
-    // FUSED_SPLIT_S2Y (whole transforms; round 6; OFF: see the switch).  The Y step is LDS traffic with a sliver of arithmetic, the second row stage
-    // arithmetic with a sliver of LDS traffic, and as phases of their own -- every wave in both, a barrier between -- neither
-    // covers the other (2.5 k + 2.1 k cycles per round).  Round rho + 1's Y step needs nothing of round rho but its first
-    // stage's stores into the other buffer: waves 4-7 do it (four butterflies per thread: 250 threads x 4 = the 1000 of a
-    // round) WHILE waves 0-3 do both halves of round rho's second stage one after the other -- every SIMD holds one wave
-    // of each kind.
-    constexpr bool kSplit = FUSED_SPLIT_S2Y && WHOLE && !FUSED_MERGE_Y;
-    auto y_by_upper_waves = [&](double2* X) {
-        const int ty = t_ - 256;
-        if (ty >= 0 && ty < 250) {
-            const int yr = ty / 50, yc = ty - 50 * yr;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                double2* const col = X + (5 * yr) * N2 + yc + 50 * j;
-                double2 t5[5];
-#pragma unroll
-                for (int rr = 0; rr < 5; ++rr) t5[rr] = col[rr * N2];
-                ibf5(t5);
-#pragma unroll
-                for (int q = 0; q < 5; ++q) col[q * N2] = t5[q];
-            }
-        }
-    };
-    // the row's four-step twiddle w_N^(k1 (e + 20 m)) = base * step^m: two scattered table reads per round, requested
-    // a phase ahead
-#if FUSED_MERGE_Y
-    if (live) y_in_place(lds4);
-    if (tid < 180) tab[tid] = twi((N / 200) * ((tid % 20) * (tid / 20 + 1)));   // (every w125 read lies before the last barrier)
-    __syncthreads();
-    FUSED_STAMP(4);
-#endif
 
     double best_sq = -1.0, best_x = 0.0, best_y = 0.0;
     int best_k = -1;
@@ -562,18 +424,15 @@ __device__ __forceinline__ void one_unit(const Args& a, double2* lds4, const int
         const bool live1 = r1_ >= 0, live2 = r2_ >= 0;
         const int ri = r1_ & 31, re = (r1_ >> 5) & 31, sw1 = (r1_ >> 10) & 7, k1b = (r1_ >> 13) & 127;
         const int si = r2_ & 31, sk = (r2_ >> 5) & 15, sw2 = (r2_ >> 10) & 7, kf0 = (r2_ >> 13) & 4095;
+        // the row's four-step twiddle w_N^(k1 (e + 20 m)) = base * step^m: two scattered table reads per round, requested
+        // a phase ahead
         const double2 tw_base = twi((rho + k1b) * re), tw_step = twi(20 * (rho + k1b));
-#if !FUSED_MERGE_Y
-        // (kSplit: rounds 1-4 had their Y step done by waves 4-7 during the round before's second row stage, barrier included)
-        if (!kSplit || rho == 0) {
-            if (live) y_in_place(X);
-            // w200^(e k''), k'' = 1..9, stored [k'' - 1][e]: the sixteen lanes of a read group take sixteen consecutive entries
-            // (indexed e * k'' the strides 2, 4, 6, 8 cost 2-, 4-, 2-, 8-way conflicts: 1.6 k cycles per transform)
-            if ((rho == 0 || !WHOLE) && tid < 180) tab[tid] = twi((N / 200) * ((tid % 20) * (tid / 20 + 1)));   // (every w125 read lies before the last barrier)
-            __syncthreads();
-        }
+        if (live) y_in_place(X);
+        // w200^(e k''), k'' = 1..9, stored [k'' - 1][e]: the sixteen lanes of a read group take sixteen consecutive entries
+        // (indexed e * k'' the strides 2, 4, 6, 8 cost 2-, 4-, 2-, 8-way conflicts: 1.6 k cycles per transform)
+        if ((rho == 0 || !WHOLE) && tid < 180) tab[tid] = twi((N / 200) * ((tid % 20) * (tid / 20 + 1)));   // (every w125 read lies before the last barrier)
+        __syncthreads();
         FUSED_STAMP(4);
-#endif
         // ---- rows, first stage (reads first; then the parked round rho + 1 moves into the buffer round rho - 1 has
         // left -- its stores drain while the transform computes)
         double2 z[10];
@@ -624,147 +483,100 @@ __device__ __forceinline__ void one_unit(const Args& a, double2* lds4, const int
         }
         __syncthreads();
         FUSED_STAMP(6);
-        if constexpr (kPf) {
-            // (FUSED_PREFETCH_UNIT) every parked round has moved into its buffer: 120 registers are free from here to the
-            // unit's end -- the next whole unit's first three operand groups go into them
-            if (rho == 3 && pf->next_whole) {                  // (uniform: a per-lane condition would keep the old values alive in the lanes it leaves out; the twelve spare lanes read column 0)
-                const Operand nxs = make_operand(a.spec + (a.spec_off ? (size_t)next_spec : (size_t)pf->next_bin * NF));
-                const Operand ncs = make_operand(a.code_spec + (size_t)pf->next_prn * NF);
-#pragma unroll
-                for (int g = 0; g < kPfGroups; ++g)
-#pragma unroll
-                    for (int m2 = 0; m2 < 5; ++m2) {
-                        pf->x[g][m2] = ldb(nxs, toff, kRowBytes * 5 * (g + 5 * m2));
-                        pf->c[g][m2] = ldb(ncs, toff, kRowBytes * 5 * (g + 5 * m2));
-                    }
-                __builtin_amdgcn_sched_barrier(0);
-            } else if (rho == 3) {
-                // (no next whole unit: the registers are "defined" all the same -- an empty statement -- so that on no path
-                // this unit's consumed operands count as alive from the column stage to the next unit)
-#pragma unroll
-                for (int g = 0; g < kPfGroups; ++g)
-#pragma unroll
-                    for (int m2 = 0; m2 < 5; ++m2)
-                        asm volatile("" : "=v"(pf->x[g][m2].x), "=v"(pf->x[g][m2].y), "=v"(pf->c[g][m2].x), "=v"(pf->c[g][m2].y));
-            }
-        }
-        // ---- rows, second stage: 20 = 2 x 10, radix-2 decimation in frequency while reading; and the next round's Y
-        // in place in the other buffer (its stores overlap this stage's arithmetic)
+        // ---- rows, second stage: 20 = 2 x 10, radix-2 decimation in frequency while reading
         double2 u[10];
-        if (kSplit && tid >= 256) {
-            if (rho < 4) y_by_upper_waves(Xo);              // (waves 4-7: the next round's Y step, in the other buffer)
-        } else {
-#pragma unroll 1
-            for (int hh = 0; hh < (kSplit ? 2 : 1); ++hh) {  // (kSplit: both halves by the same lane, one after the other)
-                const int hcur = kSplit ? hh : h;
-            if (live2) {
-                // element (e, k'') of the row sits at (10 e + k'') ^ swizzle: with e = 4 a + q that is ((k'' + 2 q) ^ swizzle) + 40 a + 8 q
-                // -- four per-lane places, the rest a constant
-                const double2* __restrict__ const row = X + si * N2;
-                const double2* __restrict__ const rowq[4] = {row + (sk ^ sw2), row + ((sk + 2) ^ sw2), row + ((sk + 4) ^ sw2), row + ((sk + 6) ^ sw2)};
+        if (live2) {
+            // element (e, k'') of the row sits at (10 e + k'') ^ swizzle: with e = 4 a + q that is ((k'' + 2 q) ^ swizzle) + 40 a + 8 q
+            // -- four per-lane places, the rest a constant
+            const double2* __restrict__ const row = X + si * N2;
+            const double2* __restrict__ const rowq[4] = {row + (sk ^ sw2), row + ((sk + 2) ^ sw2), row + ((sk + 4) ^ sw2), row + ((sk + 6) ^ sw2)};
 #pragma unroll
-                for (int t0 = 0; t0 < 10; t0 += 5) {     // (five pairs of reads in flight: registers)
-                    double2 lo[5], hi[5];
+            for (int t0 = 0; t0 < 10; t0 += 5) {     // (five pairs of reads in flight: registers)
+                double2 lo[5], hi[5];
 #pragma unroll
-                    for (int t = 0; t < 5; ++t) {
-                        const int e_lo = t0 + t, e_hi = t0 + t + 10;
-                        lo[t] = rowq[e_lo & 3][10 * e_lo - 2 * (e_lo & 3)];
-                        hi[t] = rowq[e_hi & 3][10 * e_hi - 2 * (e_hi & 3)];
-                    }
+                for (int t = 0; t < 5; ++t) {
+                    const int e_lo = t0 + t, e_hi = t0 + t + 10;
+                    lo[t] = rowq[e_lo & 3][10 * e_lo - 2 * (e_lo & 3)];
+                    hi[t] = rowq[e_hi & 3][10 * e_hi - 2 * (e_hi & 3)];
+                }
 #pragma unroll
-                    for (int t = 0; t < 5; ++t) u[t0 + t] = hcur ? csub(lo[t], hi[t]) : cadd(lo[t], hi[t]);
-                    __builtin_amdgcn_sched_barrier(0);
+                for (int t = 0; t < 5; ++t) u[t0 + t] = h ? csub(lo[t], hi[t]) : cadd(lo[t], hi[t]);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if (h) {
+#pragma unroll
+                for (int t = 1; t < 10; ++t) u[t] = cmul_conj(u[t], make_double2(kW20X[t], kW20Y[t]));
+            }
+            idft10c(u);
+            const int k_first = kf0 + rho;
+            double sqv[10];
+#pragma unroll
+            for (int g = 0; g < 10; ++g) {
+                sqv[g] = __builtin_fma(u[g].x, u[g].x, u[g].y * u[g].y);
+                if constexpr (SECOND) {        // (a column the peak comparison excludes never becomes a candidate: -2 loses against -1)
+                    const int k = TERMS * (k_first + 20 * N1 * (g / 2 + 5 * (g % 2))) + par;     // (sample of the whole row)
+                    sqv[g] = (k < a1 || (k >= b0 && k < b1)) ? sqv[g] : -2.0;
                 }
             }
-#if FUSED_MERGE_Y
-            if (rho < 4 && live) y_in_place(Xo);
-#ifdef FUSED_MERGE_SB
-            __builtin_amdgcn_sched_barrier(0);
+            const double m01 = fmax(sqv[0], sqv[1]), m23 = fmax(sqv[2], sqv[3]), m45 = fmax(sqv[4], sqv[5]), m67 = fmax(sqv[6], sqv[7]),
+                         m89 = fmax(sqv[8], sqv[9]);
+            const double round_max = fmax(fmax(fmax(m01, m23), fmax(m45, m67)), m89);
+            // (the lane's own best with the same margin: a value within 2^-48 of it must still meet it below)
+            const bool candidate = round_max >= fmax(floor_sq, best_sq * (1.0 - 0x1p-40));
+            if (__any(candidate)) {
+#ifdef SDR_FUSED_STAMPS
+                if (tid == 0) g_fused_stamps[blockIdx.x & 255][6] += 1000000;    // (diagnostic: rounds of wave 0 that keep books)
 #endif
-#endif
-            if (live2) {
-                if (hcur) {
-#pragma unroll
-                    for (int t = 1; t < 10; ++t) u[t] = cmul_conj(u[t], make_double2(kW20X[t], kW20Y[t]));
-                }
-                idft10c(u);
-                const int k_first = kf0 + rho + (kSplit ? N1 * 10 * hh : 0);
-                double sqv[10];
+                // Ordering by the squared magnitude.  A candidate within 2^-48 of the lane's best has to be compared through
+                // the scaled hypot -- the reference's np.abs -- with an exact tie keeping the smaller index (pcps_fast.h): the
+                // round is then redone from the state it started with by ONE run-time loop over a copy of the ten values
+                // (a private array: scratch memory, touched on this path alone).  Inlined per candidate that comparison
+                // made the kernel several times the instruction cache.
+                const double sq0 = best_sq, x0 = best_x, y0 = best_y;
+                const int k0 = best_k;
+                bool tie = false;
 #pragma unroll
                 for (int g = 0; g < 10; ++g) {
-                    sqv[g] = __builtin_fma(u[g].x, u[g].x, u[g].y * u[g].y);
-                    if constexpr (SECOND) {        // (a column the peak comparison excludes never becomes a candidate: -2 loses against -1)
-                        const int k = TERMS * (k_first + 20 * N1 * (g / 2 + 5 * (g % 2))) + par;     // (sample of the whole row)
-                        sqv[g] = (k < a1 || (k >= b0 && k < b1)) ? sqv[g] : -2.0;
-                    }
+                    const int p = g / 2 + 5 * (g % 2);
+                    const int k = k_first + 20 * N1 * p;              // code phase = position in the transform
+                    const double sq = sqv[g];
+                    const bool take = sq > best_sq;
+                    tie |= sq >= 0.0 && fabs(sq - best_sq) <= best_sq * 0x1p-48;
+                    best_sq = take ? sq : best_sq;
+                    best_x = take ? u[g].x : best_x;
+                    best_y = take ? u[g].y : best_y;
+                    best_k = take ? k : best_k;
                 }
-                const double m01 = fmax(sqv[0], sqv[1]), m23 = fmax(sqv[2], sqv[3]), m45 = fmax(sqv[4], sqv[5]), m67 = fmax(sqv[6], sqv[7]),
-                             m89 = fmax(sqv[8], sqv[9]);
-                const double round_max = fmax(fmax(fmax(m01, m23), fmax(m45, m67)), m89);
-                // (the lane's own best with the same margin: a value within 2^-48 of it must still meet it below)
-                const bool candidate = round_max >= fmax(floor_sq, best_sq * (1.0 - 0x1p-40));
-                if (__any(candidate)) {
-#ifdef SDR_FUSED_STAMPS
-                    if (tid == 0) g_fused_stamps[blockIdx.x & 255][6] += 1000000;    // (diagnostic: rounds of wave 0 that keep books)
-#endif
-                    // Ordering by the squared magnitude.  A candidate within 2^-48 of the lane's best has to be compared through
-                    // the scaled hypot -- the reference's np.abs -- with an exact tie keeping the smaller index (pcps_fast.h): the
-                    // round is then redone from the state it started with by ONE run-time loop over a copy of the ten values
-                    // (a private array: scratch memory, touched on this path alone).  Inlined per candidate that comparison
-                    // made the kernel several times the instruction cache.
-                    const double sq0 = best_sq, x0 = best_x, y0 = best_y;
-                    const int k0 = best_k;
-                    bool tie = false;
+                if (__builtin_expect(__any(tie), 0)) {
+                    double2 copy[10];
 #pragma unroll
+                    for (int g = 0; g < 10; ++g) copy[g] = u[g];
+                    best_sq = sq0;
+                    best_x = x0;
+                    best_y = y0;
+                    best_k = k0;
+#pragma unroll 1
                     for (int g = 0; g < 10; ++g) {
                         const int p = g / 2 + 5 * (g % 2);
-                        const int k = k_first + 20 * N1 * p;              // code phase = position in the transform
-                        const double sq = sqv[g];
-                        const bool take = sq > best_sq;
-                        tie |= sq >= 0.0 && fabs(sq - best_sq) <= best_sq * 0x1p-48;
-                        best_sq = take ? sq : best_sq;
-                        best_x = take ? u[g].x : best_x;
-                        best_y = take ? u[g].y : best_y;
-                        best_k = take ? k : best_k;
-                    }
-                    if (__builtin_expect(__any(tie), 0)) {
-                        double2 copy[10];
-#pragma unroll
-                        for (int g = 0; g < 10; ++g) copy[g] = u[g];
-                        best_sq = sq0;
-                        best_x = x0;
-                        best_y = y0;
-                        best_k = k0;
-#pragma unroll 1
-                        for (int g = 0; g < 10; ++g) {
-                            const int p = g / 2 + 5 * (g % 2);
-                            const int k = k_first + 20 * N1 * p;
-                            const double2 x = copy[g];
-                            double sq = __builtin_fma(x.x, x.x, x.y * x.y);
-                            if (SECOND && !(TERMS * k + par < a1 || (TERMS * k + par >= b0 && TERMS * k + par < b1))) sq = -2.0;
-                            bool take = sq > best_sq;
-                            if (sq >= 0.0 && fabs(sq - best_sq) <= best_sq * 0x1p-48) {
-                                const double m_new = hypot(x.x * a.scale, x.y * a.scale), m_old = hypot(best_x * a.scale, best_y * a.scale);
-                                take = m_new > m_old || (m_new == m_old && k < best_k);
-                            }
-                            best_sq = take ? sq : best_sq;
-                            best_x = take ? x.x : best_x;
-                            best_y = take ? x.y : best_y;
-                            best_k = take ? k : best_k;
+                        const int k = k_first + 20 * N1 * p;
+                        const double2 x = copy[g];
+                        double sq = __builtin_fma(x.x, x.x, x.y * x.y);
+                        if (SECOND && !(TERMS * k + par < a1 || (TERMS * k + par >= b0 && TERMS * k + par < b1))) sq = -2.0;
+                        bool take = sq > best_sq;
+                        if (sq >= 0.0 && fabs(sq - best_sq) <= best_sq * 0x1p-48) {
+                            const double m_new = hypot(x.x * a.scale, x.y * a.scale), m_old = hypot(best_x * a.scale, best_y * a.scale);
+                            take = m_new > m_old || (m_new == m_old && k < best_k);
                         }
+                        best_sq = take ? sq : best_sq;
+                        best_x = take ? x.x : best_x;
+                        best_y = take ? x.y : best_y;
+                        best_k = take ? k : best_k;
                     }
                 }
             }
-            }
         }
-        if (kSplit && rho < 4) __syncthreads();             // (the Y step's stores; and this round's readers are done with X, which round rho + 1 overwrites)
-#if FUSED_MERGE_Y
-        if (rho < 4) __syncthreads();   // (the last round's readers meet the next transform's first barrier)
-#endif
         FUSED_STAMP(7);
     }
-    if constexpr (kPf)
-        pf->have = pf->next_whole;                              // (what was requested in round 3 is the next unit's)
     int best_i = 0x7fffffff;
     double best_v = -1.0;
     if (role2 >= 0 && best_k >= 0) {
@@ -785,21 +597,17 @@ __global__ __launch_bounds__(kThreads) void ifft_max_kernel(const Args a) {
     extern __shared__ double2 lds4[];
 #ifdef SDR_FUSED_STAMPS
     unsigned long long stamp_ = __builtin_amdgcn_s_memtime();
-#define FUSED_STAMP_ARG , 0, 0, 0, par, nullptr, stamp_
-#define FUSED_STAMP_ARG_PF , 0, 0, 0, par, &pf, stamp_
+#define FUSED_STAMP_ARG , 0, 0, 0, par, stamp_
 #else
 #define FUSED_STAMP_ARG , 0, 0, 0, par
-#define FUSED_STAMP_ARG_PF , 0, 0, 0, par, &pf
 #endif
     const int tid = threadIdx.x;
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
     if (blockIdx.x == 0)
         for (int p = tid; p < a.n_prn; p += kThreads) a.theta_next[p] = 0ull;
     const int w_end = a.xcd_first[xcd + 1];
-    // (requesting the NEXT unit's list entry a unit ahead by itself measured 0.2037 against 0.2023 ms per search at 25 MHz: the
-    // other waves cover those latencies; it is read ahead here because FUSED_PREFETCH_UNIT needs to know the next unit)
-    UnitPrefetch pf;
-    pf.have = false;
+    // (requesting the NEXT unit's list entry a unit ahead measured 0.2037 against 0.2023 ms per search at 25 MHz: the other
+    // waves cover those latencies)
     for (int w = a.xcd_first[xcd] + slot; w < w_end; w += kSlotsPerXcd) {
         // (wave-uniform: scalar base addresses in the unit)
         const int prn = __builtin_amdgcn_readfirstlane(a.work[w].prn);
@@ -807,26 +615,10 @@ __global__ __launch_bounds__(kThreads) void ifft_max_kernel(const Args a) {
         if (TERMS == 2 && bin >= a.nbins) bin -= a.nbins, par = 1;            // (virtual bin = parity * nbins + bin)
         const int mode = __builtin_amdgcn_readfirstlane(a.work[w].round);     // -1: the whole transform; else its rounds r0 | r1 << 4
         const int rec_slot = __builtin_amdgcn_readfirstlane(a.work[w].record);
-        pf.next_whole = false;
-        pf.next_prn = pf.next_bin = 0;
-        if (FUSED_PREFETCH_UNIT > 0 && TERMS == 1 && w + kSlotsPerXcd < w_end) {
-            pf.next_whole = __builtin_amdgcn_readfirstlane(a.work[w + kSlotsPerXcd].round) < 0;
-            pf.next_prn = __builtin_amdgcn_readfirstlane(a.work[w + kSlotsPerXcd].prn);
-            pf.next_bin = __builtin_amdgcn_readfirstlane(a.work[w + kSlotsPerXcd].bin);
-        }
-        if (mode < 0) {
-            one_unit<true, false, TERMS, true>(a, lds4, tid, prn, bin, mode, rec_slot FUSED_STAMP_ARG_PF);
-        } else {
-            // (nothing requested ahead lives across a short unit: "defined" here by an empty statement, so that the register
-            // allocator does not carry thirty operands through this body)
-#pragma unroll
-            for (int g = 0; g < kPfGroups; ++g)
-#pragma unroll
-                for (int m2 = 0; m2 < 5; ++m2)
-                    asm volatile("" : "=v"(pf.x[g][m2].x), "=v"(pf.x[g][m2].y), "=v"(pf.c[g][m2].x), "=v"(pf.c[g][m2].y));
+        if (mode < 0)
+            one_unit<true, false, TERMS>(a, lds4, tid, prn, bin, mode, rec_slot FUSED_STAMP_ARG);
+        else
             one_unit<false, false, TERMS>(a, lds4, tid, prn, bin, mode, rec_slot FUSED_STAMP_ARG);
-            pf.have = false;
-        }
     }
 }
 
@@ -915,7 +707,7 @@ __global__ __launch_bounds__(kThreads) void ifft_second_kernel(const SecondArgs 
     __syncthreads();                     // (the record scratch is the first buffer)
 #ifdef SDR_FUSED_STAMPS
     unsigned long long stamp_ = __builtin_amdgcn_s_memtime();
-    one_unit<false, true, TERMS>(s.a, lds4, tid, prn, bin, rounds, prn * kUnits + unit, a1, b0, b1, par, nullptr, stamp_);
+    one_unit<false, true, TERMS>(s.a, lds4, tid, prn, bin, rounds, prn * kUnits + unit, a1, b0, b1, par, stamp_);
 #else
     one_unit<false, true, TERMS>(s.a, lds4, tid, prn, bin, rounds, prn * kUnits + unit, a1, b0, b1, par);
 #endif

@@ -1,5 +1,7 @@
-// The closed-loop kernel for more channels than compute units: see the SDR_TRACK_DENSE_TU block of track.hip.
-#define SDR_TRACK_DENSE_TU 1
+// The closed-loop kernel for more channels than compute units, in a translation unit of its own: 256-thread workgroups
+// capped at 168 registers so that THREE share a CU.  It is compiled with -mllvm -disable-machine-licm: hoisting the fp64
+// polynomial constants of sincos / atan / division out of the epoch loop parks ~80 of them in VGPRs for the whole kernel
+// (256 instead of 173 registers).
 #ifdef SDR_TRACE_DENSE   // (diagnostics: the per-phase clocks of THIS unit's kernels, under their own names)
 #define SDR_TRACE_TRACK 1
 #define g_track_phase g_track_phase_dense
@@ -7,4 +9,21 @@
 #else
 #undef SDR_TRACE_TRACK  // (the per-phase clocks of the debug build live in track.hip's own translation unit)
 #endif
-#include "track.hip"
+#include "track_kernel.h"
+
+hipError_t sdr_track_dense_launch(int fmt, int n_taps, int n_ch, size_t shmem, hipStream_t stream, void** args) {
+    auto launch = [&](auto kernel) {
+        (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+        return hipLaunchKernel((const void*)kernel, dim3(n_ch), dim3(256), args, shmem, stream);
+    };
+    auto by_taps = [&](auto fmt_c) {
+        constexpr int F = decltype(fmt_c)::value;
+        return n_taps == 5 ? launch(track_kernel<F, 256, 3, 5>) : launch(track_kernel<F, 256, 3, 3>);
+    };
+    switch (fmt) {
+        case SDR_FMT_CI8: return by_taps(std::integral_constant<int, SDR_FMT_CI8>{});
+        case SDR_FMT_CI16: return by_taps(std::integral_constant<int, SDR_FMT_CI16>{});
+        case SDR_FMT_CF32: return by_taps(std::integral_constant<int, SDR_FMT_CF32>{});
+        default: return by_taps(std::integral_constant<int, SDR_FMT_CF64>{});
+    }
+}

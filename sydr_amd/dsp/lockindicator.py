@@ -1,7 +1,7 @@
 """Host-side scalar lock indicators and C/N0 estimators under the names and signatures of
 sydr/dsp/lockindicator.py:6-122.
 
-On the product path these run on the device every epoch (sydr_amd/csrc/track.hip); the host functions exist
+On the product path these run on the device every epoch (sydr_amd/csrc/track_kernel.h); the host functions exist
 for callers that use them one at a time (a reference plugin behind the seams mixin, notebooks, the database
 report) and are pinned bit for bit against values captured from the reference (tests/golden/g7_loopmath.npz).
 Every expression keeps the reference's operation order: the results feed thresholds."""

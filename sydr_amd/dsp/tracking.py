@@ -2,7 +2,7 @@
 
 `EPL` (tracking.py:92-116) -- the sample-touching function -- runs on the GPU.  The scalar discriminators and
 loop filters (tracking.py:39-61,120-186,246-325) run on the DEVICE in closed-loop tracking
-(sydr_amd/csrc/track.hip); the host functions below carry the reference's names and signatures for callers
+(sydr_amd/csrc/track_kernel.h); the host functions below carry the reference's names and signatures for callers
 that use them one at a time (a reference plugin behind the GpuCorrelatorSeams mixin may import either), and
 are pinned bit for bit against values captured from the reference (tests/golden/g7_loopmath.npz).  They keep
 the reference's operation order and its GPS-ICD pi: their results feed thresholds and NCOs.

@@ -1,5 +1,5 @@
 /* a / b with y = RN(1/b): q0 = a*y, two FMA-residual corrections; compared with the IEEE quotient.
- * Mirrors div_by() of sydr_amd/csrc/track.hip.  Test infrastructure (tests/test_div_by_constant.py). */
+ * Mirrors div_by() of sydr_amd/csrc/track_kernel.h.  Test infrastructure (tests/test_div_by_constant.py). */
 #include <math.h>
 #include <stdio.h>
 #include <stdint.h>

@@ -1,5 +1,5 @@
 """The closed-loop kernel divides by run constants (fs, GPS 2*pi, the epoch duration) with a precomputed
-reciprocal and two FMA corrections (track.hip: div_by) and claims the SAME bits as an IEEE division.  This
+reciprocal and two FMA corrections (track_kernel.h: div_by) and claims the SAME bits as an IEEE division.  This
 checks the identity on the CPU -- same IEEE-754 double arithmetic, hardware or correctly rounded software fma --
 for the denominators a receiver meets, on 10^6 random numerators each here (the committed C program runs 4*10^7
 per denominator when called without an argument: 0 mismatches in 6*10^8)."""

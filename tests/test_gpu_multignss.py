@@ -101,7 +101,7 @@ def test_device_synth_of_staged_boc_code_correlates(engine):
 
 
 # ------------------------------------------------------------------------------------------------ closed loop
-# Loop closure on the device for the configs-4/5 geometry (track.hip templated on the tap count; chips per epoch,
+# Loop closure on the device for the configs-4/5 geometry (track_kernel.h, templated on the tap count; chips per epoch,
 # epochs per symbol and the epoch duration are per-channel configuration).  Checked against the oracle's
 # generalised loops, which reduce bit for bit to the reference's trajectories at 3 taps / 1023 chips / 20 / 1 ms
 # (tests/test_oracle_golden.py::test_generalised_loop_reduces_to_the_reference).
