@@ -90,9 +90,9 @@ int sdr_prof_read(sdr_engine* e, const char* prefix, double* total_ms, int64_t* 
 int sdr_prof_reset(sdr_engine* e);
 
 /* Diagnostic switches (tests, A/B timing): "pcps_materialise_map" = 1 writes the whole correlation map even when the
- * caller asks for indices and ratio only; "pcps_radix_passes" = 1 runs one kernel per radix pass instead of the
- * four-step transform; "pcps_general_kernels" = 1 keeps the general four-step kernels where the register-resident
- * 125 x 200 ones would run; "pcps_prn_chunk" = n searches n PRNs per inverse sweep; "pcps_one_stream" = 1 keeps the sweeps of a map-free search on one stream;
+ * caller asks for indices and ratio only; "pcps_general_kernels" = 1 keeps the general four-step kernels where the
+ * register-resident 125 x 200 ones would run; "pcps_prn_chunk" = n searches n PRNs per inverse sweep; "pcps_one_stream" = 1
+ * keeps the sweeps of a map-free search on one stream;
  * "pcps_fused" = 0 keeps a map-free search at 25 MHz on the two-kernel sweeps where one launch of persistent workgroups, one
  * (PRN, bin) transform per workgroup, would run (256 transforms or more); "pcps_no_spectra_cache" = 1
  * recomputes conj(fft(code)) in every search, as the reference does (channel_l1ca_kaplan.py:184-185), instead of keeping

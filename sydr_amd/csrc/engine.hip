@@ -252,11 +252,9 @@ extern "C" {
 int sdr_set_option(sdr_engine* e, const char* name, int value) {
     if (!e || !name) return sdr_fail(SDR_ERR_INVALID, "NULL engine or option name");
     if (!strcmp(name, "pcps_materialise_map")) e->pcps_force_map = value != 0;
-    else if (!strcmp(name, "pcps_radix_passes")) e->pcps_force_passes = value != 0;
     else if (!strcmp(name, "pcps_general_kernels")) e->pcps_no_fast = value != 0;
     else if (!strcmp(name, "pcps_one_stream")) e->pcps_no_overlap = value != 0;
     else if (!strcmp(name, "pcps_fused")) e->pcps_fused = value != 0;
-    else if (!strcmp(name, "pcps_general_second_sweep")) e->pcps_slow_second = value != 0;
     else if (!strcmp(name, "pcps_no_spectra_cache")) e->pcps_no_spec_cache = value != 0;
     else if (!strcmp(name, "ingest_by_copy_command")) e->ingest_by_copy = value != 0;
     else if (!strcmp(name, "track_one_launch_tick")) e->track_one_launch_tick = value != 0;

@@ -98,8 +98,6 @@ struct sdr_engine {
     DevBuf pcps_fwd, pcps_a, pcps_b, pcps_code, pcps_tw, pcps_map, pcps_csum, pcps_part, pcps_res;
     DevBuf pcps_code2;            // N = 50 000, fused search: [prn][parity][N] -- the spectra and their image with the odd half's twiddle (pcps_fused.h)
     bool pcps_code2_ok = false;   // ... made from what pcps_code holds now
-    bool pcps_shared = false;     // the search in flight read shared spectra (its second sweep reads them the same way)
-    const long long* pcps_shared_off = nullptr;
     DevBuf pcps_spec_off;         // shared spectra: every bin's element offset into the padded class spectra (pcps.hip)
     std::vector<int64_t> pcps_spec_off_key;
     bool pcps_no_shared_spectra = false;   // "pcps_no_shared_spectra": one forward transform per bin, as before round 5
@@ -108,11 +106,7 @@ struct sdr_engine {
     DevBuf track_state, track_cfg;
     int n_cus = 0;              // compute units of the device (sizes the closed-loop clusters)
     int track_force_parts = 0;  // diagnostics / tests: 0 = choose, else 1, 2, 4 or 8 workgroups per channel
-    void* pcps_res_direct = nullptr;  // during sdr_pcps: page-locked block the peak kernels write their results into
-    const void* pcps_slots_pinned = nullptr;   // ... the caller's slot numbers in it (copied to the device when spectra have to be made)
-    unsigned* pcps_done = nullptr;    // ... one word per PRN the fused second sweep raises to pcps_done_seq behind the PRN's results
-    unsigned pcps_done_seq = 0, pcps_done_counter = 0;
-    bool pcps_done_used = false;      // the search ended in a kernel that raises them
+    unsigned pcps_done_counter = 0;   // the last sequence number a search's done words were raised to (pcps.hip)
     void* slab_pinned = nullptr;  // page-locked staging of the slab a receiver tick brings (sdr_bank_tick)
     size_t slab_bytes = 0;        // bytes of ONE of its two halves
     int slab_flip = 0;
@@ -159,8 +153,6 @@ struct sdr_engine {
     int64_t srv_slab_off = 0, srv_slab_n = 0;
     bool ingest_by_copy = false;     // "ingest_by_copy_command": queued slabs go into the ring by hipMemcpyAsync, not by the ingest kernel
     bool pcps_no_spec_cache = false; // "pcps_no_spectra_cache": conj(fft(code)) recomputed by every search, as the reference does (kaplan:184-185)
-    bool pcps_force_passes = false;  // diagnostics: use the one-kernel-per-radix-pass transform instead of the four-step one
-    bool pcps_slow_second = false;   // "pcps_general_second_sweep": peak kernel + general four-step pair where the fused second sweep would run
     bool pcps_fused = true;          // map-free search at N = 125 x 200 of a round of 256 transforms or more: one workgroup per (PRN, bin) transform (pcps_fused.h); "pcps_fused" = 0: the two-kernel sweeps
     DevBuf pcps_work;                // its work list (transform numbers in processing order)
     int pcps_work_prn = 0, pcps_work_bins = 0, pcps_work_block = 0;   // ... and the grid / block shape it was made for
@@ -239,11 +231,13 @@ int sdr_pcps_fused_records_per_prn(int n_prn, int nbins, int terms);
 // forward spectra, records = n_prn * nbins * SDR_PCPS_FUSED10K_RECORD_BYTES bytes of scratch; the results go to out_*.
 #define SDR_PCPS_FUSED10K_RECORD_BYTES 32
 // (spec_off / blk_stride: shared spectra, as above; nullptr / nbins * N: one spectrum per bin)
+// done (nullable): one page-locked word per PRN, raised to done_seq behind the PRN's results
 int sdr_pcps_fused10k_search(sdr_engine* e, const void* F_all, const void* spec_off, long long blk_stride, const void* C, const void* tw, int n_prn,
-                             int nbins, int noncoh, int N, int spc, void* records, void* out_bin, void* out_code, void* out_ratio);
+                             int nbins, int noncoh, int N, int spc, void* records, void* out_bin, void* out_code, void* out_ratio,
+                             unsigned* done, unsigned done_seq);
 // The second sweep of such a search in one launch: the first peaks from `recs` ([n_prn][per_prn] records) into tops / dev_bin /
 // dev_code, and 5 x SDR_PCPS_FUSED_RECORDS records per PRN of its winning row's allowed columns into `seconds`.
-// ... and TwoCorrelationPeakComparison's results (bin, code phase, ratio of the two peaks) into res_*.
+// ... and TwoCorrelationPeakComparison's results (bin, code phase, ratio of the two peaks) into res_*; done: as above.
 int sdr_pcps_fused_second(sdr_engine* e, const void* F, const void* spec_off, const void* C, const void* tw, int n_prn, int N, int spc, const void* recs,
                           int per_prn, void* tops, void* dev_bin, void* dev_code, void* seconds, void* res_bin, void* res_code,
-                          void* res_ratio);
+                          void* res_ratio, unsigned* done, unsigned done_seq);

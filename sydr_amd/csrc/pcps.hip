@@ -939,16 +939,18 @@ void run_four_step_t(sdr_engine* e, const FourStep& f, PassArgs a, int batch, do
 #define SDR_PCPS_COL_TILE 8
 #endif
 constexpr int kRowTile = SDR_PCPS_ROW_TILE;
-inline bool fast25k_applies(const sdr_engine* e, const FourStep& f) {
-    return f.ok && f.N1 == fast25k::N1 && f.N2 == fast25k::N2 && !e->pcps_no_fast;
-}
-// the register-resident kernels of either header serve this length (they split it as N1 x 200 themselves)
-inline bool fast_applies(const sdr_engine* e, const FourStep& f) {
-    return fast25k_applies(e, f) || (f.ok && fastn::handles(f.N1 * f.N2) && !e->pcps_no_fast);
-}
+// How a transform of length N is done: the four-step pair where the planner splits N, else one kernel per radix pass
+// (plan_pcps).  `fast`: the register-resident kernels of either header run the inverse transforms of a search at 4 / 10 /
+// 25 / 50 MHz instead (they split N as N1 x 200 themselves).
+enum FastKernels { FAST_NONE = 0, FAST_25K, FAST_N };
+struct Xform {
+    std::vector<int> radices;
+    FourStep four;
+    FastKernels fast = FAST_NONE;
+};
 template <int STORE = STORE_MAG_MAX>
-inline void fast_run(sdr_engine* e, const FourStep& f, PassArgs a, int batch, double2* Z, hipStream_t stream) {
-    if (fast25k_applies(e, f)) {
+inline void fast_run(sdr_engine* e, const Xform& t, PassArgs a, int batch, double2* Z, hipStream_t stream) {
+    if (t.fast == FAST_25K) {
         if constexpr (STORE == STORE_MAG_MAX) {
             fast25k::run(e, a, batch, Z, stream);
         } else {
@@ -956,15 +958,15 @@ inline void fast_run(sdr_engine* e, const FourStep& f, PassArgs a, int batch, do
             fastn::run_rows<fast25k::N1, STORE>(a, batch, Z, stream);
         }
     } else {
-        fastn::run<STORE>(f.N1 * f.N2, a, batch, Z, stream);
+        fastn::run<STORE>(t.four.N1 * t.four.N2, a, batch, Z, stream);
     }
 }
 template <bool INV, int LOAD0, int STORE_LAST, int FMT>
-void run_four_step(sdr_engine* e, const FourStep& f, PassArgs a, int batch, double2* Z, double2* final_out) {
+void run_four_step(sdr_engine* e, const Xform& t, PassArgs a, int batch, double2* Z, double2* final_out) {
     if constexpr (INV && LOAD0 == LOAD_MUL_CODE &&
                   (STORE_LAST == STORE_MAG_MAX || STORE_LAST == STORE_MAG_ACC || STORE_LAST == STORE_CPLX_ACC)) {
-        if (fast_applies(e, f)) {         // the inverse transforms of a search at 4 / 10 / 25 / 50 MHz
-            fast_run<STORE_LAST>(e, f, a, batch, Z, e->stream);
+        if (t.fast) {         // the inverse transforms of a search at 4 / 10 / 25 / 50 MHz
+            fast_run<STORE_LAST>(e, t, a, batch, Z, e->stream);
             return;
         }
     }
@@ -972,31 +974,14 @@ void run_four_step(sdr_engine* e, const FourStep& f, PassArgs a, int batch, doub
         // a handful of forward transforms (shared spectra: four for a 250 Hz grid) are a chain of latencies, not work: narrower
         // column tiles put twice as many workgroups on its first half
         if (batch <= 8) {           // (measured: 0.2179 -> 0.2159 ms per 32-PRN call at 25 MHz, 0.4863 -> 0.4833 at 50 MHz)
-            run_four_step_t<INV, LOAD0, STORE_LAST, FMT, 4, 4>(e, f, a, batch, Z, final_out);
+            run_four_step_t<INV, LOAD0, STORE_LAST, FMT, 4, 4>(e, t.four, a, batch, Z, final_out);
             return;
         }
     }
-    run_four_step_t<INV, LOAD0, STORE_LAST, FMT, SDR_PCPS_COL_TILE, kRowTile>(e, f, a, batch, Z, final_out);
+    run_four_step_t<INV, LOAD0, STORE_LAST, FMT, SDR_PCPS_COL_TILE, kRowTile>(e, t.four, a, batch, Z, final_out);
 }
 // per-wave records one map-free inverse sweep leaves per transform
 inline int records_per_transform(const FourStep& f) { return ((f.N1 + kRowTile - 1) / kRowTile) * (kThreads / 64); }
-// ... and of the main sweep, which may run the register-resident kernels
-// operand terms per point of the one-workgroup-per-transform sweep: 1 at N = 25 000, 2 at N = 50 000 (a radix-2 step in
-// front of two 25 000-point transforms, pcps_fused.h), 0 = the sweep does not serve this length
-inline int fused_terms(const sdr_engine* e, const FourStep& f) {
-    if (!e->pcps_fused || !f.ok || e->pcps_no_fast) return 0;
-    if (f.N1 == fast25k::N1 && f.N2 == fast25k::N2) return 1;
-    return f.N1 * f.N2 == 2 * fast25k::N ? 2 : 0;
-}
-// The fused sweep takes a map-free search whole when it fills at least one round of its 256 persistent workgroups (a
-// smaller search is quicker through the two-kernel path: ~8 us + 0.19 us per transform against ~35 us per round).
-inline bool fused_takes(const sdr_engine* e, const FourStep& f, int n_prn, int nbins) {
-    return fused_terms(e, f) * n_prn * nbins >= 256;
-}
-inline int records_main_sweep(const sdr_engine* e, const FourStep& f) {
-    if (fast25k_applies(e, f)) return fast25k::kRecordsPerTransform;
-    return fast_applies(e, f) ? fastn::records(f.N1 * f.N2) : records_per_transform(f);
-}
 
 /* ------------------------------------------------------------------------------------------------
  * Chirp-z (Bluestein) transform for a length N the planner cannot factor (a prime factor above 64):
@@ -1014,7 +999,7 @@ struct BluPlan {
     const double2* spec_inv = nullptr;  // FFT_M of the inverse kernel, [M]
     const double2* twM = nullptr;     // twiddles of the length-M transform
     double2 *x = nullptr, *a = nullptr, *b = nullptr;  // [max batch][M] work buffers
-    std::vector<int> radM;
+    const Xform* xm = nullptr;        // the length-M transform
 };
 
 __global__ __launch_bounds__(kThreads) void blu_chirp_kernel(double2* chirp, double2* kern_fwd, double2* kern_inv, int N, int M) {
@@ -1073,8 +1058,8 @@ __global__ __launch_bounds__(kThreads) void blu_post_kernel(const PassArgs a, co
 // Runs all passes of one batched transform.  `first` carries the fused load of
 // pass 0, `last_store` the fused store of the final pass.  Ping-pongs bufA/bufB.
 template <bool INV, int LOAD0, int STORE_LAST, int FMT>
-void run_fft(sdr_engine* e, const std::vector<int>& radices, PassArgs a, int batch, double2* bufA, double2* bufB,
-             double2* final_out, const char* prof_name, const BluPlan* blu = nullptr);
+void run_fft(sdr_engine* e, const Xform& t, PassArgs a, int batch, double2* bufA, double2* bufB, double2* final_out,
+             const char* prof_name, const BluPlan* blu = nullptr);
 
 template <bool INV, int LOAD0, int STORE_LAST, int FMT>
 void run_bluestein(sdr_engine* e, const BluPlan& blu, PassArgs a, int batch, double2* final_out) {
@@ -1086,25 +1071,25 @@ void run_bluestein(sdr_engine* e, const BluPlan& blu, PassArgs a, int batch, dou
     p.N = M;
     p.tw = blu.twM;
     p.in = blu.x;
-    run_fft<false, LOAD_PLAIN, STORE_PLAIN, FMT>(e, blu.radM, p, batch, blu.a, blu.b, blu.x, "pcps_bluestein_fft");
+    run_fft<false, LOAD_PLAIN, STORE_PLAIN, FMT>(e, *blu.xm, p, batch, blu.a, blu.b, blu.x, "pcps_bluestein_fft");
     hipLaunchKernelGGL(blu_mul_kernel, gm, dim3(kThreads), 0, e->stream, blu.x, INV ? blu.spec_inv : blu.spec_fwd, M);
-    run_fft<true, LOAD_PLAIN, STORE_PLAIN, FMT>(e, blu.radM, p, batch, blu.a, blu.b, blu.x, "pcps_bluestein_fft");
+    run_fft<true, LOAD_PLAIN, STORE_PLAIN, FMT>(e, *blu.xm, p, batch, blu.a, blu.b, blu.x, "pcps_bluestein_fft");
     hipLaunchKernelGGL((blu_post_kernel<STORE_LAST, INV>), gn, dim3(kThreads), 0, e->stream, a, blu.chirp, M, blu.x);
 }
 
 template <bool INV, int LOAD0, int STORE_LAST, int FMT>
-void run_fft(sdr_engine* e, const std::vector<int>& radices, PassArgs a, int batch, double2* bufA, double2* bufB,
-             double2* final_out, const char* prof_name, const BluPlan* blu) {
+void run_fft(sdr_engine* e, const Xform& t, PassArgs a, int batch, double2* bufA, double2* bufB, double2* final_out,
+             const char* prof_name, const BluPlan* blu) {
     ProfScope ps(e, prof_name);
     if (blu) {
         run_bluestein<INV, LOAD0, STORE_LAST, FMT>(e, *blu, a, batch, final_out);
         return;
     }
-    const FourStep four = plan_four_step(a.N);
-    if (four.ok && !e->pcps_force_passes) {
-        run_four_step<INV, LOAD0, STORE_LAST, FMT>(e, four, a, batch, bufA, final_out);
+    if (t.four.ok) {
+        run_four_step<INV, LOAD0, STORE_LAST, FMT>(e, t, a, batch, bufA, final_out);
         return;
     }
+    const std::vector<int>& radices = t.radices;
     const int np = (int)radices.size();
     int Ns = 1;
     const double2* src = a.in;
@@ -1136,280 +1121,425 @@ void run_fft(sdr_engine* e, const std::vector<int>& radices, PassArgs a, int bat
 // shift is a contiguous read H - j q elements into the row.
 struct SharedSpectra {
     int P = 0, q = 0, H = 0;            // P == 0: every bin has its own transform
-    const long long* off = nullptr;     // device: element offset of every bin's spectrum inside ITS BLOCK of P rows of H + N
 };
-inline int plan_shared_spectra(sdr_engine* e, int nbins, int N, double fs, double bin_delta, SharedSpectra* out) {
-    *out = SharedSpectra{};
-    if (e->pcps_no_shared_spectra || !(bin_delta > 0.0)) return SDR_OK;
+inline SharedSpectra plan_shared_spectra(const sdr_engine* e, int nbins, int N, double fs, double bin_delta) {
+    SharedSpectra s;
+    if (e->pcps_no_shared_spectra || !(bin_delta > 0.0)) return s;
     for (int P = 1; P <= 64 && 2 * P <= nbins; ++P) {
         const double v = (double)P * bin_delta * (double)N / fs, r = std::nearbyint(v);
         if (r >= 1.0 && std::fabs(v - r) <= 1e-9 * r && r * (double)((nbins - 1) / P) <= 4096.0) {
-            out->P = P, out->q = (int)r;
+            s.P = P, s.q = (int)r;
+            s.H = s.q * ((nbins - 1) / P);
             break;
         }
     }
-    if (!out->P) return SDR_OK;
-    out->H = out->q * ((nbins - 1) / out->P);
-    std::vector<int64_t> key = {(int64_t)N, (int64_t)nbins, (int64_t)out->P, (int64_t)out->q};
+    return s;
+}
+
+// ---- one search, planned once: its route, how one transform is done, how the PRNs are cut and every buffer size
+enum Route {
+    ROUTE_FUSED10K,  // N = 10 000, indices and ratio only: the forward transforms, then one launch for the rest (pcps_fused10k.h)
+    ROUTE_FUSED,     // map-free at N = 25 000 / 50 000, a round of 256 transforms or more: fused sweep + fused second sweep
+    ROUTE_SWEEPS,    // map-free: inverse sweeps that leave per-wave records, then the winning row of every PRN again
+    ROUTE_MAP,       // the map accumulated over the blocks, then its peaks (also every radix-pass and chirp-z length)
+};
+struct PcpsPlan {
+    int N = 0, spc = 0, nbins = 0, coh = 1, noncoh = 1, n_prn = 0;
+    double fs = 0.0, bin_start = 0.0, bin_delta = 0.0;
+    Xform xf;                  // the length-N transform
+    int M = 0;                 // chirp-z (Bluestein) length, 0 = none; xm its transform (plain loads: never `fast`)
+    Xform xm;
+    Route route = ROUTE_MAP;
+    int terms = 0;             // ROUTE_FUSED: operand terms per point (pcps_fused.h)
+    int prn_chunk = 0;         // PRNs per inverse sweep
+    bool overlap = false;      // ROUTE_SWEEPS: the sweeps alternate between two streams
+    SharedSpectra sh;          // (ROUTE_FUSED10K, ROUTE_FUSED only)
+    bool done_words = false;   // the search ends in a kernel that raises a done word per PRN behind its results
+    int records_sweep = 0;     // per-wave records a transform of the main inverse sweep leaves
+    int records_per_prn = 0;   // ... the first sweep leaves per PRN (map-free routes)
+    int records_second = 0;    // ... a transform of the second sweep leaves
+    size_t tbytes = 0, fwd_bytes = 0, work_bytes = 0, code_bytes = 0, code2_bytes = 0, map_bytes = 0, csum_bytes = 0,
+           part_bytes = 0, res_bytes = 0, pinned_bytes = 0, blu_bytes = 0, blu_work_bytes = 0;
+};
+
+// operand terms per point of the one-workgroup-per-transform sweep: 1 at N = 25 000, 2 at N = 50 000 (a radix-2 step in
+// front of two 25 000-point transforms, pcps_fused.h), 0 = the sweep does not serve this length
+inline int fused_terms(const sdr_engine* e, const FourStep& f) {
+    if (!e->pcps_fused || !f.ok || e->pcps_no_fast) return 0;
+    if (f.N1 == fast25k::N1 && f.N2 == fast25k::N2) return 1;
+    return f.N1 * f.N2 == 2 * fast25k::N ? 2 : 0;
+}
+// The fused sweep takes a map-free search whole when it fills at least one round of its 256 persistent workgroups (a
+// smaller search is quicker through the two-kernel path: ~8 us + 0.19 us per transform against ~35 us per round).
+inline bool fused_takes(const sdr_engine* e, const FourStep& f, int n_prn, int nbins) {
+    return fused_terms(e, f) * n_prn * nbins >= 256;
+}
+inline Xform plan_xform(const sdr_engine* e, int N) {
+    Xform t;
+    t.radices = factor_radices(N);
+    t.four = plan_four_step(N);
+    // (the register-resident kernels of either header serve this length: they split it as N1 x 200 themselves)
+    if (t.four.ok && !e->pcps_no_fast)
+        t.fast = t.four.N1 == fast25k::N1 && t.four.N2 == fast25k::N2 ? FAST_25K : fastn::handles(N) ? FAST_N : FAST_NONE;
+    return t;
+}
+
+// The request (samples per code N, Doppler grid, integration, PRNs, map wanted) and the engine's switches -> the plan.
+PcpsPlan plan_pcps(const sdr_engine* e, int N, double fs, int nbins, double bin_start, double bin_delta, int coh, int noncoh,
+                   int n_prn, bool want_map) {
+    PcpsPlan p;
+    p.N = N, p.fs = fs, p.nbins = nbins, p.bin_start = bin_start, p.bin_delta = bin_delta;
+    p.coh = coh, p.noncoh = noncoh, p.n_prn = n_prn;
+    // samplesPerCodeChip (channel_l1ca_kaplan.py:205-206), Python round = half-even
+    p.spc = (int)std::nearbyint(fs / 1.023e6);
+    p.xf = plan_xform(e, N);
+    const FourStep& four = p.xf.four;
+    // A code length the mixed-radix planner cannot factor (prime factor above 64) goes through the chirp-z
+    // transform with M = the next 2^a 3^b 5^c >= 2N-1.
+    if (p.xf.radices.empty()) {
+        for (int64_t m = 2 * (int64_t)N - 1;; ++m) {
+            int64_t q = m;
+            for (int f : {2, 3, 5})
+                while (q % f == 0) q /= f;
+            if (q == 1) {
+                p.M = (int)m;
+                break;
+            }
+        }
+        p.xm = plan_xform(e, p.M);
+    }
+
+    // Work-buffer sizing: transforms in flight per inverse sweep are capped at 8 GiB per buffer.
+    const size_t tbytes = (size_t)N * sizeof(double2);
+    const size_t mbytes = (size_t)p.M * sizeof(double2);  // (0 without the chirp-z path)
+    int prn_chunk = (int)std::min<int64_t>(n_prn, std::max<int64_t>(1, (int64_t)((8ull << 30) / (std::max(tbytes, mbytes) * nbins))));
+    if ((int64_t)prn_chunk * nbins > 65535) prn_chunk = std::max(1, 65535 / nbins);
+    // Indices and ratio only, one block, four-step transform available: the map is never materialised.
+    const bool map_free = !want_map && coh == 1 && noncoh == 1 && !p.M && four.ok && !e->pcps_force_map;
+    // The column kernel of an inverse sweep writes 16 N bytes per (PRN, bin) and the row kernel reads them back: as
+    // many PRNs per sweep as keep that intermediate inside the 256 MB Infinity Cache (a 200 MB budget), in sweeps of
+    // equal size -- 32 PRNs x 41 bins x 25 000: three sweeps of 11 / 11 / 10 PRNs instead of one of 525 MB, measured
+    // 0.40 -> 0.34 ms per acquisition (tools/pcps_breakdown.py <chunk>: 12: 0.341, 11: 0.339, 10: 0.348, 8: 0.357,
+    // 16: 0.379, 6: 0.392 -- the smaller the sweep, the larger the share of its partial last round of workgroups).
+    if (map_free && e->pcps_prn_chunk == 0) {
+        const int64_t per_prn = (int64_t)tbytes * nbins;
+        // (two sweeps alive at a time where they alternate between two streams: run_sweeps)
+        const bool two_alive = p.xf.fast && !e->prof && !e->pcps_no_overlap;
+        const int fit = (int)std::max<int64_t>(1, ((two_alive ? SDR_PCPS_OVERLAP_MB : 200ll) << 20) / per_prn);
+        if (fit < prn_chunk) {
+            const int sweeps = (n_prn + fit - 1) / fit;
+            prn_chunk = (n_prn + sweeps - 1) / sweeps;
+        }
+    }
+    if (e->pcps_prn_chunk > 0) prn_chunk = std::min(prn_chunk, e->pcps_prn_chunk);
+    p.prn_chunk = prn_chunk;
+    // (32 units and more: below that the two-kernel path's many small workgroups finish sooner than one unit per CU)
+    const bool fused10k = !want_map && coh == 1 && N == 10000 && !p.M && four.ok && !e->pcps_force_map && e->pcps_fused &&
+                          !e->pcps_no_fast && (int64_t)n_prn * nbins >= 32;
+    const bool fused = map_free && fused_takes(e, four, n_prn, nbins);
+    p.route = fused10k ? ROUTE_FUSED10K : fused ? ROUTE_FUSED : map_free ? ROUTE_SWEEPS : ROUTE_MAP;
+    p.terms = fused ? fused_terms(e, four) : 0;
+    p.overlap = p.route == ROUTE_SWEEPS && p.xf.fast && n_prn > prn_chunk && !e->prof && !e->pcps_no_overlap;
+    // (shared spectra: the shipped 300 Hz grid at 10 MHz has ten classes -- 10 transforms per block instead of 34)
+    if (fused10k || fused) p.sh = plan_shared_spectra(e, nbins, N, fs, bin_delta);
+    // the searches that end in the fused second sweep or the fused 10 MHz search raise a word per PRN behind its results:
+    // those are waited for instead of the stream's signal, which follows the last store by ~9 us (the receiver tick's finding)
+    p.done_words = fused10k || fused;
+    // (per-wave records a transform of the main sweep leaves: it may run the register-resident kernels)
+    p.records_sweep = p.xf.fast == FAST_25K ? fast25k::kRecordsPerTransform
+                      : p.xf.fast ? fastn::records(N) : records_per_transform(four);
+    p.records_per_prn = fused ? sdr_pcps_fused_records_per_prn(n_prn, nbins, p.terms) : nbins * p.records_sweep;
+    p.records_second = records_per_transform(four);
+
+    p.tbytes = tbytes;
+    p.work_bytes = tbytes * (size_t)std::max(fused10k ? nbins * noncoh : prn_chunk * nbins, std::max(n_prn, nbins));
+    p.fwd_bytes = tbytes * (size_t)std::max(fused10k ? nbins * noncoh : nbins, n_prn);
+    p.code_bytes = tbytes * n_prn;
+    p.code2_bytes = p.terms == 2 ? 2 * tbytes * n_prn : 0;
+    // (the fused sweep leaves at most 5 x SDR_PCPS_FUSED_RECORDS records per transform, twice that at N = 50 000)
+    const size_t n_records = map_free ? (size_t)n_prn * (nbins + 1) * std::max(std::max(p.records_second, p.records_sweep), 10 * SDR_PCPS_FUSED_RECORDS) + n_prn : 0;
+    p.map_bytes = (size_t)n_prn * ((map_free || fused10k) ? 1 : nbins) * N * sizeof(double);
+    p.csum_bytes = coh > 1 ? (size_t)n_prn * nbins * tbytes : 0;
+    p.part_bytes = std::max(std::max((size_t)n_prn * kPeakParts, n_records) * sizeof(Best),
+                            fused10k ? (size_t)n_prn * nbins * SDR_PCPS_FUSED10K_RECORD_BYTES : 0);
+    // [results: bin, code, ratio per PRN][slot numbers] on the device; page-locked: the same and the done words
+    p.res_bytes = (size_t)n_prn * 3 * sizeof(double) + n_prn * sizeof(int32_t);
+    p.pinned_bytes = (size_t)n_prn * 3 * sizeof(double) + 2 * (size_t)n_prn * sizeof(int32_t);
+    if (p.M) {
+        p.blu_bytes = tbytes + 3 * mbytes;
+        p.blu_work_bytes = mbytes * (size_t)std::max(2, std::max(prn_chunk * nbins, std::max(n_prn, nbins)));
+    }
+    return p;
+}
+
+// What one call brings along that the plan does not hold.
+struct PcpsCall {
+    int64_t start = 0;
+    double if_hz = 0.0;
+    // the caller's slot numbers (nullptr: it handed in the code spectra), their copy in the page-locked block, their place
+    // on the device (copied there only when the spectra have to be made)
+    const int32_t *slots = nullptr, *slots_pinned = nullptr;
+    int32_t* d_slots = nullptr;
+    // the page-locked results the peak kernels write (a few hundred bytes: one copy command and its stream latency less per
+    // acquisition), and the done words behind them, raised to done_seq
+    long long *res_bin = nullptr, *res_code = nullptr;
+    double* res_ratio = nullptr;
+    unsigned* done = nullptr;
+    unsigned done_seq = 0;
+    const BluPlan* blu = nullptr;
+    const long long* spec_off = nullptr;   // shared spectra: every bin's element offset inside its block of P class spectra
+};
+
+// The device table of shared-spectra offsets (kept while the shape stays).
+int upload_spec_offsets(sdr_engine* e, const PcpsPlan& p, const long long** off_out) {
+    const SharedSpectra& s = p.sh;
+    *off_out = nullptr;
+    if (!s.P) return SDR_OK;
+    std::vector<int64_t> key = {(int64_t)p.N, (int64_t)p.nbins, (int64_t)s.P, (int64_t)s.q};
     if (key != e->pcps_spec_off_key) {
-        std::vector<long long> off((size_t)nbins);
-        for (int b = 0; b < nbins; ++b)
-            off[(size_t)b] = (long long)(b % out->P) * (out->H + N) + out->H - (long long)(b / out->P) * out->q;
+        std::vector<long long> off((size_t)p.nbins);
+        for (int b = 0; b < p.nbins; ++b)
+            off[(size_t)b] = (long long)(b % s.P) * (s.H + p.N) + s.H - (long long)(b / s.P) * s.q;
         e->pcps_spec_off_key.clear();
         if (int rc = sdr_devbuf_reserve(e, &e->pcps_spec_off, off.size() * sizeof(long long))) return rc;
         SDR_HIP(hipMemcpyAsync(e->pcps_spec_off.ptr, off.data(), off.size() * sizeof(long long), hipMemcpyHostToDevice, e->stream));
         SDR_HIP(hipStreamSynchronize(e->stream));      // (pageable source: complete before `off` goes)
         e->pcps_spec_off_key = key;
     }
-    out->off = (const long long*)e->pcps_spec_off.ptr;
+    *off_out = (const long long*)e->pcps_spec_off.ptr;
+    return SDR_OK;
+}
+
+// K7/a3: upsample every code and take conj(fft(code)) (channel_l1ca_kaplan.py:184-185), unless the caller handed in its own
+// codeFFT arrays (function-level drop-in of PCPS()) -- or the spectra of exactly these staged codes at this rate are still in
+// the buffer from the previous search (the reference recomputes them on every acquisition, kaplan:184-185; they only change
+// when a slot is re-staged).
+template <int FMT>
+int code_spectra(sdr_engine* e, const PcpsPlan& p, const PcpsCall& c) {
+    const int N = p.N, n_prn = p.n_prn;
+    std::vector<int64_t> key;
+    if (c.slots) {
+        int64_t fs_bits;
+        memcpy(&fs_bits, &p.fs, sizeof(fs_bits));
+        key = {(int64_t)N, fs_bits, e->code_generation};
+        for (int i = 0; i < n_prn; ++i) {
+            key.push_back(c.slots[i]);
+            key.push_back(e->code_stamp[c.slots[i]]);
+        }
+    }
+    const bool spectra_cached = c.slots && key == e->pcps_spec_key && !e->pcps_no_spec_cache;
+    if (!spectra_cached) {
+        e->pcps_code2_ok = false;
+        e->pcps_spec_key.clear();   // (valid again only once the new spectra are queued without error, below)
+    }
+    if (!c.slots || spectra_cached) return SDR_OK;
+    int8_t* up = (int8_t*)e->pcps_b.ptr;  // scratch: n_prn*N bytes fits easily in a work buffer
+    // (the slot numbers reach the device only now: a search whose spectra are still there needs no copy command in
+    // front of its first kernel -- 2.7 us of copy and two boundaries on the stream)
+    SDR_HIP(hipMemcpyAsync(c.d_slots, c.slots_pinned, (size_t)n_prn * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    {
+        ProfScope ps(e, "pcps_upsample");
+        hipLaunchKernelGGL(upsample_batch_kernel, dim3((N + kThreads - 1) / kThreads, n_prn), dim3(kThreads), 0,
+                           e->stream, e->codes, e->code_len, e->code_stride, c.d_slots, 1.0 / p.fs, 1.0 / 1.023e6, N, up);
+    }
+    PassArgs a = {};
+    a.tw = (const double2*)e->pcps_tw.ptr;
+    a.N = N;
+    a.code_samples = up;
+    // ping-pong inside A (two halves are not needed: code batch is small) -> use A and F as scratch
+    run_fft<false, LOAD_CODE_REAL, STORE_CONJ, FMT>(e, p.xf, a, n_prn, (double2*)e->pcps_a.ptr, (double2*)e->pcps_fwd.ptr,
+                                                    (double2*)e->pcps_code.ptr, "pcps_code_fft", c.blu);
+    SDR_HIP(hipGetLastError());
+    e->pcps_spec_key = key;
+    return SDR_OK;
+}
+
+// Forward transforms of the Doppler-mixed millisecond number `block` (coherent index ic), `batch` bins (or classes of
+// shared spectra, written with their halos: F holds P rows of H + N) at once.
+template <int FMT>
+void forward(sdr_engine* e, const PcpsPlan& p, const PcpsCall& c, int batch, int64_t block, int ic, int iq_blocks) {
+    PassArgs f = {};
+    f.tw = (const double2*)e->pcps_tw.ptr;
+    f.N = p.N;
+    f.ring = e->iq;
+    f.capacity = e->iq_capacity;
+    f.first_sample = c.start + block * p.N;
+    f.carrier_offset = (int64_t)ic * p.N;
+    f.fs = p.fs;
+    f.if_hz = c.if_hz;
+    f.bin_start = p.bin_start;
+    f.bin_delta = p.bin_delta;
+    f.iq_blocks = iq_blocks;
+    f.halo = p.sh.H;
+    run_fft<false, LOAD_IQ_MIX, STORE_PLAIN, FMT>(e, p.xf, f, batch, (double2*)e->pcps_a.ptr, (double2*)e->pcps_b.ptr,
+                                                  (double2*)e->pcps_fwd.ptr, "pcps_fwd_fft", c.blu);
+}
+
+// The operands of an inverse sweep over the PRNs from p0 on, every bin.
+PassArgs sweep_args(const sdr_engine* e, const PcpsPlan& p, int p0) {
+    PassArgs g = {};
+    g.tw = (const double2*)e->pcps_tw.ptr;
+    g.N = p.N;
+    g.in = (const double2*)e->pcps_fwd.ptr;
+    g.code_spec = (const double2*)e->pcps_code.ptr + (size_t)p0 * p.N;
+    g.nbins = p.nbins;
+    g.scale = 1.0 / (double)p.N;
+    g.map = (double*)e->pcps_map.ptr + (size_t)p0 * p.nbins * p.N;
+    g.csum = e->pcps_csum.ptr ? (double2*)e->pcps_csum.ptr + (size_t)p0 * p.nbins * p.N : nullptr;
+    return g;
+}
+
+// N = 10 000, indices and ratio only, one coherent millisecond per block: the forward transforms of every block first, then
+// ONE launch that keeps each (PRN, bin)'s transform in LDS and its non-coherent sum in registers and finds both peaks
+// (pcps_fused10k.h) -- no map, no intermediate, no second sweep
+template <int FMT>
+int run_fused10k(sdr_engine* e, const PcpsPlan& p, const PcpsCall& c) {
+    // (the carrier restarts with every block; all blocks in one batch: [block][bin])
+    const int per_block = p.sh.P ? p.sh.P : p.nbins;
+    forward<FMT>(e, p, c, per_block * p.noncoh, 0, 0, per_block);
+    const long long blk_stride = p.sh.P ? (long long)p.sh.P * (p.sh.H + p.N) : (long long)p.nbins * p.N;
+    return sdr_pcps_fused10k_search(e, e->pcps_fwd.ptr, c.spec_off, blk_stride, e->pcps_code.ptr, e->pcps_tw.ptr, p.n_prn, p.nbins,
+                                    p.noncoh, p.N, p.spc, e->pcps_part.ptr, c.res_bin, c.res_code, c.res_ratio, c.done, c.done_seq);
+}
+
+// Every (PRN, bin) transform of the search in ONE launch of persistent workgroups (no intermediate, no sweeps), then the first
+// peaks, the second sweep and the ratio of the two in one more: the whole K6 (pcps_fused.h ifft_second_kernel).
+template <int FMT>
+int run_fused(sdr_engine* e, const PcpsPlan& p, const PcpsCall& c) {
+    const int N = p.N, n_prn = p.n_prn;
+    forward<FMT>(e, p, c, p.sh.P ? p.sh.P : p.nbins, 0, 0, 0);
+    const double2* C = (const double2*)e->pcps_code.ptr;
+    const double2* tw = (const double2*)e->pcps_tw.ptr;
+    if (p.terms == 2) {                    // N = 50 000: the spectra and their parity images
+        if (!e->pcps_code2_ok) {           // (made with the spectra, kept as long as they are)
+            ProfScope ps(e, "pcps_code_fft");
+            hipLaunchKernelGGL(code_parity_kernel, dim3((N + kThreads - 1) / kThreads, n_prn), dim3(kThreads), 0, e->stream, C,
+                               tw, N, (double2*)e->pcps_code2.ptr);
+            e->pcps_code2_ok = true;
+        }
+        C = (const double2*)e->pcps_code2.ptr;
+    }
+    Best* parts = (Best*)e->pcps_part.ptr;
+    if (int rc = sdr_pcps_fused_sweep(e, e->pcps_fwd.ptr, c.spec_off, C, tw, n_prn, p.nbins, N, parts)) return rc;
+    Best* tops = parts + (size_t)n_prn * p.records_per_prn;
+    long long* dev_bin = (long long*)e->pcps_res.ptr;      // device copies of the first peaks
+    return sdr_pcps_fused_second(e, e->pcps_fwd.ptr, c.spec_off, C, tw, n_prn, N, p.spc, parts, p.records_per_prn, tops,
+                                 dev_bin, dev_bin + n_prn, tops + n_prn, c.res_bin, c.res_code, c.res_ratio, c.done, c.done_seq);
+}
+
+// Map-free inverse sweeps that leave per-wave records; then the maximum from the records and the winning row of every PRN
+// alone (1/nbins of one inverse sweep) for the second peak.
+template <int FMT>
+int run_sweeps(sdr_engine* e, const PcpsPlan& p, const PcpsCall& c) {
+    const int n_prn = p.n_prn, nbins = p.nbins;
+    double2* A = (double2*)e->pcps_a.ptr;
+    double2* B = (double2*)e->pcps_b.ptr;
+    Best* parts = (Best*)e->pcps_part.ptr;
+    forward<FMT>(e, p, c, nbins, 0, 0, 0);
+    // Register-resident kernels, several sweeps, nobody timing the stages: the sweeps alternate between two
+    // streams and two intermediates, so that one sweep's partial last rounds of workgroups (and its launch
+    // ramps) are filled by the other's -- ordered behind the forward transforms and in front of the peak
+    // kernels by two events.
+    if (p.overlap) {
+        if (!e->pcps_aux) {
+            SDR_HIP(hipStreamCreateWithFlags(&e->pcps_aux, hipStreamNonBlocking));
+            SDR_HIP(hipEventCreateWithFlags(&e->pcps_ev[0], hipEventDisableTiming));
+            SDR_HIP(hipEventCreateWithFlags(&e->pcps_ev[1], hipEventDisableTiming));
+        }
+        SDR_HIP(hipEventRecord(e->pcps_ev[0], e->stream));
+        SDR_HIP(hipStreamWaitEvent(e->pcps_aux, e->pcps_ev[0], 0));
+    }
+    int sweep = 0;
+    for (int p0 = 0; p0 < n_prn; p0 += p.prn_chunk, ++sweep) {
+        const int pc = std::min(n_prn - p0, p.prn_chunk);
+        PassArgs g = sweep_args(e, p, p0);
+        g.partials = parts + (size_t)p0 * nbins * p.records_sweep;
+        if (p.overlap)
+            fast_run(e, p.xf, g, pc * nbins, (sweep & 1) ? B : A, (sweep & 1) ? e->pcps_aux : e->stream);
+        else
+            run_fft<true, LOAD_MUL_CODE, STORE_MAG_MAX, FMT>(e, p.xf, g, pc * nbins, A, B, nullptr, "pcps_inv_fft", c.blu);
+    }
+    if (p.overlap) {
+        SDR_HIP(hipEventRecord(e->pcps_ev[1], e->pcps_aux));
+        SDR_HIP(hipStreamWaitEvent(e->stream, e->pcps_ev[1], 0));
+    }
+    Best* tops = parts + (size_t)n_prn * p.records_per_prn;
+    Best* seconds = tops + n_prn;      // [n_prn][records of the second sweep]
+    long long* dev_bin = (long long*)e->pcps_res.ptr;      // device copies of the first peaks (read by the second sweep)
+    long long* dev_code = dev_bin + n_prn;
+    {
+        ProfScope ps(e, "pcps_peak");
+        hipLaunchKernelGGL(argmax_records_kernel, dim3(n_prn), dim3(kThreads), 0, e->stream, parts, p.records_per_prn, p.N, tops,
+                           dev_bin, dev_code);
+    }
+    PassArgs g = sweep_args(e, p, 0);
+    g.sel_bin = dev_bin;
+    g.tops = tops;
+    g.spc = p.spc;
+    g.partials = seconds;
+    run_fft<true, LOAD_MUL_CODE_SEL, STORE_MAG_MAX, FMT>(e, p.xf, g, n_prn, A, B, nullptr, "pcps_inv_fft", c.blu);
+    {
+        ProfScope ps(e, "pcps_peak");
+        hipLaunchKernelGGL(ratio_kernel, dim3(n_prn), dim3(64), 0, e->stream, seconds, p.records_second,
+                           tops, dev_bin, dev_code, c.res_bin, c.res_code, c.res_ratio);
+    }
+    SDR_HIP(hipGetLastError());
+    return SDR_OK;
+}
+
+// The map: |.| of every (PRN, bin) transform accumulated over the non-coherent blocks (the complex values over the coherent
+// ones first), then its peaks.
+template <int FMT>
+int run_map(sdr_engine* e, const PcpsPlan& p, const PcpsCall& c) {
+    const int n_prn = p.n_prn, nbins = p.nbins, N = p.N;
+    double2* A = (double2*)e->pcps_a.ptr;
+    double2* B = (double2*)e->pcps_b.ptr;
+    double* map = (double*)e->pcps_map.ptr;
+    for (int inc = 0; inc < p.noncoh; ++inc) {
+        for (int ic = 0; ic < p.coh; ++ic) {
+            forward<FMT>(e, p, c, nbins, (int64_t)inc * p.coh + ic, ic, 0);
+            for (int p0 = 0; p0 < n_prn; p0 += p.prn_chunk) {
+                const int pc = std::min(n_prn - p0, p.prn_chunk);
+                PassArgs g = sweep_args(e, p, p0);
+                if (p.coh == 1) {
+                    g.first_block = inc == 0;
+                    run_fft<true, LOAD_MUL_CODE, STORE_MAG_ACC, FMT>(e, p.xf, g, pc * nbins, A, B, nullptr, "pcps_inv_fft", c.blu);
+                } else {
+                    g.first_block = ic == 0;
+                    run_fft<true, LOAD_MUL_CODE, STORE_CPLX_ACC, FMT>(e, p.xf, g, pc * nbins, A, B, nullptr, "pcps_inv_fft", c.blu);
+                }
+            }
+        }
+        if (p.coh > 1) {
+            ProfScope ps(e, "pcps_mag_acc");
+            size_t count = (size_t)n_prn * nbins * N;
+            hipLaunchKernelGGL(mag_acc_kernel, dim3((unsigned)((count + kThreads - 1) / kThreads)), dim3(kThreads), 0,
+                               e->stream, (const double2*)e->pcps_csum.ptr, map, count, inc == 0 ? 1 : 0);
+        }
+    }
+    // K6
+    {
+        ProfScope ps(e, "pcps_peak");
+        Best* parts = (Best*)e->pcps_part.ptr;
+        hipLaunchKernelGGL(argmax_part_kernel, dim3(kPeakParts, n_prn), dim3(kThreads), 0, e->stream, map,
+                           (long long)nbins * N, parts);
+        hipLaunchKernelGGL(peak_finish_kernel, dim3(n_prn), dim3(kThreads), 0, e->stream, map, nbins, N, p.spc, parts,
+                           c.res_bin, c.res_code, c.res_ratio);
+    }
+    SDR_HIP(hipGetLastError());
     return SDR_OK;
 }
 
 template <int FMT>
-int pcps_run(sdr_engine* e, const int32_t* d_slots, const int32_t* h_slots, int n_prn, int64_t start, double fs, double if_hz,
-             double bin_start, double bin_delta, int nbins, int N, int spc, int coh, int noncoh,
-             const std::vector<int>& radices, int prn_chunk, bool have_spectra, const BluPlan* blu, bool map_free, bool fused10k) {
-    double2* F = (double2*)e->pcps_fwd.ptr;
-    double2* A = (double2*)e->pcps_a.ptr;
-    double2* B = (double2*)e->pcps_b.ptr;
-    double2* C = (double2*)e->pcps_code.ptr;
-    double* map = (double*)e->pcps_map.ptr;
-    double2* csum = (double2*)e->pcps_csum.ptr;
-    const double2* tw = (const double2*)e->pcps_tw.ptr;
-
-    // K7/a3: upsample every code and take conj(fft(code)) (channel_l1ca_kaplan.py:184-185), unless the caller
-    // handed in its own codeFFT arrays (function-level drop-in of PCPS()) -- or the spectra of exactly these
-    // staged codes at this rate are still in the buffer from the previous search (the reference recomputes them
-    // on every acquisition, kaplan:184-185; they only change when a slot is re-staged).
-    std::vector<int64_t> key;
-    if (!have_spectra) {
-        int64_t fs_bits;
-        memcpy(&fs_bits, &fs, sizeof(fs_bits));
-        key = {(int64_t)N, fs_bits, e->code_generation};
-        for (int i = 0; i < n_prn; ++i) {
-            key.push_back(h_slots[i]);
-            key.push_back(e->code_stamp[h_slots[i]]);
-        }
+int pcps_search(sdr_engine* e, const PcpsPlan& p, PcpsCall& c) {
+    if (int rc = code_spectra<FMT>(e, p, c)) return rc;
+    if (int rc = upload_spec_offsets(e, p, &c.spec_off)) return rc;
+    switch (p.route) {
+        case ROUTE_FUSED10K: return run_fused10k<FMT>(e, p, c);
+        case ROUTE_FUSED: return run_fused<FMT>(e, p, c);
+        case ROUTE_SWEEPS: return run_sweeps<FMT>(e, p, c);
+        default: return run_map<FMT>(e, p, c);
     }
-    const bool spectra_cached = !have_spectra && key == e->pcps_spec_key && !e->pcps_no_spec_cache;
-    if (have_spectra) e->pcps_spec_key.clear();
-    if (!spectra_cached) e->pcps_code2_ok = false;
-    if (!have_spectra && !spectra_cached) {
-        e->pcps_spec_key.clear();   // (valid again only once the new spectra are queued without error, below)
-        int8_t* up = (int8_t*)B;  // scratch: n_prn*N bytes fits easily in a work buffer
-        // (the slot numbers reach the device only now: a search whose spectra are still there needs no copy command in
-        // front of its first kernel -- 2.7 us of copy and two boundaries on the stream)
-        SDR_HIP(hipMemcpyAsync(const_cast<int32_t*>(d_slots), e->pcps_slots_pinned, (size_t)n_prn * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-        {
-            ProfScope ps(e, "pcps_upsample");
-            hipLaunchKernelGGL(upsample_batch_kernel, dim3((N + kThreads - 1) / kThreads, n_prn), dim3(kThreads), 0,
-                               e->stream, e->codes, e->code_len, e->code_stride, d_slots, 1.0 / fs, 1.0 / 1.023e6, N, up);
-        }
-        PassArgs a = {};
-        a.tw = tw;
-        a.N = N;
-        a.code_samples = up;
-        // ping-pong inside A (two halves are not needed: code batch is small) -> use A and F as scratch
-        run_fft<false, LOAD_CODE_REAL, STORE_CONJ, FMT>(e, radices, a, n_prn, A, F, C, "pcps_code_fft", blu);
-        SDR_HIP(hipGetLastError());
-        e->pcps_spec_key = key;
-    }
-
-    if (fused10k) {
-        // N = 10 000, indices and ratio only, one coherent millisecond per block: the forward transforms of every block
-        // first, then ONE launch that keeps each (PRN, bin)'s transform in LDS and its non-coherent sum in registers and
-        // finds both peaks (pcps_fused10k.h) -- no map, no intermediate, no second sweep
-        SharedSpectra sh10;
-        {
-            PassArgs f = {};
-            f.tw = tw;
-            f.N = N;
-            f.ring = e->iq;
-            f.capacity = e->iq_capacity;
-            f.first_sample = start;
-            f.carrier_offset = 0;            // (one coherent millisecond per block: the carrier restarts with every block)
-            f.fs = fs;
-            f.if_hz = if_hz;
-            f.bin_start = bin_start;
-            f.bin_delta = bin_delta;
-            // (shared spectra: the shipped 300 Hz grid has ten classes -- 10 transforms per block instead of 34)
-            if (int rcs = plan_shared_spectra(e, nbins, N, fs, bin_delta, &sh10)) return rcs;
-            const int per_block = sh10.P ? sh10.P : nbins;
-            f.iq_blocks = per_block;         // all blocks in one batch: [block][bin]
-            f.halo = sh10.H;
-            run_fft<false, LOAD_IQ_MIX, STORE_PLAIN, FMT>(e, radices, f, per_block * noncoh, A, B, F, "pcps_fwd_fft", blu);
-        }
-        long long* out_bin = e->pcps_res_direct ? (long long*)e->pcps_res_direct : (long long*)e->pcps_res.ptr;
-        return sdr_pcps_fused10k_search(e, F, sh10.off, sh10.P ? (long long)sh10.P * (sh10.H + N) : (long long)nbins * N, C, tw, n_prn, nbins,
-                                        noncoh, N, spc, e->pcps_part.ptr, out_bin, out_bin + n_prn, (double*)(out_bin + 2 * n_prn));
-    }
-    for (int inc = 0; inc < noncoh; ++inc) {
-        for (int ic = 0; ic < coh; ++ic) {
-            // Forward transforms of the Doppler-mixed millisecond, all bins at once.
-            PassArgs f = {};
-            f.tw = tw;
-            f.N = N;
-            f.ring = e->iq;
-            f.capacity = e->iq_capacity;
-            f.first_sample = start + ((int64_t)inc * coh + ic) * N;
-            f.carrier_offset = (int64_t)ic * N;
-            f.fs = fs;
-            f.if_hz = if_hz;
-            f.bin_start = bin_start;
-            f.bin_delta = bin_delta;
-            SharedSpectra sh;
-            if (map_free && fused_takes(e, plan_four_step(N), n_prn, nbins))
-                if (int rcs = plan_shared_spectra(e, nbins, N, fs, bin_delta, &sh)) return rcs;
-            const int share_P = sh.P;
-            const long long* spec_off = sh.off;
-            if (share_P) {
-                // (the class spectra with their halos, written so by the transform's last pass: F holds share_P rows of H + N)
-                f.halo = sh.H;
-                run_fft<false, LOAD_IQ_MIX, STORE_PLAIN, FMT>(e, radices, f, share_P, A, B, F, "pcps_fwd_fft", blu);
-            } else {
-                run_fft<false, LOAD_IQ_MIX, STORE_PLAIN, FMT>(e, radices, f, nbins, A, B, F, "pcps_fwd_fft", blu);
-            }
-            e->pcps_shared = share_P != 0;
-            e->pcps_shared_off = spec_off;
-
-            if (map_free && fused_takes(e, plan_four_step(N), n_prn, nbins)) {
-                // every (PRN, bin) transform of the search in ONE launch of persistent workgroups: no intermediate, no sweeps
-                if (fused_terms(e, plan_four_step(N)) == 2) {
-                    if (!e->pcps_code2_ok) {       // (made with the spectra, kept as long as they are)
-                        ProfScope ps(e, "pcps_code_fft");
-                        hipLaunchKernelGGL(code_parity_kernel, dim3((N + kThreads - 1) / kThreads, n_prn), dim3(kThreads), 0, e->stream, C,
-                                           tw, N, (double2*)e->pcps_code2.ptr);
-                        e->pcps_code2_ok = true;
-                    }
-                    C = (double2*)e->pcps_code2.ptr;
-                }
-                if (int rcf = sdr_pcps_fused_sweep(e, F, spec_off, C, tw, n_prn, nbins, N, e->pcps_part.ptr)) return rcf;
-                continue;
-            }
-            // Register-resident kernels, several sweeps, nobody timing the stages: the sweeps alternate between two
-            // streams and two intermediates, so that one sweep's partial last rounds of workgroups (and its launch
-            // ramps) are filled by the other's -- ordered behind the forward transforms and in front of the peak
-            // kernels by two events.
-            const bool overlap = map_free && fast_applies(e, plan_four_step(N)) && n_prn > prn_chunk && !e->prof &&
-                                 !e->pcps_no_overlap;
-            if (overlap) {
-                if (!e->pcps_aux) {
-                    SDR_HIP(hipStreamCreateWithFlags(&e->pcps_aux, hipStreamNonBlocking));
-                    SDR_HIP(hipEventCreateWithFlags(&e->pcps_ev[0], hipEventDisableTiming));
-                    SDR_HIP(hipEventCreateWithFlags(&e->pcps_ev[1], hipEventDisableTiming));
-                }
-                SDR_HIP(hipEventRecord(e->pcps_ev[0], e->stream));
-                SDR_HIP(hipStreamWaitEvent(e->pcps_aux, e->pcps_ev[0], 0));
-            }
-            int sweep = 0;
-            for (int p0 = 0; p0 < n_prn; p0 += prn_chunk, ++sweep) {
-                const int pc = n_prn - p0 < prn_chunk ? n_prn - p0 : prn_chunk;
-                if (overlap) {
-                    PassArgs g = {};
-                    g.tw = tw;
-                    g.N = N;
-                    g.in = F;
-                    g.code_spec = C + (size_t)p0 * N;
-                    g.nbins = nbins;
-                    g.scale = 1.0 / (double)N;
-                    g.partials = (Best*)e->pcps_part.ptr + (size_t)p0 * nbins * records_main_sweep(e, plan_four_step(N));
-                    fast_run(e, plan_four_step(N), g, pc * nbins, (sweep & 1) ? B : A, (sweep & 1) ? e->pcps_aux : e->stream);
-                    continue;
-                }
-                PassArgs g = {};
-                g.tw = tw;
-                g.N = N;
-                g.in = F;
-                g.code_spec = C + (size_t)p0 * N;
-                g.nbins = nbins;
-                g.scale = 1.0 / (double)N;
-                g.map = map + (size_t)p0 * nbins * N;
-                g.csum = csum ? csum + (size_t)p0 * nbins * N : nullptr;
-                if (map_free) {
-                    g.partials = (Best*)e->pcps_part.ptr + (size_t)p0 * nbins * records_main_sweep(e, plan_four_step(N));
-                    run_fft<true, LOAD_MUL_CODE, STORE_MAG_MAX, FMT>(e, radices, g, pc * nbins, A, B, nullptr, "pcps_inv_fft", blu);
-                } else if (coh == 1) {
-                    g.first_block = inc == 0;
-                    run_fft<true, LOAD_MUL_CODE, STORE_MAG_ACC, FMT>(e, radices, g, pc * nbins, A, B, nullptr, "pcps_inv_fft", blu);
-                } else {
-                    g.first_block = ic == 0;
-                    run_fft<true, LOAD_MUL_CODE, STORE_CPLX_ACC, FMT>(e, radices, g, pc * nbins, A, B, nullptr, "pcps_inv_fft", blu);
-                }
-            }
-            if (overlap) {
-                SDR_HIP(hipEventRecord(e->pcps_ev[1], e->pcps_aux));
-                SDR_HIP(hipStreamWaitEvent(e->stream, e->pcps_ev[1], 0));
-            }
-        }
-        if (coh > 1) {
-            ProfScope ps(e, "pcps_mag_acc");
-            size_t count = (size_t)n_prn * nbins * N;
-            hipLaunchKernelGGL(mag_acc_kernel, dim3((unsigned)((count + kThreads - 1) / kThreads)), dim3(kThreads), 0,
-                               e->stream, csum, map, count, inc == 0 ? 1 : 0);
-        }
-    }
-
-    // K6
-    Best* parts = (Best*)e->pcps_part.ptr;
-    // (the three result arrays are a few hundred bytes: the peak kernels write them straight into page-locked host
-    // memory when the caller set it up -- one copy command and its stream latency less per acquisition)
-    long long* res_bin = e->pcps_res_direct ? (long long*)e->pcps_res_direct : (long long*)e->pcps_res.ptr;
-    long long* res_code = res_bin + n_prn;
-    double* res_ratio = (double*)(res_code + n_prn);
-    long long* dev_bin = (long long*)e->pcps_res.ptr;      // device copies of the first peaks (read by the second sweep)
-    long long* dev_code = dev_bin + n_prn;
-    if (map_free) {
-        // the map was never written: maximum from the per-wave records, then the winning row of every PRN alone
-        // (1/nbins of one inverse sweep) for the second peak
-        const FourStep four = plan_four_step(N);
-        const int per_prn = fused_takes(e, four, n_prn, nbins) ? sdr_pcps_fused_records_per_prn(n_prn, nbins, fused_terms(e, four))
-                                                               : nbins * records_main_sweep(e, four);
-        Best* tops = parts + (size_t)n_prn * per_prn;
-        Best* seconds = tops + n_prn;      // [n_prn][records of the second sweep]
-        int per_second = records_per_transform(four);
-        if (fused_takes(e, four, n_prn, nbins) && !e->pcps_slow_second) {
-            // first peaks + second sweep in one launch of n_prn x 5 workgroups (pcps_fused.h ifft_second_kernel)
-            // ... which also divides the two peaks (its last workgroup per PRN): the whole K6 in one launch
-            // (C: at N = 50 000 the parity images the first sweep used; the spectra: shared ones when that sweep read them so)
-            const bool two = fused_terms(e, four) == 2;
-            return sdr_pcps_fused_second(e, F, e->pcps_shared_off, two ? (double2*)e->pcps_code2.ptr : C, tw, n_prn, N, spc,
-                                         parts, per_prn, tops, dev_bin, dev_code, seconds, res_bin, res_code, res_ratio);
-        } else {
-            {
-                ProfScope ps(e, "pcps_peak");
-                hipLaunchKernelGGL(argmax_records_kernel, dim3(n_prn), dim3(kThreads), 0, e->stream, parts, per_prn, N, tops,
-                                   dev_bin, dev_code);
-            }
-            PassArgs g = {};
-            g.tw = tw;
-            g.N = N;
-            g.in = F;
-            g.code_spec = C;
-            g.nbins = nbins;
-            g.scale = 1.0 / (double)N;
-            g.sel_bin = dev_bin;
-            g.tops = tops;
-            g.spc = spc;
-            g.partials = seconds;
-            run_fft<true, LOAD_MUL_CODE_SEL, STORE_MAG_MAX, FMT>(e, radices, g, n_prn, A, B, nullptr, "pcps_inv_fft", blu);
-        }
-        {
-            ProfScope ps(e, "pcps_peak");
-            hipLaunchKernelGGL(ratio_kernel, dim3(n_prn), dim3(64), 0, e->stream, seconds, per_second,
-                               tops, dev_bin, dev_code, res_bin, res_code, res_ratio);
-        }
-        SDR_HIP(hipGetLastError());
-        return SDR_OK;
-    }
-    {
-        ProfScope ps(e, "pcps_peak");
-        hipLaunchKernelGGL(argmax_part_kernel, dim3(kPeakParts, n_prn), dim3(kThreads), 0, e->stream, map,
-                           (long long)nbins * N, parts);
-        hipLaunchKernelGGL(peak_finish_kernel, dim3(n_prn), dim3(kThreads), 0, e->stream, map, nbins, N, spc, parts,
-                           res_bin, res_code, res_ratio);
-    }
-    SDR_HIP(hipGetLastError());
-    return SDR_OK;
 }
 
 }  // namespace
@@ -1466,27 +1596,10 @@ static int pcps_impl(sdr_engine* e, const int32_t* code_slots, const double* cod
     const int nbins = sdr_pcps_bins(doppler_range, doppler_step);
     if (nbins <= 0) return sdr_fail(SDR_ERR_INVALID, "empty Doppler grid");
     if (n_bins_out) *n_bins_out = nbins;
-    // samplesPerCode / samplesPerCodeChip (channel_l1ca_kaplan.py:186,205-206), Python round = half-even
+    // samplesPerCode (channel_l1ca_kaplan.py:186), Python round = half-even
     const int64_t N64 = code_spectra ? (int64_t)n_code_in : (int64_t)std::nearbyint(fs * 1023.0 / 1.023e6);
-    const int spc = (int)std::nearbyint(fs / 1.023e6);
     if (N64 < 2 || N64 > (1 << 24)) return sdr_fail(SDR_ERR_UNSUPPORTED, "samples per code %lld unsupported", (long long)N64);
     const int N = (int)N64;
-    const std::vector<int> radices = factor_radices(N);
-    // A code length the mixed-radix planner cannot factor (prime factor above 64) goes through the chirp-z
-    // transform with M = the next 2^a 3^b 5^c >= 2N-1.
-    const bool use_blu = radices.empty();
-    int M = 0;
-    if (use_blu) {
-        for (int64_t m = 2 * (int64_t)N - 1;; ++m) {
-            int64_t q = m;
-            for (int f : {2, 3, 5})
-                while (q % f == 0) q /= f;
-            if (q == 1) {
-                M = (int)m;
-                break;
-            }
-        }
-    }
     const int64_t need = (int64_t)N * coh * noncoh;
     if (start_sample < 0 || need > e->iq_capacity)
         return sdr_fail(SDR_ERR_RANGE, "acquisition needs %lld samples, ring holds %lld", (long long)need,
@@ -1494,134 +1607,85 @@ static int pcps_impl(sdr_engine* e, const int32_t* code_slots, const double* cod
     for (int i = 0; i < n_prn && !code_spectra; ++i)
         if (code_slots[i] < 0 || code_slots[i] >= e->n_slots || e->code_len_host[code_slots[i]] <= 0)
             return sdr_fail(SDR_ERR_INVALID, "PRN entry %d: code slot %d is not staged", i, code_slots[i]);
-
-    // Work-buffer sizing: transforms in flight per inverse sweep are capped at 8 GiB per buffer.
-    const size_t tbytes = (size_t)N * sizeof(double2);
-    const size_t mbytes = (size_t)M * sizeof(double2);  // (0 without the chirp-z path)
-    int prn_chunk = (int)std::min<int64_t>(n_prn, std::max<int64_t>(1, (int64_t)((8ull << 30) / (std::max(tbytes, mbytes) * nbins))));
-    if ((int64_t)prn_chunk * nbins > 65535) prn_chunk = std::max(1, 65535 / nbins);
-    // Indices and ratio only, one block, four-step transform available: the map is never materialised.
-    const FourStep four = plan_four_step(N);
-    const bool map_free = !corr_map && coh == 1 && noncoh == 1 && !use_blu && four.ok && !e->pcps_force_passes &&
-                          !e->pcps_force_map;
-    // The column kernel of an inverse sweep writes 16 N bytes per (PRN, bin) and the row kernel reads them back: as
-    // many PRNs per sweep as keep that intermediate inside the 256 MB Infinity Cache (a 200 MB budget), in sweeps of
-    // equal size -- 32 PRNs x 41 bins x 25 000: three sweeps of 11 / 11 / 10 PRNs instead of one of 525 MB, measured
-    // 0.40 -> 0.34 ms per acquisition (tools/pcps_breakdown.py <chunk>: 12: 0.341, 11: 0.339, 10: 0.348, 8: 0.357,
-    // 16: 0.379, 6: 0.392 -- the smaller the sweep, the larger the share of its partial last round of workgroups).
-    if (map_free && e->pcps_prn_chunk == 0) {
-        const int64_t per_prn = (int64_t)tbytes * nbins;
-        // (two sweeps alive at a time where they alternate between two streams: pcps_run)
-        const bool two_alive = fast_applies(e, four) && !e->prof && !e->pcps_no_overlap;
-        const int fit = (int)std::max<int64_t>(1, ((two_alive ? SDR_PCPS_OVERLAP_MB : 200ll) << 20) / per_prn);
-        if (fit < prn_chunk) {
-            const int sweeps = (n_prn + fit - 1) / fit;
-            prn_chunk = (n_prn + sweeps - 1) / sweeps;
-        }
-    }
-    if (e->pcps_prn_chunk > 0) prn_chunk = std::min(prn_chunk, e->pcps_prn_chunk);
-    // (32 units and more: below that the two-kernel path's many small workgroups finish sooner than one unit per CU)
-    const bool fused10k = !corr_map && coh == 1 && N == 10000 && !use_blu && four.ok && !e->pcps_force_passes && !e->pcps_force_map &&
-                          e->pcps_fused && !e->pcps_no_fast && (int64_t)n_prn * nbins >= 32;
     if (nbins > 65535 || n_prn > 65535) return sdr_fail(SDR_ERR_UNSUPPORTED, "grid too large");
-    const size_t work = tbytes * (size_t)std::max(fused10k ? nbins * noncoh : prn_chunk * nbins, std::max(n_prn, nbins));
-    int rc = sdr_devbuf_reserve(e, &e->pcps_fwd, tbytes * (size_t)std::max(fused10k ? nbins * noncoh : nbins, n_prn));
-    if (!rc) rc = sdr_devbuf_reserve(e, &e->pcps_a, work);
-    if (!rc) rc = sdr_devbuf_reserve(e, &e->pcps_b, work);
-    if (!rc) rc = sdr_devbuf_reserve(e, &e->pcps_code, tbytes * n_prn);
-    if (!rc && map_free && fused_terms(e, four) == 2 && fused_takes(e, four, n_prn, nbins)) {
-        void* before = e->pcps_code2.ptr;
-        rc = sdr_devbuf_reserve(e, &e->pcps_code2, 2 * tbytes * n_prn);
-        if (e->pcps_code2.ptr != before) e->pcps_code2_ok = false;
-    }
-    // (the fused sweep leaves at most 5 x SDR_PCPS_FUSED_RECORDS records per transform, twice that at N = 50 000)
-    const size_t n_records = map_free ? (size_t)n_prn * (nbins + 1) * std::max(std::max(records_per_transform(four), records_main_sweep(e, four)), 10 * SDR_PCPS_FUSED_RECORDS) + n_prn : 0;
-    if (!rc) rc = sdr_devbuf_reserve(e, &e->pcps_map, (size_t)n_prn * ((map_free || fused10k) ? 1 : nbins) * N * sizeof(double));
-    if (!rc && coh > 1) rc = sdr_devbuf_reserve(e, &e->pcps_csum, (size_t)n_prn * nbins * tbytes);
-    if (!rc) rc = sdr_devbuf_reserve(e, &e->pcps_part, std::max(std::max((size_t)n_prn * kPeakParts, n_records) * sizeof(Best),
-                                                                 fused10k ? (size_t)n_prn * nbins * SDR_PCPS_FUSED10K_RECORD_BYTES : 0));
-    if (!rc) rc = sdr_devbuf_reserve(e, &e->pcps_res, (size_t)n_prn * 3 * sizeof(double) + n_prn * sizeof(int32_t));
-    if (rc) return rc;
+    // np.arange(-R, R+1, S): element k = start + k*delta with delta = (start+step) - start
+    const double bin_start = -doppler_range;
+    const double bin_delta = (bin_start + doppler_step) - bin_start;
+    const PcpsPlan p = plan_pcps(e, N, fs, nbins, bin_start, bin_delta, coh, noncoh, n_prn, corr_map != nullptr);
+
+    int rc;
+    const void* code2_before = e->pcps_code2.ptr;
+    const std::pair<DevBuf*, size_t> bufs[] = {{&e->pcps_fwd, p.fwd_bytes}, {&e->pcps_a, p.work_bytes}, {&e->pcps_b, p.work_bytes},
+                                               {&e->pcps_code, p.code_bytes}, {&e->pcps_code2, p.code2_bytes}, {&e->pcps_map, p.map_bytes},
+                                               {&e->pcps_csum, p.csum_bytes}, {&e->pcps_part, p.part_bytes}, {&e->pcps_res, p.res_bytes}};
+    for (const auto& b : bufs)       // (0 bytes: a buffer this search does not use)
+        if (b.second && (rc = sdr_devbuf_reserve(e, b.first, b.second))) return rc;
+    if (e->pcps_code2.ptr != code2_before) e->pcps_code2_ok = false;
     if (e->pcps_tw_n != N) {
-        if ((rc = sdr_devbuf_reserve(e, &e->pcps_tw, tbytes))) return rc;
+        if ((rc = sdr_devbuf_reserve(e, &e->pcps_tw, p.tbytes))) return rc;
         hipLaunchKernelGGL(twiddle_kernel, dim3((N + kThreads - 1) / kThreads), dim3(kThreads), 0, e->stream,
                            (double2*)e->pcps_tw.ptr, N);
         SDR_HIP(hipGetLastError());
         e->pcps_tw_n = N;
     }
     BluPlan blu;
-    if (use_blu) {
-        const size_t max_batch = (size_t)std::max(2, std::max(prn_chunk * nbins, std::max(n_prn, nbins)));
-        if ((rc = sdr_devbuf_reserve(e, &e->pcps_blu, tbytes + 3 * mbytes))) return rc;
-        if (!rc) rc = sdr_devbuf_reserve(e, &e->pcps_blu_x, mbytes * max_batch);
-        if (!rc) rc = sdr_devbuf_reserve(e, &e->pcps_blu_a, mbytes * max_batch);
-        if (!rc) rc = sdr_devbuf_reserve(e, &e->pcps_blu_b, mbytes * max_batch);
-        if (rc) return rc;
+    if (p.M) {
+        const int M = p.M;
+        for (DevBuf* b : {&e->pcps_blu, &e->pcps_blu_x, &e->pcps_blu_a, &e->pcps_blu_b})
+            if ((rc = sdr_devbuf_reserve(e, b, b == &e->pcps_blu ? p.blu_bytes : p.blu_work_bytes))) return rc;
         double2* chirp = (double2*)e->pcps_blu.ptr;
         double2* spec_fwd = chirp + N;
-        double2* spec_inv = spec_fwd + M;
-        double2* twM = spec_inv + M;
-        blu.N = N;
-        blu.M = M;
-        blu.chirp = chirp;
-        blu.spec_fwd = spec_fwd;
-        blu.spec_inv = spec_inv;
-        blu.twM = twM;
-        blu.x = (double2*)e->pcps_blu_x.ptr;
-        blu.a = (double2*)e->pcps_blu_a.ptr;
-        blu.b = (double2*)e->pcps_blu_b.ptr;
-        blu.radM = factor_radices(M);
+        double2* twM = spec_fwd + 2 * M;
+        blu = {N, M, chirp, spec_fwd, spec_fwd + M, twM, (double2*)e->pcps_blu_x.ptr, (double2*)e->pcps_blu_a.ptr,
+               (double2*)e->pcps_blu_b.ptr, &p.xm};
         if (e->pcps_blu_n != N) {  // plan cached per code length: chirp, length-M twiddles, spectra of both kernels
             hipLaunchKernelGGL(twiddle_kernel, dim3((M + kThreads - 1) / kThreads), dim3(kThreads), 0, e->stream, twM, M);
             hipLaunchKernelGGL(blu_chirp_kernel, dim3((M + kThreads - 1) / kThreads), dim3(kThreads), 0, e->stream, chirp,
                                blu.x, blu.x + M, N, M);
-            PassArgs p = {};
-            p.N = M;
-            p.tw = twM;
-            p.in = blu.x;  // two transforms at once: [kernel_fwd, kernel_inv] -> [spec_fwd, spec_inv] (adjacent)
-            run_fft<false, LOAD_PLAIN, STORE_PLAIN, SDR_FMT_CF64>(e, blu.radM, p, 2, blu.a, blu.b, spec_fwd, "pcps_bluestein_plan");
+            PassArgs a = {};
+            a.N = M;
+            a.tw = twM;
+            a.in = blu.x;  // two transforms at once: [kernel_fwd, kernel_inv] -> [spec_fwd, spec_inv] (adjacent)
+            run_fft<false, LOAD_PLAIN, STORE_PLAIN, SDR_FMT_CF64>(e, p.xm, a, 2, blu.a, blu.b, spec_fwd, "pcps_bluestein_plan");
             SDR_HIP(hipGetLastError());
             e->pcps_blu_n = N;
         }
     }
-    int32_t* d_slots = (int32_t*)((char*)e->pcps_res.ptr + (size_t)n_prn * 3 * sizeof(double));
     // small transfers go through page-locked staging: one copy each way, no hidden synchronisation
-    const size_t res_bytes = (size_t)n_prn * 3 * sizeof(double);
     // page-locked: [results: bin, code, ratio per PRN][slot numbers][done words]
-    if ((rc = sdr_pinned_reserve(e, &e->ctx0, res_bytes + 2 * (size_t)n_prn * sizeof(int32_t)))) return rc;
+    if ((rc = sdr_pinned_reserve(e, &e->ctx0, p.pinned_bytes))) return rc;
     char* pin = (char*)e->ctx0.pinned;
+    const size_t res_bytes = (size_t)n_prn * 3 * sizeof(double);
+    PcpsCall c;
+    c.start = start_sample;
+    c.if_hz = if_hz;
+    c.slots = code_slots;
+    c.d_slots = (int32_t*)((char*)e->pcps_res.ptr + res_bytes);
+    c.res_bin = (long long*)pin;
+    c.res_code = c.res_bin + n_prn;
+    c.res_ratio = (double*)(c.res_code + n_prn);
+    c.blu = p.M ? &blu : nullptr;
     if (code_spectra) {
-        SDR_HIP(hipMemcpyAsync(e->pcps_code.ptr, code_spectra, tbytes * n_prn, hipMemcpyHostToDevice, e->stream));
+        SDR_HIP(hipMemcpyAsync(e->pcps_code.ptr, code_spectra, p.code_bytes, hipMemcpyHostToDevice, e->stream));
     } else {
         memcpy(pin + res_bytes, code_slots, (size_t)n_prn * sizeof(int32_t));
-        e->pcps_slots_pinned = pin + res_bytes;      // (copied to the device by pcps_run when it has to make spectra)
+        c.slots_pinned = (const int32_t*)(pin + res_bytes);      // (copied to the device when spectra have to be made)
     }
-    e->pcps_res_direct = pin;
-    // the searches that end in the fused second sweep raise a word per PRN behind its results (sdr_pcps_fused_second): those
-    // are waited for instead of the stream's signal, which follows the last store by ~9 us (the receiver tick's finding)
-    e->pcps_done = (unsigned*)(pin + res_bytes + (size_t)n_prn * sizeof(int32_t));
-    memset(e->pcps_done, 0, (size_t)n_prn * sizeof(unsigned));
-    e->pcps_done_seq = ++e->pcps_done_counter ? e->pcps_done_counter : ++e->pcps_done_counter;
-    e->pcps_done_used = false;
-    const bool hs = code_spectra != nullptr;
-
-    // np.arange(-R, R+1, S): element k = start + k*delta with delta = (start+step) - start
-    const double bin_start = -doppler_range;
-    const double bin_delta = (bin_start + doppler_step) - bin_start;
+    c.done = (unsigned*)(pin + res_bytes + (size_t)n_prn * sizeof(int32_t));
+    memset(c.done, 0, (size_t)n_prn * sizeof(unsigned));
+    c.done_seq = ++e->pcps_done_counter ? e->pcps_done_counter : ++e->pcps_done_counter;
 
     {
-    // (one event pair around every kernel of the search: its in-stream time; while it records, the search stays on one stream)
-    ProfScope whole(e, "call_pcps");
-    switch (e->iq_fmt) {
-        case SDR_FMT_CI8: rc = pcps_run<SDR_FMT_CI8>(e, d_slots, code_slots, n_prn, start_sample, fs, if_hz, bin_start, bin_delta, nbins, N, spc, coh, noncoh, radices, prn_chunk, hs, use_blu ? &blu : nullptr, map_free, fused10k); break;
-        case SDR_FMT_CI16: rc = pcps_run<SDR_FMT_CI16>(e, d_slots, code_slots, n_prn, start_sample, fs, if_hz, bin_start, bin_delta, nbins, N, spc, coh, noncoh, radices, prn_chunk, hs, use_blu ? &blu : nullptr, map_free, fused10k); break;
-        case SDR_FMT_CF32: rc = pcps_run<SDR_FMT_CF32>(e, d_slots, code_slots, n_prn, start_sample, fs, if_hz, bin_start, bin_delta, nbins, N, spc, coh, noncoh, radices, prn_chunk, hs, use_blu ? &blu : nullptr, map_free, fused10k); break;
-        default: rc = pcps_run<SDR_FMT_CF64>(e, d_slots, code_slots, n_prn, start_sample, fs, if_hz, bin_start, bin_delta, nbins, N, spc, coh, noncoh, radices, prn_chunk, hs, use_blu ? &blu : nullptr, map_free, fused10k); break;
+        // (one event pair around every kernel of the search: its in-stream time; while it records, the search stays on one stream)
+        ProfScope whole(e, "call_pcps");
+        auto search = [&](auto fmt) { return pcps_search<decltype(fmt)::value>(e, p, c); };
+        switch (e->iq_fmt) {
+            case SDR_FMT_CI8: rc = search(std::integral_constant<int, SDR_FMT_CI8>{}); break;
+            case SDR_FMT_CI16: rc = search(std::integral_constant<int, SDR_FMT_CI16>{}); break;
+            case SDR_FMT_CF32: rc = search(std::integral_constant<int, SDR_FMT_CF32>{}); break;
+            default: rc = search(std::integral_constant<int, SDR_FMT_CF64>{}); break;
+        }
     }
-    }
-    e->pcps_res_direct = nullptr;
-    unsigned* const done_words = e->pcps_done_used ? e->pcps_done : nullptr;
-    e->pcps_done = nullptr;
     if (rc) {
         // a search that stopped half way: what the code-spectra buffer holds is unknown, and a sweep may still be
         // running on the second stream -- join it before anybody re-uses the work buffers
@@ -1634,12 +1698,12 @@ static int pcps_impl(sdr_engine* e, const int32_t* code_slots, const double* cod
         SDR_HIP(hipMemcpyAsync(corr_map, e->pcps_map.ptr, (size_t)n_prn * nbins * N * sizeof(double),
                                hipMemcpyDeviceToHost, e->stream));
     bool seen = false;
-    if (done_words && !corr_map) {       // (bounded: a launch that died never raises the words -- the stream is asked then)
+    if (p.done_words) {       // (bounded: a launch that died never raises the words -- the stream is asked then)
         const auto t0 = std::chrono::steady_clock::now();
-        int c = 0;
+        int k = 0;
         for (long spins = 0;; ++spins) {
-            while (c < n_prn && __atomic_load_n(&done_words[c], __ATOMIC_ACQUIRE) == e->pcps_done_seq) ++c;
-            if (c == n_prn) {
+            while (k < n_prn && __atomic_load_n(&c.done[k], __ATOMIC_ACQUIRE) == c.done_seq) ++k;
+            if (k == n_prn) {
                 seen = true;
                 break;
             }
@@ -1647,12 +1711,11 @@ static int pcps_impl(sdr_engine* e, const int32_t* code_slots, const double* cod
         }
     }
     if (!seen) SDR_HIP(hipStreamSynchronize(e->stream));
-    const long long* hb = (const long long*)pin;
     for (int i = 0; i < n_prn; ++i) {
-        peak_bin[i] = hb[i];
-        peak_code[i] = hb[n_prn + i];
+        peak_bin[i] = c.res_bin[i];
+        peak_code[i] = c.res_code[i];
     }
-    memcpy(peak_ratio, pin + 2 * (size_t)n_prn * sizeof(long long), (size_t)n_prn * sizeof(double));
+    memcpy(peak_ratio, c.res_ratio, (size_t)n_prn * sizeof(double));
     return SDR_OK;
 }
 

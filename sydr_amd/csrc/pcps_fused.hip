@@ -89,7 +89,7 @@ int sdr_pcps_fused_sweep(sdr_engine* e, const void* F, const void* spec_off, con
 
 int sdr_pcps_fused_second(sdr_engine* e, const void* F, const void* spec_off, const void* C, const void* tw, int n_prn, int N, int spc, const void* recs,
                           int per_prn, void* tops, void* dev_bin, void* dev_code, void* seconds, void* res_bin, void* res_code,
-                          void* res_ratio) {
+                          void* res_ratio, unsigned* done, unsigned done_seq) {
     if (N != fused25k::N && N != 2 * fused25k::N) return sdr_fail(SDR_ERR_UNSUPPORTED, "fused PCPS sweep: N = %d", N);
     const int terms = N / fused25k::N;
     fused25k::SecondArgs s = {};
@@ -116,11 +116,8 @@ int sdr_pcps_fused_second(sdr_engine* e, const void* F, const void* spec_off, co
     s.res_bin = (long long*)res_bin;
     s.res_code = (long long*)res_code;
     s.res_ratio = (double*)res_ratio;
-    if (e->pcps_done && res_bin == e->pcps_res_direct) {      // (the results go straight to the caller's page-locked block)
-        s.done = e->pcps_done;
-        s.done_seq = e->pcps_done_seq;
-        e->pcps_done_used = true;
-    }
+    s.done = done;
+    s.done_seq = done_seq;
     auto* kernel = terms == 2 ? fused25k::ifft_second_kernel<2> : fused25k::ifft_second_kernel<1>;
     (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused25k::kLdsBytes);
     ProfScope ps(e, "pcps_inv_fft");
@@ -131,7 +128,8 @@ int sdr_pcps_fused_second(sdr_engine* e, const void* F, const void* spec_off, co
 }
 
 int sdr_pcps_fused10k_search(sdr_engine* e, const void* F_all, const void* spec_off, long long blk_stride, const void* C, const void* tw, int n_prn,
-                             int nbins, int noncoh, int N, int spc, void* records, void* out_bin, void* out_code, void* out_ratio) {
+                             int nbins, int noncoh, int N, int spc, void* records, void* out_bin, void* out_code, void* out_ratio,
+                             unsigned* done, unsigned done_seq) {
     if (N != fused10k::N) return sdr_fail(SDR_ERR_UNSUPPORTED, "fused 10 MHz PCPS search: N = %d", N);
     fused10k::Args a = {};
     a.spec = (const double2*)F_all;
@@ -149,13 +147,8 @@ int sdr_pcps_fused10k_search(sdr_engine* e, const void* F_all, const void* spec_
     }
     {
         ProfScope ps(e, "pcps_peak");
-        unsigned* done = nullptr;
-        if (e->pcps_done && out_bin == e->pcps_res_direct) {     // (the results go straight to the caller's page-locked block)
-            done = e->pcps_done;
-            e->pcps_done_used = true;
-        }
         hipLaunchKernelGGL(fused10k::peaks_kernel, dim3(n_prn), dim3(64), 0, e->stream, a.records, nbins, (long long*)out_bin,
-                           (long long*)out_code, (double*)out_ratio, done, e->pcps_done_seq);
+                           (long long*)out_code, (double*)out_ratio, done, done_seq);
     }
     SDR_HIP(hipGetLastError());
     return SDR_OK;
