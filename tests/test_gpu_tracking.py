@@ -122,13 +122,15 @@ def _check_closed_loop_against_reference(engine, case):
     assert states[0].code_counter == len(ref)
 
 
+@pytest.mark.parametrize("fs", [10e6, 16.368e6, 20e6, 25e6])
 @pytest.mark.parametrize("kind,parts", [(1, 0), (1, 1), (1, 4), (0, 0), (0, 2)])
-def test_closed_loop_at_25_mhz_matches_the_oracle_loops(engine, kind, parts):
-    """The golden trajectories are 4 MHz runs (per-sample correlator variant).  At 25 MHz the tracking kernel
-    uses the boundary variant; the same loops (oracle restatement of the plugins, pinned by the goldens) run on
-    the CPU over the same synthetic stream must give the same integers and the same loop quantities."""
-    fs, ms, prn = 25e6, 130, 11
-    n = int(ms * fs * 1e-3)
+def test_closed_loop_at_10_to_25_mhz_matches_the_oracle_loops(engine, kind, parts, fs):
+    """The golden trajectories are 4 MHz runs (per-sample correlator variant).  From 10 to 25 MHz the tracking kernel
+    uses the boundary variants (8-sample groups at 10 and 16.368 MHz, 16-sample groups or the single-round core at 20 and
+    25 MHz); the same loops (oracle restatement of the plugins, pinned by the goldens) run on the CPU over the same
+    synthetic stream must give the same integers and the same loop quantities."""
+    ms, prn = 130, 11
+    n = int(ms * fs * 1e-3) // 8 * 8
     sat = dict(prn=prn, doppler=2250.0, code_phase=417.3, phase=0.2, amp=9.0)
     engine.iq_alloc(n, FMT_CI8)
     engine.code_slots(1)
