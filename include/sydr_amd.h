@@ -39,7 +39,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define SDR_ABI_VERSION 5   /* 5: + sdr_bank_tick_mirrored_begin / _end, sdr_iq_upload_queue, sdr_host_alloc / _free, options "tick_server" + sdr_tick_server_stats, "bind_thread_to_device" (additive); 4: + sdr_build_id, sdr_epl_plan_create_dev, sdr_bank_tick_mirrored, sdr_iq_upload_begin, sdr_block_schedule, sdr_bank_step_begin / _end (additive) */
+#define SDR_ABI_VERSION 5   /* 5 (still): + sdr_acq_refine, sdr_acq_refine_bins (additive); 5: + sdr_bank_tick_mirrored_begin / _end, sdr_iq_upload_queue, sdr_host_alloc / _free, options "tick_server" + sdr_tick_server_stats, "bind_thread_to_device" (additive); 4: + sdr_build_id, sdr_epl_plan_create_dev, sdr_bank_tick_mirrored, sdr_iq_upload_begin, sdr_block_schedule, sdr_bank_step_begin / _end (additive) */
 
 typedef struct sdr_engine sdr_engine;
 
@@ -245,6 +245,47 @@ int sdr_serial_search(sdr_engine* e, const int32_t* code_slots, int n_prn, int64
                       int64_t* peak_code, double* peak_ratio, double* corr_map, int* n_bins_out);
 int sdr_two_peak_compare_ss(sdr_engine* e, const double* corr_map, int n_rows, int n_cols,
                             int64_t* peak_bin, int64_t* peak_code, double* peak_ratio);
+
+/* ------------------------------- fine carrier frequency and bit edge behind an acquisition
+ * The step between acquisition and tracking of the textbook receiver (code wipe-off over ~10 ms, a fine frequency
+ * search), which the reference left out: sdr_pcps hands tracking the best bin of its grid, up to half a grid step off
+ * (125 Hz with the shipped 250 Hz), and a Costas loop alone (the Borre plugin) never pulls that in.
+ * For each item -- code_slot, start_sample = s0, a ring index at which a code period begins (what the plugins'
+ * enterTracking leaves in currentSample), carrier_hz = f0, the coarse carrier (IF included), code_hz -- with
+ * M = n_periods, S = n_segments:
+ *   N = nearbyint(fs * L / code_hz) samples per code period (L = the chips staged in the slot), code_step = code_hz / fs.
+ *   Stage 1: segment (m, s), m < M, s < S, covers window samples [a, b), a = m*N + (s*N)/S, b = m*N + ((s+1)*N)/S
+ *   (integer divisions).  z[m][s] = the prompt tap (spacing 0.0) of EPL above on ring samples s0+a .. s0+b-1 (modulo the
+ *   capacity) with carrier_hz = f0, rem_carrier = (-(f0*2.0*pi*a/fs)) mod 2*pi, rem_code = ((s*N)/S) * code_step, that
+ *   code_step.  tau[m][s] = (a + b - 1) / 2 / fs.
+ *   Stage 2: K = 2*floor(span_hz/step_hz) + 1 frequencies d_k = (k - (K-1)/2) * step_hz;
+ *   Z[m][k] = sum_s z[m][s] * exp(-2j*pi*d_k*tau[m][s]).  Hypothesis h = 0: no sign change inside the window;
+ *   h = 1..M-1: periods m >= h enter with the opposite sign.  P[h][k] = | sum_m sign_h(m) * Z[m][k] |^2.
+ *   Result: (h*, k*) = first maximum of P in row-major (h, k) order; fine_hz = f0 + d_k*, fine_idx = k*, bit_edge = h*
+ *   (reported, not acted upon), power = P[h*][k*], power_no_edge = max_k P[0][k].
+ * One call serves all items (one per searched PRN); both stages run on the device on the engine's stream, sums in a
+ * fixed order (two identical calls return identical bits).  power (nullable) receives P as [n_items][n_periods][K],
+ * segment_sums (nullable) z as [n_items][n_periods][n_segments][2].
+ * A window that holds NaN / Inf samples (a float ring) is reported, not guessed: power = power_no_edge = NaN,
+ * fine_hz = f0, fine_idx = (K-1)/2, bit_edge = 0.
+ * SDR_ERR_INVALID: NULL items / results, n_items < 1, n_periods outside 1..20 (one data bit: at most one edge),
+ * n_segments outside 1..64, a bad grid, a slot that is not staged; SDR_ERR_UNSUPPORTED: n_segments > N, K > 4096, a code
+ * period of more than ~16 000 chips or 2^30 samples; SDR_ERR_RANGE: a window longer than the ring, a negative start_sample. */
+typedef struct sdr_refine_item {
+    int32_t code_slot, reserved;
+    int64_t start_sample;
+    double carrier_hz, code_hz;
+} sdr_refine_item;
+typedef struct sdr_refine_result {
+    double fine_hz, power, power_no_edge;
+    int32_t fine_idx, bit_edge;
+} sdr_refine_result;
+/* K of the grid above (host helper like sdr_pcps_bins; 0 for a bad grid). */
+int sdr_acq_refine_bins(double span_hz, double step_hz);
+int sdr_acq_refine(sdr_engine* e, const sdr_refine_item* items, int n_items, double fs, int n_periods, int n_segments,
+                   double span_hz, double step_hz, sdr_refine_result* results,
+                   double* power /* nullable [n_items][n_periods][K] */,
+                   double* segment_sums /* nullable [n_items][n_periods][n_segments][2] */);
 
 /* ------------------------------------------------- closed-loop tracking
  * On-device loop closure: one persistent workgroup per

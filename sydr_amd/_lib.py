@@ -37,6 +37,22 @@ EPL_ITEM_DTYPE = np.dtype([("code_slot", np.int32), ("n_samples", np.int32), ("s
                            ("code_step", np.float64)], align=True)
 
 
+class RefineItem(C.Structure):
+    _fields_ = [("code_slot", C.c_int32), ("reserved", C.c_int32), ("start_sample", C.c_int64),
+                ("carrier_hz", C.c_double), ("code_hz", C.c_double)]
+
+
+class RefineResult(C.Structure):
+    _fields_ = [("fine_hz", C.c_double), ("power", C.c_double), ("power_no_edge", C.c_double),
+                ("fine_idx", C.c_int32), ("bit_edge", C.c_int32)]
+
+
+REFINE_ITEM_DTYPE = np.dtype([("code_slot", np.int32), ("reserved", np.int32), ("start_sample", np.int64),
+                              ("carrier_hz", np.float64), ("code_hz", np.float64)], align=True)
+REFINE_RESULT_DTYPE = np.dtype([("fine_hz", np.float64), ("power", np.float64), ("power_no_edge", np.float64),
+                                ("fine_idx", np.int32), ("bit_edge", np.int32)], align=True)
+
+
 class SynthSat(C.Structure):
     _fields_ = [("prn", C.c_int32), ("flags", C.c_int32), ("doppler_hz", C.c_double),
                 ("code_phase", C.c_double), ("carrier_phase", C.c_double), ("amplitude", C.c_double)]
@@ -156,6 +172,8 @@ _PROTOTYPES = {
                                     _VP, _VP, C.POINTER(C.c_int)]),
     "sdr_two_peak_compare_ss": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                           C.POINTER(C.c_double)]),
+    "sdr_acq_refine_bins": (C.c_int, [C.c_double, C.c_double]),
+    "sdr_acq_refine": (C.c_int, [_VP, _VP, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double, _VP, _VP, _VP]),
     "sdr_track_cluster": (C.c_int, [_VP, C.c_int]),
     "sdr_track_closed_loop": (C.c_int, [_VP, C.c_int, _VP, C.POINTER(LoopCfg), C.c_int, _VP]),
     "sdr_track_closed_loop_bits": (C.c_int, [_VP, C.c_int, _VP, C.POINTER(LoopCfg), C.c_int, _VP, _VP, C.c_int, _VP]),

@@ -19,7 +19,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from ..engine import FMT_CF64, FMT_CI16, FMT_CI8, Engine
+from ..engine import FMT_CF64, FMT_CI16, FMT_CI8, Engine, make_refine_items
 from ..utils.devicering import CircularBuffer
 from ..utils.enumerations import ChannelState
 from ..utils.enumerations import ChannelMessage
@@ -535,23 +535,35 @@ class ChannelManager:
     def _acquire(self, acquiring):
         """Channels with enough samples for their search, grouped by search geometry: ONE sdr_pcps call per group
         (the forward transforms of the Doppler-mixed slab are shared by all PRNs).  Plugins that replace the
-        search seam (e.g. the SerialSearch plugin) run their own."""
+        search seam (e.g. the SerialSearch plugin) run their own.  Channels configured for the fine frequency search
+        (`fine_frequency_ms`) wait for its window as well, and a group's channels are refined in ONE sdr_acq_refine call
+        behind their search."""
         packets, groups = [], {}
         for ch in acquiring:
-            if self.sharedBuffer.getNbUnreadSamples(ch.currentSample) < ch.acq_requiredSamples:
+            if self.sharedBuffer.getNbUnreadSamples(ch.currentSample) < getattr(ch, "acq_waitSamples", ch.acq_requiredSamples):
                 continue
             if getattr(type(ch), "runSignalSearch", None) is not _default_search():
                 packets.extend(ch._processHandler())
                 continue
             ch._ensure_code()
             r = ch.acquisitionRequest()
-            key = (r["start"], r["fs"], r["if_hz"], r["doppler_range"], r["doppler_step"], r["coh"], r["noncoh"])
+            fine = (ch.acq_fineFrequencyMs, ch.acq_fineFrequencyStep, ch.FINE_FREQUENCY_SEGMENTS) \
+                if getattr(ch, "fineFrequencySearch", False) else None
+            key = (r["start"], r["fs"], r["if_hz"], r["doppler_range"], r["doppler_step"], r["coh"], r["noncoh"], fine)
             groups.setdefault(key, []).append(ch)
-        for (start, fs, if_hz, rng, step, coh, noncoh), chans in groups.items():
+        for (start, fs, if_hz, rng, step, coh, noncoh, fine), chans in groups.items():
             pb, pc, pr, cmap = self.engine.pcps([c.codeSlot for c in chans], start, fs, if_hz, rng, step, coh, noncoh,
                                                 want_map=self.keepCorrelationMap)
+            refined = None
+            if fine is not None:
+                reqs = [ch.fineFrequencyRequest([int(pb[k]), int(pc[k])]) for k, ch in enumerate(chans)]
+                items = make_refine_items(*([q[name] for q in reqs] for name in ("code_slot", "start_sample", "carrier_hz", "code_hz")))
+                # (the fine grid spans +-one bin of the search: noise may have picked the bin next to the nearest)
+                refined = self.engine.acq_refine(items, fs, n_periods=fine[0], n_segments=fine[2], span_hz=step, step_hz=fine[1])
             for k, ch in enumerate(chans):
                 ch._injectedAcquisition = (cmap[k] if cmap is not None else None, [int(pb[k]), int(pc[k])], float(pr[k]))
+                if refined is not None:
+                    ch._injectedFine = refined[k]
                 packets.append(ch.runAcquisition())
         return [p for p in packets if p is not None]
 

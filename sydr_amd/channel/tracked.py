@@ -17,7 +17,8 @@ from __future__ import annotations
 
 import numpy as np
 
-from ..utils.constants import GPS_L1CA_CODE_FREQ, GPS_L1CA_CODE_MS, GPS_L1CA_CODE_SIZE_BITS
+from ..engine import make_refine_items
+from ..utils.constants import GPS_L1CA_CODE_FREQ, GPS_L1CA_CODE_MS, GPS_L1CA_CODE_SIZE_BITS, LNAV_MS_PER_BIT
 from ..utils.devicering import CircularBuffer as DeviceRing
 from ..utils.enumerations import ChannelMessage, ChannelState, GNSSSignalType, GNSSSystems, TrackingFlags
 from .bank import tracking_packet
@@ -97,6 +98,17 @@ class DeviceTrackedChannel(GpuCorrelatorSeams, Channel, metaclass=_ViewMeta):
         self.acq_threshold = float(configuration['threshold'])
         ms = self.acq_nonCoherentIntegration * self.acq_coherentIntegration
         self.acq_requiredSamples = int(self.rfSignal.samplingFrequency * 1e-3 * ms)
+        # optional (no counterpart in the reference): a fine frequency search over `fine_frequency_ms` code periods from the
+        # sample tracking starts at, on a grid of `fine_frequency_step` Hz across +-doppler_steps (sdr_acq_refine);
+        # absent or 0: off -- tracking starts on the search grid's bin, as the reference does
+        self.acq_fineFrequencyMs = int(configuration.get('fine_frequency_ms', 0))
+        self.acq_fineFrequencyStep = float(configuration.get('fine_frequency_step', 5.0))
+        if not 0 <= self.acq_fineFrequencyMs <= LNAV_MS_PER_BIT or not self.acq_fineFrequencyStep > 0.0:
+            raise ValueError(f"fine_frequency_ms must lie in 0..{LNAV_MS_PER_BIT} (one data bit) and fine_frequency_step be positive")
+        if self.fineFrequencySearch and self.acq_waitSamples > self.rfBuffer.maxSize:
+            raise ValueError(f"the ring holds {self.rfBuffer.maxSize} samples; the search and the fine frequency window behind it "
+                             f"need {self.acq_waitSamples} (a longer ring_ms, or a shorter fine_frequency_ms)")
+        self._acqFine = None
 
     def setTracking(self, configuration):
         """Fill this channel's sdr_loop_cfg row and the state tracking starts from (kaplan:256-338, borre:206-259)."""
@@ -240,13 +252,60 @@ class DeviceTrackedChannel(GpuCorrelatorSeams, Channel, metaclass=_ViewMeta):
         return [] if packet is None else [packet]
 
     # ------------------------------------------------------------------ acquisition (host seams around sdr_pcps)
+    FINE_FREQUENCY_SEGMENTS = 8     # segments a code period is cut into for the fine search (sdr_acq_refine's n_segments)
+    _injectedFine = None            # set by a batching manager: this channel's row of its group's sdr_acq_refine results
+
+    @property
+    def fineFrequencySearch(self) -> bool:
+        """The fine search belongs to the default PCPS seam: a plugin that replaces `runSignalSearch` (the SerialSearch
+        plugin) ignores the two keys."""
+        return self.acq_fineFrequencyMs > 0 and type(self).runSignalSearch is GpuCorrelatorSeams.runSignalSearch
+
+    @property
+    def acq_waitSamples(self) -> int:
+        """Unread samples acquisition waits for: the searched slab, and with the fine search on the window behind it --
+        it starts at the sample tracking starts at, which `enterTracking` puts between one code period before and one
+        sample past the slab's end, so it ends inside (fine_frequency_ms + 1) more milliseconds."""
+        if not self.fineFrequencySearch:
+            return self.acq_requiredSamples
+        return self.acq_requiredSamples + (self.acq_fineFrequencyMs + 1) * int(self.rfSignal.samplingFrequency * 1e-3)
+
     def runAcquisition(self):
-        if self.rfBuffer.getNbUnreadSamples(self.currentSample) < self.acq_requiredSamples:
+        if self.rfBuffer.getNbUnreadSamples(self.currentSample) < self.acq_waitSamples:
             return None
         correlationMap = self.runSignalSearch()
         indices, ratio = self.runPeakFinder(correlationMap)
+        self._acqFine = self.runFineFrequencySearch(indices) if self.fineFrequencySearch else None
         self.postAcquisitionUpdate(indices)
         return self.prepareResultsAcquisition(correlationMap, indices, ratio)
+
+    def trackingStart(self, acqIndices):
+        """(coarse carrier, ring index of the sample tracking starts at) for a PCPS peak [bin, code sample]: what
+        `enterTracking` is about to set, and what the fine search starts from."""
+        start = self._firstEpochSample(int(np.round(acqIndices[1])))
+        return self.rfSignal.interFrequency - self.searchedFrequency(acqIndices[0]), start % self.rfBuffer.maxSize
+
+    def _firstEpochSample(self, code_offset: int) -> int:
+        """The sample the first tracking epoch starts at (the searched samples are skipped, the first epoch
+        is taken back, + offset + 1) -- ONE expression for `enterTracking` and for the fine search's window."""
+        first_epoch = int(self._bank.state["n_samples"][self._row])
+        return self.currentSample + self.acq_requiredSamples - first_epoch + code_offset + 1
+
+    def fineFrequencyRequest(self, acqIndices):
+        """This channel's sdr_refine_item (a batching manager refines a search group's channels in one call)."""
+        carrier, start = self.trackingStart(acqIndices)
+        return dict(code_slot=self.codeSlot, start_sample=start, carrier_hz=carrier, code_hz=GPS_L1CA_CODE_FREQ)
+
+    def runFineFrequencySearch(self, acqIndices):
+        """-> the sdr_refine_result row (fine_hz, power, power_no_edge, fine_idx, bit_edge) for this acquisition."""
+        if self._injectedFine is not None:
+            fine, self._injectedFine = self._injectedFine, None
+            return fine
+        r = self.fineFrequencyRequest(acqIndices)
+        items = make_refine_items(r["code_slot"], r["start_sample"], r["carrier_hz"], r["code_hz"])
+        return self._ensure_code().acq_refine(items, self.rfSignal.samplingFrequency, n_periods=self.acq_fineFrequencyMs,
+                                              n_segments=self.FINE_FREQUENCY_SEGMENTS, span_hz=self.acq_dopplerSteps,
+                                              step_hz=self.acq_fineFrequencyStep)[0]
 
     def searchedFrequency(self, bin_idx):
         """Frequency of Doppler bin `bin_idx` of this channel's search grid (np.arange(-range, range + 1, step))."""
@@ -258,19 +317,23 @@ class DeviceTrackedChannel(GpuCorrelatorSeams, Channel, metaclass=_ViewMeta):
         the first epoch is taken back, + offset + 1)."""
         self.codeOffset = int(np.round(code_offset_samples))
         self.carrierFrequency = carrier_hz
-        first_epoch = int(self._bank.state["n_samples"][self._row])
-        self.currentSample = self.currentSample + self.acq_requiredSamples - first_epoch + self.codeOffset + 1
+        self.currentSample = self._firstEpochSample(self.codeOffset)
         self.channelState = ChannelState.TRACKING
 
     def postAcquisitionUpdate(self, acqIndices):
         """PCPS peak [bin, code sample] -> NCO start values (kaplan:217-235 / borre:301-316)."""
-        self.enterTracking(self.rfSignal.interFrequency - self.searchedFrequency(acqIndices[0]), acqIndices[1])
+        carrier = self.rfSignal.interFrequency - self.searchedFrequency(acqIndices[0])
+        if self._acqFine is not None:                    # the fine search's frequency instead of the grid's bin
+            carrier = float(self._acqFine["fine_hz"])
+        self.enterTracking(carrier, acqIndices[1])
 
     def prepareResultsAcquisition(self, correlationMap, acqIndices, acqPeakRatio):
         packet = self.prepareResults()
         packet.update(type=ChannelMessage.ACQUISITION_UPDATE, carrierFrequency=self.carrierFrequency,
                       codeOffset=self.codeOffset, frequency_idx=acqIndices[0], code_idx=acqIndices[1],
                       correlation_map=correlationMap, peak_ratio=acqPeakRatio)
+        if self._acqFine is not None:
+            packet.update(fine_frequency_idx=int(self._acqFine["fine_idx"]), bit_edge=int(self._acqFine["bit_edge"]))
         return packet
 
     # ------------------------------------------------------------------ tracking = one device step

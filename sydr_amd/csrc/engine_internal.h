@@ -103,6 +103,8 @@ struct sdr_engine {
     bool pcps_no_shared_spectra = false;   // "pcps_no_shared_spectra": one forward transform per bin, as before round 5
     DevBuf pcps_tickets;          // one word per PRN: the second sweep's last workgroup of a PRN divides the two peaks (pcps_fused.h)
     int pcps_tickets_n = 0;
+    DevBuf refine_ws;             // sdr_acq_refine (refine.hip): [items][segment sums][results][power table]
+    std::vector<char> refine_host;   // ... and the host image of its item list (the source of the upload)
     DevBuf track_state, track_cfg;
     int n_cus = 0;              // compute units of the device (sizes the closed-loop clusters)
     int track_force_parts = 0;  // diagnostics / tests: 0 = choose, else 1, 2, 4 or 8 workgroups per channel

@@ -8,10 +8,19 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (EPL_ITEM_DTYPE, FMT_CF32, FMT_CF64, FMT_CI16, FMT_CI8, LOOP_CFG_DTYPE, TRACK_EPOCH_DTYPE,
-                   TRACK_STATE_DTYPE, LoopCfg, SynthSat, TrackState, check, ptr)
+from ._lib import (EPL_ITEM_DTYPE, FMT_CF32, FMT_CF64, FMT_CI16, FMT_CI8, LOOP_CFG_DTYPE, REFINE_ITEM_DTYPE,
+                   REFINE_RESULT_DTYPE, TRACK_EPOCH_DTYPE, TRACK_STATE_DTYPE, LoopCfg, SynthSat, TrackState, check, ptr)
 
-__all__ = ["Engine", "EplPlan", "Bank", "make_items", "FMT_CI8", "FMT_CI16", "FMT_CF32", "FMT_CF64"]
+__all__ = ["Engine", "EplPlan", "Bank", "make_items", "make_refine_items", "FMT_CI8", "FMT_CI16", "FMT_CF32", "FMT_CF64"]
+
+
+def make_refine_items(code_slot, start_sample, carrier_hz, code_hz=1.023e6) -> np.ndarray:
+    """Pack acquisition results (scalars or equal-length arrays) into sdr_refine_item records."""
+    arrs = np.broadcast_arrays(code_slot, start_sample, carrier_hz, code_hz)
+    items = np.zeros(arrs[0].shape, dtype=REFINE_ITEM_DTYPE).reshape(-1)
+    for name, a in zip(("code_slot", "start_sample", "carrier_hz", "code_hz"), arrs):
+        items[name] = np.asarray(a).reshape(-1)
+    return items
 
 
 def make_items(code_slot, n_samples, start_sample, carrier_hz, rem_carrier, rem_code, code_step) -> np.ndarray:
@@ -452,6 +461,27 @@ class Engine:
                                           float(doppler_step), int(noncoh), ptr(pb), ptr(pc), ptr(pr),
                                           ptr(cmap) if want_map else None, C.byref(nb)))
         return pb, pc, pr, cmap
+
+    def acq_refine_bins(self, span_hz: float, step_hz: float) -> int:
+        return int(self._lib.sdr_acq_refine_bins(float(span_hz), float(step_hz)))
+
+    def acq_refine(self, items, fs, n_periods=10, n_segments=8, span_hz=125.0, step_hz=5.0, want_tables=False):
+        """Fine carrier frequency and bit edge behind an acquisition (sdr_acq_refine): `items` = sdr_refine_item records
+        (REFINE_ITEM_DTYPE, see `make_refine_items`) -- one call for all of them.  -> results (REFINE_RESULT_DTYPE:
+        fine_hz, power, power_no_edge, fine_idx, bit_edge), and with want_tables also (power[n][n_periods][K],
+        segment_sums[n][n_periods][n_segments] complex)."""
+        items = np.ascontiguousarray(items, dtype=REFINE_ITEM_DTYPE).reshape(-1)
+        n = len(items)
+        res = np.zeros(n, dtype=REFINE_RESULT_DTYPE)
+        power = z = None
+        if want_tables:
+            k = max(0, self.acq_refine_bins(span_hz, step_hz))
+            power = np.empty((n, max(0, int(n_periods)), k), dtype=np.float64)
+            z = np.empty((n, max(0, int(n_periods)), max(0, int(n_segments))), dtype=np.complex128)
+        check(self._lib.sdr_acq_refine(self._h, ptr(items), n, float(fs), int(n_periods), int(n_segments), float(span_hz),
+                                       float(step_hz), ptr(res), ptr(power) if want_tables else None,
+                                       ptr(z) if want_tables else None))
+        return (res, power, z) if want_tables else res
 
     def two_peak_compare_ss(self, cmap: np.ndarray):
         cmap = np.ascontiguousarray(cmap, dtype=np.float64)
