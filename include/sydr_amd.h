@@ -39,7 +39,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define SDR_ABI_VERSION 5   /* 5 (still): + sdr_acq_refine, sdr_acq_refine_bins (additive); 5: + sdr_bank_tick_mirrored_begin / _end, sdr_iq_upload_queue, sdr_host_alloc / _free, options "tick_server" + sdr_tick_server_stats, "bind_thread_to_device" (additive); 4: + sdr_build_id, sdr_epl_plan_create_dev, sdr_bank_tick_mirrored, sdr_iq_upload_begin, sdr_block_schedule, sdr_bank_step_begin / _end (additive) */
+#define SDR_ABI_VERSION 5   /* 5 (still): + sdr_iq_packing, sdr_iq_packed_bytes, sdr_iq_upload_packed / _begin / _queue (additive); 5 (still): + sdr_acq_refine, sdr_acq_refine_bins (additive); 5: + sdr_bank_tick_mirrored_begin / _end, sdr_iq_upload_queue, sdr_host_alloc / _free, options "tick_server" + sdr_tick_server_stats, "bind_thread_to_device" (additive); 4: + sdr_build_id, sdr_epl_plan_create_dev, sdr_bank_tick_mirrored, sdr_iq_upload_begin, sdr_block_schedule, sdr_bank_step_begin / _end (additive) */
 
 typedef struct sdr_engine sdr_engine;
 
@@ -97,7 +97,8 @@ int sdr_prof_reset(sdr_engine* e);
  * (PRN, bin) transform per workgroup, would run (256 transforms or more); "pcps_no_spectra_cache" = 1
  * recomputes conj(fft(code)) in every search, as the reference does (channel_l1ca_kaplan.py:184-185), instead of keeping
  * the spectra of the staged codes; "ingest_by_copy_command" = 1 moves the slabs of sdr_iq_upload_begin / sdr_bank_tick
- * into the ring with a copy command instead of the ingest kernel; "track_one_launch_tick" = 1 runs a one-epoch step
+ * into the ring with a copy command instead of the ingest kernel (a packed slab of sdr_iq_upload_packed_begin: into HBM with
+ * a copy command, its unpack kernel then reads no host memory); "track_one_launch_tick" = 1 runs a one-epoch step
  * (sdr_bank_tick*, sdr_bank_step with n_epochs = 1) as one workgroup per channel instead of on the cluster a block of
  * epochs would use (other order of additions); "track_two_launch_tick" = 1 runs that cluster's one-epoch step as two
  * launches cut at the exchange of the parts' sums instead of one (the part that draws its channel's last ticket
@@ -522,6 +523,42 @@ int sdr_iq_upload_queue(sdr_engine* e, const void* iq, int64_t n_samples, int64_
  * device).  The block is the caller's until sdr_host_free; the engine keeps no pointer to it. */
 int sdr_host_alloc(sdr_engine* e, size_t bytes, void** out);
 int sdr_host_free(sdr_engine* e, void* block);
+
+/* ------------------------------------------------- packed recordings: 1, 2 or 4 bits per component
+ * What most front ends deliver and most recordings hold: several I,Q samples to a byte.  They cross the host link packed and
+ * are widened on the device INTO the ci8 ring (what enters is converted where it enters, as the ring's sign flip is): after a
+ * packed upload the ring holds, byte for byte, what unpacking on the host followed by the unpacked namesake of the call would
+ * have left, and nothing downstream of the ring changes.
+ * A packing is `bits` in {1, 2, 4} per component, a field order and a table of 1 << bits int8 levels:
+ *   fields per byte F = 8 / bits; samples per byte SPB = 4 / bits (4, 2, 1);
+ *   sample k of a slab has component c (0 = I, 1 = Q) in field j = 2k + c: byte j / F, position p = j % F;
+ *   the field sits at bit bits * p of its byte (least significant field first), or at bits * (F - 1 - p) with SDR_PACK_MSB_FIRST;
+ *   code = (byte >> shift) & ((1 << bits) - 1), value = levels[code] -- any int8, -128 included.
+ * n_samples of a packed slab is a multiple of SPB; the slab occupies n_samples * 2 * bits / 8 bytes from any byte address.
+ * The packing travels with every call: the engine keeps none.  Each call is its unpacked namesake with one more step and keeps
+ * that namesake's contract: sdr_iq_upload_packed is synchronous; _begin has copied the slab before it returns (up to 1 MiB of
+ * packed bytes through the page-locked staging halves, longer ones by waiting; a block of sdr_host_alloc on a 16-byte boundary
+ * whose destination is whole 16-byte ring granules is read in place under the rule stated for sdr_iq_upload_begin) and is
+ * ordered before what is queued afterwards; _queue leaves the block with the caller until sdr_engine_sync: a copy command
+ * brings the packed bytes into a staging buffer in HBM (the engine's, grown on demand, released with the ring) and the unpack
+ * kernel follows it on the engine's stream.  Any ring_offset >= 0, taken modulo the capacity, wrapping at the ring's end;
+ * n_samples up to the capacity.  Readers on other streams are ordered behind the unpack, not only behind the copy.
+ * A packed slab is never parked for the tick's own launch or the resident tick server's doormen (those pull raw granules): a
+ * slab parked earlier goes into the ring first, a resident server is told to leave, and the unpack is a launch of its own in
+ * front of the tick's.  Folding the unpack into the tick's launch is not done here.
+ * SDR_ERR_INVALID: NULL arguments, bits not 1 / 2 / 4, unknown flag bits, n_samples not a multiple of SPB;
+ * SDR_ERR_UNSUPPORTED: the ring is not SDR_FMT_CI8; SDR_ERR_RANGE / SDR_ERR_STATE as sdr_iq_upload gives them.
+ * sdr_prof_enable scopes: "unpack_kernel", "call_upload_packed". */
+#define SDR_PACK_MSB_FIRST 1
+typedef struct sdr_iq_packing {
+    int32_t bits, flags;
+    int8_t levels[16];    /* the first 1 << bits are used */
+} sdr_iq_packing;
+/* Bytes n_samples occupy packed (host helper like sdr_pcps_bins; < 0: invalid packing or sample count). */
+int64_t sdr_iq_packed_bytes(const sdr_iq_packing* pk, int64_t n_samples);
+int sdr_iq_upload_packed(sdr_engine* e, const sdr_iq_packing* pk, const void* packed, int64_t n_samples, int64_t ring_offset);
+int sdr_iq_upload_packed_begin(sdr_engine* e, const sdr_iq_packing* pk, const void* packed, int64_t n_samples, int64_t ring_offset);
+int sdr_iq_upload_packed_queue(sdr_engine* e, const sdr_iq_packing* pk, const void* packed, int64_t n_samples, int64_t ring_offset);
 
 /* Host-only helper of a receiver that tracks ahead (no device work): `records[n_ch][n_cols]` hold `done[r]` epochs per channel
  * computed in one sdr_bank_step while the host still feeds its per-millisecond loop (receiver.py:120-131); this works out

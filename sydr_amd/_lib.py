@@ -53,6 +53,14 @@ REFINE_RESULT_DTYPE = np.dtype([("fine_hz", np.float64), ("power", np.float64), 
                                 ("fine_idx", np.int32), ("bit_edge", np.int32)], align=True)
 
 
+class IqPacking(C.Structure):
+    """sdr_iq_packing (include/sydr_amd.h): bits per component, SDR_PACK_* flags, the table of levels."""
+    _fields_ = [("bits", C.c_int32), ("flags", C.c_int32), ("levels", C.c_int8 * 16)]
+
+
+PACK_MSB_FIRST = 1
+
+
 class SynthSat(C.Structure):
     _fields_ = [("prn", C.c_int32), ("flags", C.c_int32), ("doppler_hz", C.c_double),
                 ("code_phase", C.c_double), ("carrier_phase", C.c_double), ("amplitude", C.c_double)]
@@ -191,6 +199,10 @@ _PROTOTYPES = {
     "sdr_bank_tick_mirrored_end": (C.c_int, [_VP, _VP, C.POINTER(TickMirror)]),
     "sdr_iq_upload_begin": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64]),
     "sdr_iq_upload_queue": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64]),
+    "sdr_iq_packed_bytes": (C.c_int64, [C.POINTER(IqPacking), C.c_int64]),
+    "sdr_iq_upload_packed": (C.c_int, [_VP, C.POINTER(IqPacking), _VP, C.c_int64, C.c_int64]),
+    "sdr_iq_upload_packed_begin": (C.c_int, [_VP, C.POINTER(IqPacking), _VP, C.c_int64, C.c_int64]),
+    "sdr_iq_upload_packed_queue": (C.c_int, [_VP, C.POINTER(IqPacking), _VP, C.c_int64, C.c_int64]),
     "sdr_tick_server_stats": (C.c_int, [_VP, C.POINTER(C.c_int64)]),
     "sdr_tick_server_phases": (C.c_int, [_VP, C.POINTER(C.c_double)]),
     "sdr_tick_server_tracker_phases": (C.c_int, [_VP, C.POINTER(C.c_double)]),

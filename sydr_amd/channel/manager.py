@@ -65,6 +65,11 @@ class ChannelManager:
         self._engine_queues_slabs = hasattr(engine, "iq_upload_begin")      # (asked once, not every millisecond)
         buffersize = int(self.rfSignal.samplingFrequency * 1e-3 * ring_ms)   # 100 ms, as channelManager.py:57
         fmt = {np.int8: FMT_CI8, np.int16: FMT_CI16}.get(getattr(rfSignal, "fileDataType", None), FMT_CF64)
+        # a packed recording (1, 2 or 4 bits per component: signal/packing.py) crosses the link packed and is widened into a
+        # ci8 ring on the device; its slabs are uint8 arrays of packed bytes
+        self._packing = getattr(rfSignal, "packing", None)
+        if self._packing is not None:
+            fmt = FMT_CI8
         self.sharedBuffer = CircularBuffer(buffersize, rfSignal.dtype, engine=engine, fmt=fmt)
         self.resultQueue = None
         self.keepCorrelationMap = keepCorrelationMap
@@ -142,21 +147,26 @@ class ChannelManager:
         self._ra_ms = max(0, int(nbMilliseconds))
         self._EpochSchedule = EpochSchedule
 
+    def _samples_in(self, data) -> int:
+        """Samples a raw slab holds: packed bytes of a packed recording, interleaved I,Q otherwise."""
+        if self._packing is not None and data.dtype == np.uint8:
+            return data.size * self._packing.samples_per_byte
+        return data.size // 2
+
     def _recording_position(self, data):
         """Sample index of `data` inside the recording when it is the slab `rfSignal` handed out last (or equals it
         byte for byte), else None."""
-        rec_of = getattr(self.rfSignal, "_recording", None)
-        if rec_of is None or not getattr(self.rfSignal, "filepath", None) or not isinstance(data, np.ndarray):
+        samples_of = getattr(self.rfSignal, "samples", None)
+        if samples_of is None or not getattr(self.rfSignal, "filepath", None) or not isinstance(data, np.ndarray):
+            return None
+        n = self._samples_in(data)
+        first = int(self.rfSignal.position) - n
+        if first < 0 or data.dtype != self.rfSignal.fileDataType or data.ndim != 1:
             return None
         try:
-            rec = rec_of()
-        except OSError:
+            there = samples_of(first, n)
+        except (OSError, ValueError):
             return None
-        n = data.size // 2
-        first = int(self.rfSignal.position) - n
-        if first < 0 or data.dtype != rec.dtype or data.ndim != 1:
-            return None
-        there = rec[2 * first:2 * (first + n)]
         same = data.__array_interface__["data"][0] == there.__array_interface__["data"][0] or np.array_equal(data, there)
         return first if same else None
 
@@ -168,7 +178,7 @@ class ChannelManager:
         ahead = self._ahead
         if ahead is not None and ahead["bank"] is not bank:
             ahead = self._ahead = None                        # (the bank was re-created from the mirror: it starts the block again)
-        if data.size != 2 * spt or self.nbChannels == 0:
+        if not isinstance(data, np.ndarray) or self._samples_in(data) != spt or self.nbChannels == 0:
             if ahead is not None:
                 raise ValueError("addNewRFData: a block of the recording is being tracked ahead; the slab must be its next millisecond")
             return False
@@ -185,12 +195,12 @@ class ChannelManager:
                 return False
             if first is None:
                 return False
-            rec = self.rfSignal._recording()
+            total = self.rfSignal.totalSamples
             cids = np.array([ch.channelID for ch in chans], dtype=np.int32)
         unread = bank.unread(cids)
         if ahead is None:
             room = (ring.maxSize - int(unread.max())) // spt - 1      # milliseconds the ring can take without overwriting
-            k = min(self._ra_ms, (rec.size // 2 - first) // spt, room)
+            k = min(self._ra_ms, (total - first) // spt, room)
             if any(ch.channelState is ChannelState.IDLE for ch in self.channels.values()):
                 # a channel started later begins reading at ring position 0 (channel.py:93) with everything up to the write
                 # index unread: samples written there ahead of the write index's own wrap would be searched in place of the
@@ -199,8 +209,8 @@ class ChannelManager:
             if k < 4:
                 return False
             self._flush_pending()
-            block = rec[2 * first:2 * (first + k * spt)]
-            self.engine.iq_upload(block, ring.idxWrite)
+            block = self.rfSignal.samples(first, k * spt)
+            self._upload_block(block, k * spt, ring.idxWrite)
             bank.flush()
         # every epoch that is complete inside the block: ONE persistent launch of as many epochs as every channel has room
         # for, then a launch per group of channels with equal numbers of epochs left (one or two more: an epoch that just fits)
@@ -266,14 +276,14 @@ class ChannelManager:
         ring, bank, spt = self.sharedBuffer, self.bank, self._readahead.spt
         if not self._ra_ms or not self.PREFETCH or not hasattr(bank.device, "step_begin") or pending_lost.any():
             return
-        rec = self.rfSignal._recording()
+        total = self.rfSignal.totalSamples
         # the ring has to hold both blocks beside whatever any channel has not read yet -- the block's own channels (what
         # they will have left at its end) and everybody else who is active (a late joiner lags by its acquisition time)
         mine = set(int(c) for c in cids)
         behind = [int(unread_then.max())] + [ring.getNbUnreadSamples(ch.currentSample) for ch in self.channels.values()
                                              if ch.channelState is not ChannelState.IDLE and ch.channelID not in mine]
         room = (ring.maxSize - max(behind)) // spt - k_now - 1
-        k = min(self._ra_ms, (rec.size // 2 - first) // spt, room)
+        k = min(self._ra_ms, (total - first) // spt, room)
         if any(ch.channelState is ChannelState.IDLE for ch in self.channels.values()):
             # a channel started later begins reading at ring position 0 (channel.py:93: currentSample = 0) -- samples the
             # plain loop would still hold there must not be replaced ahead of their time: the block stops at the ring's end
@@ -287,8 +297,8 @@ class ChannelManager:
         if (budget <= 0).any():
             return
         n_ep = int(budget.min())
-        block = rec[2 * first:2 * (first + k * spt)]
-        self.engine.iq_upload(block, (ring.idxWrite + k_now * spt) % ring.maxSize)
+        block = self.rfSignal.samples(first, k * spt)
+        self._upload_block(block, k * spt, (ring.idxWrite + k_now * spt) % ring.maxSize)
         bank.flush()
         bank.device.step_begin(cids, n_ep)
         self._ahead = dict(bank=bank, first=first, k=k, cids=cids, n_ep=n_ep, block=block)
@@ -297,9 +307,10 @@ class ChannelManager:
         ra = self._readahead
         spt = ra.spt
         # (the usual case costs one address comparison: the slab IS the recording's next millisecond)
-        ok = isinstance(data, np.ndarray) and data.size == 2 * spt and (
-            data.__array_interface__["data"][0] == ra.raw_address + 2 * ra.slab_no * spt * ra.raw.itemsize
-            or np.array_equal(data, ra.raw[2 * ra.slab_no * spt:2 * (ra.slab_no + 1) * spt]))
+        per_slab = ra.raw.size // (ra.slab_no + ra.slabs_left)       # elements of the block's array per millisecond
+        ok = isinstance(data, np.ndarray) and data.size == per_slab and (
+            data.__array_interface__["data"][0] == ra.raw_address + ra.slab_no * per_slab * ra.raw.itemsize
+            or np.array_equal(data, ra.raw[ra.slab_no * per_slab:(ra.slab_no + 1) * per_slab]))
         if not ok:
             raise ValueError("addNewRFData: while a read-ahead block is replayed the slab must be the recording's next "
                              f"millisecond (sample {ra.first + ra.slab_no * spt}); call enableReadAhead(0) to feed other data")
@@ -321,7 +332,15 @@ class ChannelManager:
         if self._pending:
             self._flush_pending()
         ring = self.sharedBuffer
-        if (type(data) is np.ndarray and data.ndim == 1 and data.dtype == ring.rawDtype and data.flags.c_contiguous
+        packing = self._packing
+        packed = (packing is not None and type(data) is np.ndarray and data.dtype == np.uint8 and data.ndim == 1
+                  and data.flags.c_contiguous and data.size)
+        if packed:
+            # packed bytes of a packed recording: over the link as they are, widened where they enter the ring
+            staged, offset, count = data, ring.idxWrite, data.size * packing.samples_per_byte
+            if ring.maxSize % count:
+                raise ValueError("Data shift need to be a multiple from the max buffer size.")
+        elif (type(data) is np.ndarray and data.ndim == 1 and data.dtype == ring.rawDtype and data.flags.c_contiguous
                 and not data.size & 1 and data.size):
             # the usual slab -- interleaved I,Q in the ring's own element type: nothing to convert (stage() does the rest)
             staged, offset, count = data, ring.idxWrite, data.size >> 1
@@ -332,7 +351,13 @@ class ChannelManager:
         if ring.full and (self._unread_max is None or self._unread_max + count > ring.maxSize):
             self._guard_unread(count)
         self._unread_max = None
-        if staged.nbytes > self.DEFER_BYTES or not self._engine_queues_slabs:
+        if packed:
+            if staged.nbytes > self.DEFER_BYTES or not self._engine_queues_slabs:
+                self.engine.iq_upload_packed(staged, count, packing, offset)
+            else:
+                self.engine.iq_upload_packed_begin(staged, count, packing, offset)
+                self._pending = True
+        elif staged.nbytes > self.DEFER_BYTES or not self._engine_queues_slabs:
             self.engine.iq_upload(staged, offset)
         else:
             # the reference copies at this point (circularbuffer.py:54-82); so does this: the samples are copied out of
@@ -341,6 +366,13 @@ class ChannelManager:
             self.engine.iq_upload_begin(staged, offset)
             self._pending = True
         ring.shiftIdxWrite(count)
+
+    def _upload_block(self, block, n_samples: int, offset: int):
+        """A block of the recording (a view from `rfSignal.samples`) into the ring at `offset`, waited for."""
+        if self._packing is not None and block.dtype == np.uint8:
+            self.engine.iq_upload_packed(block, n_samples, self._packing, offset)
+        else:
+            self.engine.iq_upload(block, offset)
 
     def _guard_unread(self, count: int):
         """Refuse to overwrite samples a tracking channel has not consumed yet (the reference would silently wrap:

@@ -384,7 +384,7 @@ void sdr_engine_destroy(sdr_engine* e) {
     DevBuf* bufs[] = {&e->ws_items,  &e->ws_out,   &e->ws_spacing, &e->ws_setups, &e->ws_stats, &e->pcps_fwd,   &e->pcps_a,
                       &e->pcps_b,    &e->pcps_code, &e->pcps_code2, &e->pcps_tickets, &e->pcps_spec_off, &e->pcps_tw,   &e->pcps_map,   &e->pcps_csum,
                       &e->pcps_part, &e->pcps_res,  &e->track_state, &e->track_cfg,
-                      &e->pcps_blu,  &e->pcps_blu_x, &e->pcps_blu_a, &e->pcps_blu_b, &e->pcps_work, &e->pcps_theta, &e->refine_ws};
+                      &e->pcps_blu,  &e->pcps_blu_x, &e->pcps_blu_a, &e->pcps_blu_b, &e->pcps_work, &e->pcps_theta, &e->refine_ws, &e->unpack_stage};
     for (DevBuf* b : bufs)
         if (b->ptr) (void)hipFree(b->ptr);
     for (DevBuf& b : e->plan_pool)
@@ -487,6 +487,10 @@ int sdr_iq_alloc(sdr_engine* e, int64_t capacity_samples, int fmt) {
         SDR_HIP(hipFree(e->iq));
         e->iq = nullptr;
         e->iq_capacity = 0;
+    }
+    if (e->unpack_stage.ptr) {          // (the staging of packed uploads goes with the ring it served)
+        SDR_HIP(hipFree(e->unpack_stage.ptr));
+        e->unpack_stage = DevBuf();
     }
     // (256 bytes of slack behind the ring: the chip-aligned correlator loads whole 56-byte windows, whose tail
     // may reach past the last sample of the last epoch)
@@ -621,6 +625,40 @@ int sdr_iq_flush_server_slab(sdr_engine* e) {
     return SDR_OK;
 }
 
+// One of the two page-locked staging halves of a receiver tick's slab, at least `bytes` long and free to be written: whoever
+// fills it records slab_done[half] behind the transfer that reads it and sets slab_busy[half].
+int sdr_slab_half_acquire(sdr_engine* e, size_t bytes, int* half_out, char** stage_out) {
+    if (bytes > e->slab_bytes) {
+        SDR_HIP(hipStreamSynchronize(e->stream));   // (an earlier slab's DMA may still read the old buffer)
+        if (e->slab_pinned) SDR_HIP(hipHostFree(e->slab_pinned));
+        e->slab_pinned = nullptr;
+        e->slab_bytes = 0;
+        // (a multiple of 16: the second half starts on a granule boundary too -- the kernels that pull a half load 8 or 16 bytes per lane)
+        const size_t want = bytes < 131072 ? 131072 : (bytes * 2 + 15) / 16 * 16;
+        hipError_t err = hipHostMalloc(&e->slab_pinned, 2 * want, hipHostMallocDefault);   // two halves, used alternately
+        if (err != hipSuccess) {
+            e->slab_pinned = nullptr;
+            return sdr_fail(SDR_ERR_NOMEM, "hipHostMalloc(%zu) failed: %s", 2 * want, hipGetErrorString(err));
+        }
+        e->slab_bytes = want;
+        e->slab_busy[0] = e->slab_busy[1] = false;   // (the synchronisation above completed whatever read the old halves)
+    }
+    // Two halves, used alternately, each guarded by an event recorded behind the transfer that reads it: a tick normally
+    // ends with a synchronisation of this stream, but a tick in which no channel is ready does not, and a C caller may
+    // queue any number of slabs -- a half is written again only when the transfer out of it has completed (the wait is
+    // free in the common case: the event completed with the tick before last).
+    e->slab_flip ^= 1;
+    const int half = e->slab_flip;
+    if (e->slab_busy[half]) {
+        SDR_HIP(hipEventSynchronize(e->slab_done[half]));
+        e->slab_busy[half] = false;
+    }
+    if (!e->slab_done[half]) SDR_HIP(hipEventCreateWithFlags(&e->slab_done[half], hipEventDisableTiming));
+    *half_out = half;
+    *stage_out = (char*)e->slab_pinned + (half ? e->slab_bytes : 0);
+    return SDR_OK;
+}
+
 // Asynchronous upload of a caller-owned (pageable) slab: small slabs -- a receiver tick brings 1 ms, 50 KB at 25 MHz --
 // go through a page-locked staging buffer of the engine (one memcpy here, then a DMA the stream does not wait for the
 // host on); the caller's pointer is not kept past return either way.
@@ -659,32 +697,9 @@ int sdr_iq_upload_async(sdr_engine* e, const void* iq, int64_t n_samples, int64_
             return SDR_OK;
         }
     }
-    if (bytes > e->slab_bytes) {
-        SDR_HIP(hipStreamSynchronize(e->stream));   // (an earlier slab's DMA may still read the old buffer)
-        if (e->slab_pinned) SDR_HIP(hipHostFree(e->slab_pinned));
-        e->slab_pinned = nullptr;
-        e->slab_bytes = 0;
-        const size_t want = bytes < 131072 ? 131072 : bytes * 2;
-        hipError_t err = hipHostMalloc(&e->slab_pinned, 2 * want, hipHostMallocDefault);   // two halves, used alternately
-        if (err != hipSuccess) {
-            e->slab_pinned = nullptr;
-            return sdr_fail(SDR_ERR_NOMEM, "hipHostMalloc(%zu) failed: %s", 2 * want, hipGetErrorString(err));
-        }
-        e->slab_bytes = want;
-        e->slab_busy[0] = e->slab_busy[1] = false;   // (the synchronisation above completed whatever read the old halves)
-    }
-    // Two halves, used alternately, each guarded by an event recorded behind the transfer that reads it: a tick normally
-    // ends with a synchronisation of this stream, but a tick in which no channel is ready does not, and a C caller may
-    // queue any number of slabs -- a half is written again only when the transfer out of it has completed (the wait is
-    // free in the common case: the event completed with the tick before last).
-    e->slab_flip ^= 1;
-    const int half = e->slab_flip;
-    if (e->slab_busy[half]) {
-        SDR_HIP(hipEventSynchronize(e->slab_done[half]));
-        e->slab_busy[half] = false;
-    }
-    if (!e->slab_done[half]) SDR_HIP(hipEventCreateWithFlags(&e->slab_done[half], hipEventDisableTiming));
-    char* stage = (char*)e->slab_pinned + (half ? e->slab_bytes : 0);
+    int half = 0;
+    char* stage = nullptr;
+    if (int rc = sdr_slab_half_acquire(e, bytes, &half, &stage)) return rc;
     memcpy(stage, iq, bytes);
     // A KERNEL pulls the slab out of the page-locked buffer (16 bytes per lane over PCIe) instead of a copy command: the
     // tick's launch follows it on the same queue with nothing but the queue's own ordering in between, where a DMA

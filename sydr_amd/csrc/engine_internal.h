@@ -153,6 +153,8 @@ struct sdr_engine {
     const void* srv_slab_src = nullptr;  // where it lies: a staging half or the caller's block
     std::vector<std::pair<const char*, size_t>> host_blocks;   // what sdr_host_alloc has handed out
     int64_t srv_slab_off = 0, srv_slab_n = 0;
+    DevBuf unpack_stage;             // packed recordings (unpack.hip): the packed bytes of a queued / synchronous upload in HBM, read by the unpack
+                                     // kernel behind their copy command on `stream` (whose order is all the guard it needs); released with the ring
     bool ingest_by_copy = false;     // "ingest_by_copy_command": queued slabs go into the ring by hipMemcpyAsync, not by the ingest kernel
     bool pcps_no_spec_cache = false; // "pcps_no_spectra_cache": conj(fft(code)) recomputed by every search, as the reference does (kaplan:184-185)
     bool pcps_fused = true;          // map-free search at N = 125 x 200 of a round of 256 transforms or more: one workgroup per (PRN, bin) transform (pcps_fused.h); "pcps_fused" = 0: the two-kernel sweeps
@@ -183,6 +185,9 @@ int sdr_tick_server_stop(sdr_engine* e);
 void sdr_tick_server_free(sdr_engine* e);
 // engine.hip: the slab waiting in a staging half (srv_slab_*) into the ring by the ingest kernel, on the engine's stream
 int sdr_iq_flush_server_slab(sdr_engine* e);
+// engine.hip: one of the two page-locked staging halves of a tick's slab (slab_pinned), >= bytes, free to be written; the
+// caller records slab_done[*half] behind whatever reads it and sets slab_busy[*half]
+int sdr_slab_half_acquire(sdr_engine* e, size_t bytes, int* half, char** stage);
 // Ring samples [offset, offset + n) (modulo capacity) are being written on e->stream: readers on other streams are ordered
 // behind the write (sdr_iq_order_reader).
 void sdr_iq_mark_written(sdr_engine* e, int64_t ring_offset, int64_t n_samples);

@@ -342,6 +342,41 @@ class Engine:
         if status:
             check(status)
 
+    # ------------------------------------------------------------------ packed recordings (signal/packing.py)
+    def _packed_args(self, packed, n_samples, packing):
+        """(sdr_iq_packing, address, n_samples) of a packed slab: contiguous uint8, as long as the samples need."""
+        if not (isinstance(packed, np.ndarray) and packed.ndim == 1 and packed.dtype == np.uint8 and packed.flags.c_contiguous):
+            raise ValueError("packed samples are a contiguous 1-D uint8 array")
+        n_samples = int(n_samples)
+        pk = getattr(packing, "_c_struct", None)
+        if pk is None:
+            pk = _lib.IqPacking(int(packing.bits), _lib.PACK_MSB_FIRST if packing.msb_first else 0)
+            for i, v in enumerate(packing.levels.tolist()):
+                pk.levels[i] = v
+            packing._c_struct = pk
+        need = self._lib.sdr_iq_packed_bytes(C.byref(pk), n_samples)
+        if need >= 0 and packed.size != need:
+            raise ValueError(f"{n_samples} samples at {packing.bits} bits are {need} packed bytes, {packed.size} given")
+        # (need < 0: the library refuses the call below with its own status and text)
+        return pk, packed.ctypes.data, n_samples
+
+    def iq_upload_packed(self, packed: np.ndarray, n_samples: int, packing, ring_offset: int = 0):
+        """Packed 1- / 2- / 4-bit I,Q into a ci8 ring, widened on the device (sdr_iq_upload_packed): synchronous."""
+        pk, address, n = self._packed_args(packed, n_samples, packing)
+        check(self._lib.sdr_iq_upload_packed(self._h, C.byref(pk), address, n, int(ring_offset)))
+
+    def iq_upload_packed_begin(self, packed: np.ndarray, n_samples: int, packing, ring_offset: int = 0):
+        """iq_upload_packed without the wait (sdr_iq_upload_packed_begin): a receiver tick's slab, copied before the call
+        returns (a `host_alloc` block on a 16-byte boundary is read in place, as with `iq_upload_begin`)."""
+        pk, address, n = self._packed_args(packed, n_samples, packing)
+        check(self._lib.sdr_iq_upload_packed_begin(self._h, C.byref(pk), address, n, int(ring_offset)))
+
+    def iq_upload_packed_queue(self, packed: np.ndarray, n_samples: int, packing, ring_offset: int = 0):
+        """A packed chunk of a recording queued for the ring (sdr_iq_upload_packed_queue): `packed` stays alive and
+        unchanged until `sync()`."""
+        pk, address, n = self._packed_args(packed, n_samples, packing)
+        check(self._lib.sdr_iq_upload_packed_queue(self._h, C.byref(pk), address, n, int(ring_offset)))
+
     def host_alloc(self, n_elements: int, dtype=np.int8) -> np.ndarray:
         """Page-locked host memory as a NumPy array (sdr_host_alloc); `host_free(array)` gives it back -- the array must not
         be used afterwards."""
