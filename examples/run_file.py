@@ -2,6 +2,7 @@
 """Track an IQ recording with the reference's own configuration files.
 
     python examples/run_file.py receiver.ini [--ms 2000] [--block 80 | --read-ahead 50] [--csv out.csv]
+                                              [--profile N_TAPS]
 
 `receiver.ini` is the reference's receiver configuration (config/receiver.ini: [DEFAULT] nb_channels /
 ms_to_process, [RFSIGNAL], [SATELLITES] include_prn, [CHANNELS] gps_l1ca = <channel ini>).  What the reference's
@@ -35,6 +36,8 @@ def main(argv=None):
     ap.add_argument("--block", type=int, default=80, help="epochs per closed-loop block once all channels track (0: per-tick only)")
     ap.add_argument("--read-ahead", type=int, default=0, help="keep the per-millisecond loop and let the manager track this many ms ahead (overrides --block)")
     ap.add_argument("--csv", default=None, help="write one line per tracking epoch")
+    ap.add_argument("--profile", type=int, default=0, metavar="N_TAPS",
+                    help="print |correlation function| of every channel's last epoch at the end: N_TAPS taps across +-2 chips")
     args = ap.parse_args(argv)
 
     rcfg = configparser.ConfigParser()
@@ -93,6 +96,13 @@ def main(argv=None):
         if ch.channelState is not ChannelState.IDLE:
             bits = "".join(str(int(b)) for b in getattr(ch, "navBits", [])[:40])
             print(f"channel {ch.channelID} G{ch.satelliteID:02d}: state {ch.channelState.name}, carrier {ch.carrierFrequency:+.2f} Hz, bits {bits}")
+    if args.profile > 0:
+        step = 4.0 / (args.profile - 1) if args.profile > 1 else 0.0
+        for cid, prof in mgr.correlationProfiles(-2.0 if args.profile > 1 else 0.0, step, args.profile).items():
+            mag = np.hypot(prof[:, 0], prof[:, 1])
+            print(f"channel {cid} correlation profile, {args.profile} taps from {-2.0 if args.profile > 1 else 0.0:+.3f} chips "
+                  f"in steps of {step:.4f}: peak {mag.max():.1f} at tap {int(mag.argmax())}")
+            print("  " + " ".join(f"{v / max(mag.max(), 1e-300):.3f}" for v in mag))
     print(f"{ms} ms of signal, {n_track} tracking epochs in {dt:.2f} s = {ms * 1e-3 / dt:.2f}x real time")
     if out:
         out.close()

@@ -39,7 +39,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define SDR_ABI_VERSION 5   /* 5 (still): + sdr_iq_packing, sdr_iq_packed_bytes, sdr_iq_upload_packed / _begin / _queue (additive); 5 (still): + sdr_acq_refine, sdr_acq_refine_bins (additive); 5: + sdr_bank_tick_mirrored_begin / _end, sdr_iq_upload_queue, sdr_host_alloc / _free, options "tick_server" + sdr_tick_server_stats, "bind_thread_to_device" (additive); 4: + sdr_build_id, sdr_epl_plan_create_dev, sdr_bank_tick_mirrored, sdr_iq_upload_begin, sdr_block_schedule, sdr_bank_step_begin / _end (additive) */
+#define SDR_ABI_VERSION 5   /* 5 (still): + sdr_corr_profile, option "corr_profile_per_sample" (additive); 5 (still): + sdr_iq_packing, sdr_iq_packed_bytes, sdr_iq_upload_packed / _begin / _queue (additive); 5 (still): + sdr_acq_refine, sdr_acq_refine_bins (additive); 5: + sdr_bank_tick_mirrored_begin / _end, sdr_iq_upload_queue, sdr_host_alloc / _free, options "tick_server" + sdr_tick_server_stats, "bind_thread_to_device" (additive); 4: + sdr_build_id, sdr_epl_plan_create_dev, sdr_bank_tick_mirrored, sdr_iq_upload_begin, sdr_block_schedule, sdr_bank_step_begin / _end (additive) */
 
 typedef struct sdr_engine sdr_engine;
 
@@ -246,6 +246,34 @@ int sdr_serial_search(sdr_engine* e, const int32_t* code_slots, int n_prn, int64
                       int64_t* peak_code, double* peak_ratio, double* corr_map, int* n_bins_out);
 int sdr_two_peak_compare_ss(sdr_engine* e, const double* corr_map, int n_rows, int n_cols,
                             int64_t* peak_bin, int64_t* peak_code, double* peak_ratio);
+
+/* ------------------------------------------- the correlation function on a dense tap grid
+ * What a multi-correlator receiver shows of the peak it tracks (multipath and signal-quality monitoring, discriminator
+ * S-curves, the correlation plot beside the acquisition map): the taps of EPL above on the grid
+ *   s_j = first_chips + j * step_chips,   0 <= j < n_taps <= SDR_CORR_MAX_TAPS
+ * (fp64 exactly as written, one multiply and one add: first + step * np.arange(T)), for every item, in ONE pass over the
+ * samples.  out[i][j] = (I, Q) of what EPL returns for item i with the single spacing s_j:
+ *   - the same carrier replica;
+ *   - the same ceil(linspace(rem_code + s_j, code_step*n + rem_code + s_j, n, endpoint=False)) index in the reference's
+ *     operation order;
+ *   - padded index p standing for chip c[(p - 1) mod L] (Python's modulo) for ANY p: the call indexes the chip table
+ *     modulo the code length itself, so taps many chips out and epochs of several code periods need no
+ *     sdr_code_slots_ex periods.
+ * Any finite first_chips / step_chips (zero, negative, not dyadic); all four ring formats; a window may cross the ring's
+ * end.  Synchronous on the engine's stream like sdr_epl_batch; sums are added in a fixed order (two identical calls return
+ * identical bits).  A window that holds NaN / Inf samples (a float ring) gives non-finite outputs for that item.
+ * Once the carrier is wiped off, a tap's sum is a sum over CHIPS of the chip's sign times a difference of prefix sums of
+ * the wiped samples (~1000 terms per tap at any rate, not one per sample); below ~8 samples per chip -- or with
+ * sdr_set_option(e, "corr_profile_per_sample", 1) at any rate (tests, A/B timing) -- the taps are summed sample by
+ * sample instead: same definition, results equal to rounding.
+ * SDR_ERR_INVALID: NULL pointers, n_items < 1, n_taps outside 1..1024, non-finite first_chips / step_chips, fs <= 0, a
+ * slot that is not staged, n_samples < 1, code_step <= 0 or non-finite NCO parameters; SDR_ERR_RANGE: a window longer
+ * than the ring, a negative start_sample (the rules of sdr_epl_batch); SDR_ERR_UNSUPPORTED: a chip index that would leave
+ * +-2^30; SDR_ERR_STATE: no ring or no code slots.
+ * sdr_prof_enable scopes: "corr_items_upload", "corr_walk_kernel" / "corr_per_sample_kernel", "call_corr_profile". */
+#define SDR_CORR_MAX_TAPS 1024
+int sdr_corr_profile(sdr_engine* e, const sdr_epl_item* items, int n_items, double first_chips, double step_chips,
+                     int n_taps, double fs, double* out /* [n_items][n_taps][2] = I, Q */);
 
 /* ------------------------------- fine carrier frequency and bit edge behind an acquisition
  * The step between acquisition and tracking of the textbook receiver (code wipe-off over ~10 ms, a fine frequency

@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SYDR_AMD_LIB") or os.path.join(_HERE, "libsydr_amd.so")  # (override: A/B builds of tools/ab_compare.sh)
 
 SDR_MAX_TAPS = 8
+SDR_CORR_MAX_TAPS = 1024
 FMT_CI8, FMT_CI16, FMT_CF32, FMT_CF64 = 0, 1, 2, 3
 _FMT_NP = {FMT_CI8: np.int8, FMT_CI16: np.int16, FMT_CF32: np.float32, FMT_CF64: np.float64}
 
@@ -182,6 +183,7 @@ _PROTOTYPES = {
                                           C.POINTER(C.c_double)]),
     "sdr_acq_refine_bins": (C.c_int, [C.c_double, C.c_double]),
     "sdr_acq_refine": (C.c_int, [_VP, _VP, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double, _VP, _VP, _VP]),
+    "sdr_corr_profile": (C.c_int, [_VP, _VP, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, _VP]),
     "sdr_track_cluster": (C.c_int, [_VP, C.c_int]),
     "sdr_track_closed_loop": (C.c_int, [_VP, C.c_int, _VP, C.POINTER(LoopCfg), C.c_int, _VP]),
     "sdr_track_closed_loop_bits": (C.c_int, [_VP, C.c_int, _VP, C.POINTER(LoopCfg), C.c_int, _VP, _VP, C.c_int, _VP]),

@@ -19,7 +19,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from ..engine import FMT_CF64, FMT_CI16, FMT_CI8, Engine, make_refine_items
+from ..engine import FMT_CF64, FMT_CI16, FMT_CI8, Engine, make_items, make_refine_items
 from ..utils.devicering import CircularBuffer
 from ..utils.enumerations import ChannelState
 from ..utils.enumerations import ChannelMessage
@@ -398,6 +398,27 @@ class ChannelManager:
         if channelID not in self.channels:
             raise ValueError("Channel ID does not exist.")
         return self.channels[channelID]
+
+    def correlationProfiles(self, first: float, step: float, n_taps: int):
+        """{channelID: float64[n_taps, 2]}: the correlation function of the latest epoch of every channel that is tracking
+        and not lost, on the tap grid first + step * arange(n_taps) [chips] -- ONE library call for all of them
+        (sdr_corr_profile).  A channel that has run no epoch yet, or whose last epoch the ring no longer holds
+        (`DeviceTrackedChannel.correlationProfile` raises for it), has no entry."""
+        cids, rows = [], []
+        for cid, ch in self.channels.items():
+            if ch.channelState is not ChannelState.TRACKING or not hasattr(ch, "correlationProfileItem") or ch.lostLock:
+                continue
+            try:
+                rows.append(ch.correlationProfileItem())
+            except ValueError:
+                continue
+            cids.append(cid)
+        if not cids:
+            return {}
+        items = make_items(*(np.array(col) for col in zip(*rows)))
+        out = self.engine.corr_profile(items, first, step, n_taps, self.rfSignal.samplingFrequency)
+        self._pending = False         # (the call waited for the engine's stream: a queued slab is in the ring)
+        return {cid: out[k] for k, cid in enumerate(cids)}
 
     def close(self):
         self._flush_pending()

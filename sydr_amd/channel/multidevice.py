@@ -115,6 +115,15 @@ class MultiDeviceChannelManager:
         """Index (into `devices` / `engines`) of the device that tracks this channel."""
         return self._part_of[channelID]
 
+    def correlationProfiles(self, first: float, step: float, n_taps: int):
+        """{channelID: float64[n_taps, 2]} over all devices: one library call per device (ChannelManager.correlationProfiles),
+        the results merged."""
+        out = {}
+        for part in self.parts:
+            if part.nbChannels:
+                out.update(part.correlationProfiles(first, step, n_taps))
+        return dict(sorted(out.items()))
+
     def close(self):
         for part in self.parts:
             part.close()

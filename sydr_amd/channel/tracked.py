@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from ..engine import make_refine_items
+from ..engine import make_items, make_refine_items
 from ..utils.constants import GPS_L1CA_CODE_FREQ, GPS_L1CA_CODE_MS, GPS_L1CA_CODE_SIZE_BITS, LNAV_MS_PER_BIT
 from ..utils.devicering import CircularBuffer as DeviceRing
 from ..utils.enumerations import ChannelMessage, ChannelState, GNSSSignalType, GNSSSystems, TrackingFlags
@@ -204,6 +204,7 @@ class DeviceTrackedChannel(GpuCorrelatorSeams, Channel, metaclass=_ViewMeta):
         self.signalID = GNSSSignalType.GPS_L1_CA
         eng = self._ensure_code()                       # Gold code generated by the device LFSR kernel
         self._bank.state["code_slot"][self._row] = self.codeSlot
+        self._bank.last["n_samples"][self._row] = 0     # (no epoch of THIS satellite yet: correlationProfileItem)
         chips = eng.read_code(self.codeSlot).astype(np.float64)
         self.code = np.r_[chips[-1], chips, chips[0]]   # padded table of kaplan:104-107, kept for API compatibility
 
@@ -341,6 +342,38 @@ class DeviceTrackedChannel(GpuCorrelatorSeams, Channel, metaclass=_ViewMeta):
         """The correlator seam (kaplan:378-401), kept for function-level use: the taps of the NEXT epoch for the
         current NCO state, open loop -- the state does not advance (runTracking / the manager's tick do that)."""
         return self._correlate()
+
+    def correlationProfileItem(self):
+        """The latest epoch of this channel as sdr_epl_item fields (code_slot, n_samples, start_sample, carrier_hz,
+        rem_carrier, rem_code, code_step), from its record in the bank's `last` row: what the epoch's correlators ran with.
+        ValueError when the channel has run no epoch yet (since it was given its satellite), when the device has parked
+        it (`lostLock`: nothing guards the ring for it any more), or when the ring no longer holds that epoch's samples --
+        the samples between the epoch's first one and the write index are then more than the ring's capacity (the
+        channel's unread samples, which the manager never lets pass the capacity, plus the epoch itself).
+        The last test reads the ring's write index: with read-ahead on (`ChannelManager.enableReadAhead`) the manager
+        uploads whole blocks AHEAD of that index and protects unread samples only, so the epoch just read may have been
+        overwritten although the index says otherwise -- profile from the per-tick loop or `runBlock`, not under
+        read-ahead."""
+        if self.lostLock:
+            raise ValueError(f"channel {self.channelID} lost lock on the device: its last epoch is not kept in the ring")
+        rec = self._bank.last[self._row]
+        n = int(rec["n_samples"])
+        if n <= 0:
+            raise ValueError(f"channel {self.channelID} has run no tracking epoch yet: there is no epoch to profile")
+        ring = self.rfBuffer
+        unread = ring.getNbUnreadSamples((int(rec["start_sample"]) + n) % ring.maxSize)
+        if unread + n > ring.maxSize:
+            raise ValueError(f"the ring no longer holds the last epoch of channel {self.channelID} "
+                             f"({n} samples, {unread} written behind it, ring of {ring.maxSize})")
+        return (int(self._bank.state["code_slot"][self._row]), n, int(rec["start_sample"]), float(rec["carrier_hz_in"]),
+                float(rec["rem_carrier_in"]), float(rec["rem_code_in"]), float(rec["code_step_in"]))
+
+    def correlationProfile(self, first: float, step: float, n_taps: int):
+        """The correlation function of this channel's LATEST epoch on the tap grid first + step * arange(n_taps) [chips]
+        (sdr_corr_profile): the shape of the peak the channel tracks.  -> float64[n_taps, 2] = I, Q per tap; the grid
+        (-0.5, 0.5, 3) gives the epoch's E, P, L again.  ValueError: see `correlationProfileItem`."""
+        items = make_items(*self.correlationProfileItem())
+        return self._bank.engine.corr_profile(items, first, step, n_taps, self.rfSignal.samplingFrequency)[0]
 
     def runTracking(self):
         if self.lostLock or self.rfBuffer.getNbUnreadSamples(self.currentSample) < self.track_requiredSamples:

@@ -168,6 +168,12 @@ struct sdr_engine {
     bool prof = false;
     std::vector<ProfRecord> prof_records;
     std::vector<hipEvent_t> prof_pool;
+
+    // sdr_corr_profile (corr_profile.hip)
+    DevBuf corr_ws;               // [items][out]
+    std::vector<char> corr_host;  // the host image of its item list (the source of the upload)
+    size_t corr_lds_allowed[8] = {0};   // dynamic LDS its kernels were last allowed, per (format, form)
+    bool corr_per_sample = false; // "corr_profile_per_sample": the per-sample form at any rate (tests, A/B timing)
 };
 
 int sdr_devbuf_reserve(sdr_engine* e, DevBuf* b, size_t bytes);

@@ -39,6 +39,27 @@ def EPL(rfData, code, samplingFrequency, carrierFrequency, remainingCarrier, rem
     return [float(v) for v in out]
 
 
+def CorrelationProfile(rfData, code, samplingFrequency, carrierFrequency, remainingCarrier, remainingCode, codeStep,
+                       first, step, n_taps):
+    """The correlation function of one epoch on the tap grid first + step * arange(n_taps) [chips]: what `EPL` returns
+    for every one of those spacings, in one pass over the samples (sdr_corr_profile; no counterpart in the reference,
+    whose EPL stops at three taps).  Arguments as for `EPL`.  -> float64[n_taps, 2] = I, Q per tap."""
+    rf = np.squeeze(np.asarray(rfData, dtype=np.complex128))
+    n = rf.size
+    chips = np.asarray(code)[1:-1]
+    eng = get_engine()
+    if getattr(eng, "n_slots", 0) < 4:
+        eng.code_slots(4, 4092)
+    eng.set_code(2, chips.astype(np.int8))
+    cap = (n + 15) // 8 * 8
+    if eng.iq_fmt != FMT_CF64 or eng.iq_capacity < cap:
+        eng.iq_alloc(cap, FMT_CF64)
+    eng.iq_upload(rf, 0)
+    items = make_items(2, n, 0, float(carrierFrequency), float(remainingCarrier), float(remainingCode),
+                       float(codeStep))
+    return eng.corr_profile(items, float(first), float(step), int(n_taps), samplingFrequency)[0]
+
+
 def EPL_nonvector(rfData, code, samplingFrequency, carrierFrequency, remainingCarrier, remainingCode, codeStep,
                   correlatorsSpacing):
     """The reference's per-sample Python loop (tracking.py:65-88) computes what `EPL` computes; served by the same
@@ -134,6 +155,6 @@ def FLLassistedPLL_3rdOrder(phaseInput: float, freqInput: float, w0f: float, w0p
     return out, vel, acc
 
 
-__all__ = ["EPL", "EPL_nonvector", "generateReplica", "getCorrelator", "LoopFiltersCoefficients", "DLL_NNEML",
+__all__ = ["EPL", "CorrelationProfile", "EPL_nonvector", "generateReplica", "getCorrelator", "LoopFiltersCoefficients", "DLL_NNEML",
            "PLL_costa", "FLL_ATAN2", "FLL_ATAN", "phase_unwrap", "BorreLoopFilter", "FLLassistedPLL_2ndOrder",
            "FLLassistedPLL_3rdOrder"]

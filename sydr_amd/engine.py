@@ -444,6 +444,17 @@ class Engine:
                                       ptr(out)))
         return out
 
+    def corr_profile(self, items: np.ndarray, first: float, step: float, n_taps: int, fs: float) -> np.ndarray:
+        """The correlation function on the tap grid first + step * arange(n_taps) [chips] (sdr_corr_profile): what
+        `epl_batch` returns for every one of those spacings, in one pass over the samples -- any spacing, up to 1024 taps.
+        `items` as for `epl_batch` (`make_items`).  -> float64[n_items, n_taps, 2] = I, Q."""
+        items = np.ascontiguousarray(items, dtype=EPL_ITEM_DTYPE).reshape(-1)
+        n_taps = int(n_taps)
+        out = np.empty((len(items), max(0, min(n_taps, _lib.SDR_CORR_MAX_TAPS)), 2), dtype=np.float64)
+        check(self._lib.sdr_corr_profile(self._h, ptr(items), len(items), float(first), float(step), n_taps, float(fs),
+                                         ptr(out)))
+        return out
+
     def epl_plan_dev(self, device_items: int, n_items: int, spacing, fs) -> EplPlan:
         """A plan of n_items items that are already in device memory at address device_items."""
         return EplPlan(self, None, spacing, fs, device_items=device_items, n_items=n_items)
