@@ -93,6 +93,9 @@ __device__ __forceinline__ int wave_min_i32(int x) {
 #define SDR_BIASED_CVT 1
 #endif
 constexpr double kCvtBias = 4224.0;
+#ifndef SDR_ALT_PAIRS
+#define SDR_ALT_PAIRS 1      // (0: every sample on one set of register pairs, as before -- for A/B runs of the s_nop pads)
+#endif
 // The double lives in a register PAIR whose low word stays zero for the whole epoch: only the high word is rewritten
 // (built from a fresh zero each time, the compiler spends a v_mov on every low word and nothing is gained).
 typedef uint32_t sdr_u32x2 __attribute__((ext_vector_type(2)));
@@ -234,6 +237,47 @@ __host__ __device__ inline void chip_setup(int n, int64_t start_sample, int64_t 
     }
 }
 
+// ---- The block walk of the straight-line forms (KS / KI).  A lane carries the first sample S of its block and the 32-bit
+// fraction f of that boundary on the Q32.32 line (u = S * 2^32 + f), nothing wider.  Everything a block needs beyond S is
+// the CARRY of a 32-bit add onto f: the block is M + 1 samples long iff f + lo(T) carries (hi(u + T) - hi(u) - M), tap t
+// switches at m_t + 1 iff f + lo(delta_t) carries, and the lane's next block starts Dmin + 1 samples on iff f + lo(stride * T)
+// carries.  A carry is 0 or 1: none of the range checks of the integer formulation can fire here.  The sums f + lo(T),
+// f + lo(delta_t) are also the fractions of those boundaries, which the 2^-16 window looks at: the same blocks as before go
+// through the exact re-evaluation.  __host__ __device__: tests/csrc/chip_walk_dump.hip walks epochs with these on the CPU.
+struct ChipWalk {
+    int S;
+    uint32_t f;
+};
+__host__ __device__ __forceinline__ ChipWalk chip_walk_at(uint64_t u) { return ChipWalk{(int)(u >> 32), (uint32_t)u}; }
+__host__ __device__ __forceinline__ bool chip_carry(uint32_t a, uint32_t b, uint32_t& sum) { return __builtin_add_overflow(a, b, &sum); }
+__host__ __device__ __forceinline__ bool chip_near_sample(uint32_t fr) { return fr + 0x10000u < 0x20000u; }
+// The lane's next block, `stride` chips on (stride_lo = lo(stride * T), Dmin = hi(stride * T)); returns dd.
+__host__ __device__ __forceinline__ bool chip_walk_step(ChipWalk& w, uint32_t stride_lo, int Dmin) {
+    const bool dd = chip_carry(w.f, stride_lo, w.f);
+    w.S = w.S + Dmin + (dd ? 1 : 0);
+    return dd;
+}
+// The last round of an epoch: a lane beyond the last whole chip re-does that chip (w_last), it does not walk on.
+__host__ __device__ __forceinline__ ChipWalk chip_walk_clamp(const ChipWalk& w, bool inside, const ChipWalk& w_last) {
+    return ChipWalk{inside ? w.S : w_last.S, inside ? w.f : w_last.f};
+}
+// The flags of the block that starts at fraction f: dn, ds[t] (t != A; whole-chip taps, KI: none) and whether one of its
+// boundaries lies within 2^-16 of a sample.
+template <int NT, int KI>
+__host__ __device__ __forceinline__ void chip_walk_flags(uint32_t f, uint32_t T_lo, const uint32_t* delta_lo, bool& dn, bool* ds, bool& near) {
+    uint32_t fE;
+    dn = chip_carry(f, T_lo, fE);
+    near = chip_near_sample(f) || chip_near_sample(fE);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        ds[t] = false;
+        if (t == NT / 2 || KI != 0) continue;
+        uint32_t fT;
+        ds[t] = chip_carry(f, delta_lo[t], fT);
+        near = near || chip_near_sample(fT);
+    }
+}
+
 // One lane's block, prepared one round ahead of its use (its loads are in flight while the previous block computes).
 template <int NT>
 struct ChipBlock {
@@ -241,6 +285,11 @@ struct ChipBlock {
     int S;             // first sample of the block (epoch-relative)
     int dn;            // block length - M            (0 or 1)
     int ds[NT];        // per tap: switch position - m_t (0 or 1; anchor: unused)
+    // (straight-line forms: dn / ds are the carries of the block's fraction f, taken where they are used; the integers above
+    // are set only in a block that went through the exact re-evaluation -- slow != 0 -- which then speaks for the carries)
+    uint32_t f;
+    int slow;
+    int adj;           // (slow != 0) S - the walk's S: where the exact re-evaluation moved the block's start
 };
 
 // Returns false when a lane met a configuration the uniform-position scheme does not cover: the caller redoes the
@@ -307,6 +356,10 @@ __device__ __forceinline__ bool correlate_epoch_chip(const void* __restrict__ ri
     // k = 1 .. KS + 1 are needed and they fit in scalar registers -- no LDS reads in the sample loop at all)
     static_assert(!(KS != 0 && KI != 0), "either the taps switch inside the block (KS) or with it (KI)");
     constexpr bool kStatic = KM != 0 && (KS != 0 || KI != 0);
+    // ... of which the forms short of scalar registers -- taps switching inside the block, or five taps -- walk their blocks by
+    // the fraction (ChipWalk); the three-tap whole-chip forms have registers of both kinds to spare for a fourth wave per SIMD,
+    // which the walk's vector registers would cost them, and keep the 64-bit line
+    constexpr bool kWalk = kStatic && (KS != 0 || NT > 3);
     constexpr int kHalf = chip_half(KM, KS, KI);
     double urc[kStatic ? kHalf + 1 : 1], urs[kStatic ? kHalf + 1 : 1];
     double biasc[3] = {0.0, 0.0, 0.0}, biass[3] = {0.0, 0.0, 0.0};   // (biased conversion) the offset's share of a sum of kHalf - 2 / - 1 / - 0 samples
@@ -329,7 +382,13 @@ __device__ __forceinline__ bool correlate_epoch_chip(const void* __restrict__ ri
             rd0c = R->rd0c, rd0s = R->rd0s, rd1c = R->rd1c, rd1s = R->rd1s;
             if constexpr (SDR_BIASED_CVT) {
 #pragma unroll
-                for (int i = 0; i < 3; ++i) biasc[i] = R->biasc[i], biass[i] = R->biass[i];
+                for (int i = 0; i < 3; ++i) {
+                    biasc[i] = R->biasc[i], biass[i] = R->biass[i];
+                    // (they feed v_add_f64 alone, which takes them from vector registers as well: twelve scalar registers less
+                    // beside the 48 - 52 of the in-block rotations of the long blocks' forms that are short of them; the forms
+                    // that are not keep their vector registers, some of them for a fourth wave per SIMD)
+                    if constexpr (kWalk && (kHalf >= 12 || NT > 3)) asm volatile("" : "+v"(biasc[i]), "+v"(biass[i]));
+                }
             }
         } else {
             if (wlane < kChipMax) {
@@ -460,8 +519,110 @@ __device__ __forceinline__ bool correlate_epoch_chip(const void* __restrict__ ri
             b.raw[12] = w3;
         };
 
+        // ---- straight-line forms: the same block from the walk (ChipWalk): flags from carries, no integers on the fast path.
+        // clampc: the round may be the epoch's last one, where a lane beyond the last whole chip re-does that chip.
+        const uint32_t T_lo = (uint32_t)Tfx, stride_lo = (uint32_t)stride_fx;
+        uint32_t delta_lo[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) delta_lo[t] = (uint32_t)delta[t];
+        // (what the rare paths find wrong, as a vector register: a lane mask would be merged behind every uniform branch)
+        int bad_v = 0;
+        int Dmin_v = Dmin;                              // (the step's add-with-carry takes its carry from a scalar pair already)
+        if constexpr (kWalk) asm volatile("" : "+v"(bad_v), "+v"(Dmin_v));
+        auto prepare_walk = [&](auto clampc, int round, const ChipWalk& w_in, ChipBlock<NT>& b) {
+            constexpr bool kClamp = decltype(clampc)::value;
+            const int idx = round * stride + lane;
+            bool inside = true;
+            ChipWalk w = w_in;
+            if constexpr (kClamp) {
+                inside = idx <= last_idx;
+                w = chip_walk_clamp(w_in, inside, chip_walk_at((uint64_t)(Ufx + (int64_t)(q0 + last_idx) * Tfx + (int64_t)two32)));
+            }
+            bool dn, ds[NT], near;
+            chip_walk_flags<NT, KI>(w.f, T_lo, delta_lo, dn, ds, near);
+            // (KS, three taps: one select serves E and L, and a block where they switch on different samples flags the epoch.
+            // Their carries are two masks and the difference a scalar instruction: such a block takes the exact path, which
+            // finds the same and says so)
+            if constexpr (KS != 0 && NT == 3) near = near || ds[0] != ds[2];
+            b.f = w.f;
+            b.slow = 0;
+            uint32_t off;                               // of the block's first sample in the epoch, bytes
+            if (__builtin_expect(__any(near), 0)) {
+                // (the run-time-position forms' exact path, entered with the same predictions: E = hi(u + T), split = hi(u + delta) - S)
+                int S = w.S;
+                int E = S + M + (dn ? 1 : 0);
+                int split[NT];
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+                    split[t] = 0;
+                    if (t == A) continue;
+                    if constexpr (KI != 0)
+                        split[t] = J[t] == (t - A) * KI ? E - S : 0;
+                    else
+                        split[t] = m[t] + (ds[t] ? 1 : 0);
+                }
+                bool wrong = false;
+                const int q = q0 + 1 + (inside ? idx : last_idx);
+                S = chip_first_above_exact(S, (double)(q - 1), step[A], shift[A]);
+                E = chip_first_above_exact(E, (double)q, step[A], shift[A]);
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+                    if (t == A) continue;
+                    const int p0 = q + J[t];
+                    const int bt = chip_first_above_exact(S + split[t], (double)p0, step[t], shift[t]);
+                    double y = (double)S * step[t];
+                    y = y + shift[t];
+                    const int at_s = (int)ceil(y);
+                    wrong = wrong || (at_s != p0 && at_s != p0 + 1) || (at_s == p0 + 1 && bt > S);
+                    split[t] = bt < S ? 0 : bt - S;
+                }
+                const int nn = E - S;
+                b.dn = nn - M;
+                wrong = wrong || (unsigned)b.dn > 1u;
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+                    b.ds[t] = 0;
+                    if (t == A) continue;
+                    const int sp = split[t] > nn ? nn : split[t];
+                    if constexpr (KI != 0) {
+                        wrong = wrong || !(J[t] == (t - A) * KI ? sp == nn : sp == 0);
+                        continue;
+                    }
+                    b.ds[t] = sp - m[t];
+                    wrong = wrong || (unsigned)b.ds[t] > 1u;
+                }
+                if constexpr (KS != 0 && NT == 3) wrong = wrong || b.ds[0] != b.ds[2];
+                bad_v |= wrong ? 1 : 0;
+                b.adj = S - w.S;
+                b.slow = 1;
+                off = (uint32_t)S << 1;
+            } else {
+                off = (uint32_t)w.S << 1;               // (the shift is the copy: S itself stays with the walk)
+            }
+            // (opaque: knowing it zero on one side, the compiler lays out a second copy of everything that asks for it)
+            asm volatile("" : "+s"(b.slow));
+            // 13 dwords = 26 samples from the (2-byte aligned) address of sample S: gfx950 serves unaligned dword loads.  A
+            // 32-bit offset on the epoch's scalar base address: S >= 0, and an epoch is far shorter than 2^31 bytes.
+            const char* src = ring_base + off;
+            const uint4 w0 = *reinterpret_cast<const uint4*>(src);
+            const uint4 w1 = *reinterpret_cast<const uint4*>(src + 16);
+            const uint4 w2 = *reinterpret_cast<const uint4*>(src + 32);
+            const uint32_t w3 = *reinterpret_cast<const uint32_t*>(src + 48);
+            b.raw[0] = w0.x, b.raw[1] = w0.y, b.raw[2] = w0.z, b.raw[3] = w0.w;
+            b.raw[4] = w1.x, b.raw[5] = w1.y, b.raw[6] = w1.z, b.raw[7] = w1.w;
+            b.raw[8] = w2.x, b.raw[9] = w2.y, b.raw[10] = w2.z, b.raw[11] = w2.w;
+            b.raw[12] = w3;
+        };
+
         ChipBlock<NT> blk_a, blk_b;
-        prepare(0, u_cur, blk_a);
+        ChipWalk walk = chip_walk_at(u_cur);
+        if constexpr (kWalk) {
+            prepare_walk(std::true_type{}, 0, walk, blk_a);
+            const ChipWalk w0 = chip_walk_clamp(walk, lane <= last_idx, chip_walk_at((uint64_t)(Ufx + (int64_t)(q0 + last_idx) * Tfx + (int64_t)two32)));
+            blk_a.S = w0.S + (blk_a.slow ? blk_a.adj : 0);
+        } else {
+            prepare(0, u_cur, blk_a);
+        }
         // carrier phase at the lane's first block: one exact evaluation; later blocks by a fixed rotation
         double sb, cb;
         sincos_reduced(__builtin_fma(-(double)blk_a.S, dphi_u, rem_carrier_u), &sb, &cb);
@@ -478,8 +639,18 @@ __device__ __forceinline__ bool correlate_epoch_chip(const void* __restrict__ ri
 
         sdr_u32x2 zI = {0u, 0u}, zQ = {0u, 0u};     // (biased conversion) the two register pairs the samples are built in
         asm volatile("" : "+v"(zI), "+v"(zQ));
+        // (straight-line forms: a second set, for the odd samples.  v_perm_b32 rewrites the high word of a pair the v_fmac_f64
+        // just in front of it has read, and the hazard recognizer puts an s_nop between the two -- one per sample; with the
+        // pairs alternating, the pair that is rewritten was last read two samples ago and the pads are gone)
+        sdr_u32x2 zI2 = {0u, 0u}, zQ2 = {0u, 0u};
+        if constexpr (kWalk) asm volatile("" : "+v"(zI2), "+v"(zQ2));
 
-        auto process = [&](const ChipBlock<NT>& b, int round, double sbk, double cbk) {
+        // (straight-line forms: the biased conversion's high-word constant, a vector register for the whole epoch -- v_perm_b32
+        // takes one scalar operand, the selector; made opaque per block it was a move per block)
+        uint32_t hi_epoch = 0x40B00000u;
+        if constexpr (kWalk && SDR_BIASED_CVT) asm volatile("" : "+v"(hi_epoch));
+        auto process = [&](const ChipBlock<NT>& b, int round, double sbk, double cbk, auto clampc) {
+            constexpr bool kClamp = decltype(clampc)::value;   // (straight-line forms) the round may be the epoch's last one
             double pr = 0.0, pi = 0.0;
             double2* wp = strip;
             // the event positions as ONE scalar register, re-read per block: left to itself the compiler hoists the 27
@@ -534,9 +705,9 @@ __device__ __forceinline__ bool correlate_epoch_chip(const void* __restrict__ ri
                 static_assert(!SDR_BIASED_CVT || (2 * kHalf - KM >= 1 && 2 * kHalf - KM <= 2 && (KS == 0 || KS == kHalf - 1)),
                               "the offset's shares are kept for sums of KM - kHalf, + 1 and + 2 samples: kHalf must be one of the last two");
                 uint32_t flipped[kChipRawDwords];
-                uint32_t hi_const = 0x40B00000u;
+                uint32_t hi_const = hi_epoch;
                 if constexpr (SDR_BIASED_CVT) {
-                    asm volatile("" : "+v"(hi_const));             // (v_perm_b32 takes one scalar operand: the selector)
+                    if constexpr (!kWalk) asm volatile("" : "+v"(hi_const));   // (v_perm_b32 takes one scalar operand: the selector)
 #pragma unroll
                     for (int i = 0; i < kChipRawDwords; ++i) flipped[i] = b.raw[i];   // (the ring holds the flipped bytes)
                 }
@@ -546,8 +717,8 @@ __device__ __forceinline__ bool correlate_epoch_chip(const void* __restrict__ ri
                     const int w = ci8_native((int)b.raw[k >> 1]);
                     double ar, ai;
                     if constexpr (SDR_BIASED_CVT) {
-                        ar = biased_sample(zI, flipped[k >> 1], cvt_selector((k & 1) ? 2 : 0), hi_const);
-                        ai = biased_sample(zQ, flipped[k >> 1], cvt_selector((k & 1) ? 3 : 1), hi_const);
+                        ar = biased_sample(kWalk && SDR_ALT_PAIRS && (k & 1) ? zI2 : zI, flipped[k >> 1], cvt_selector((k & 1) ? 2 : 0), hi_const);
+                        ai = biased_sample(kWalk && SDR_ALT_PAIRS && (k & 1) ? zQ2 : zQ, flipped[k >> 1], cvt_selector((k & 1) ? 3 : 1), hi_const);
                     } else {
                         ar = (k & 1) ? (double)(int)(int8_t)(w >> 16) : (double)(int)(int8_t)w;
                         ai = (k & 1) ? (double)(w >> 24) : (double)(int)(int8_t)(w >> 8);
@@ -564,7 +735,10 @@ __device__ __forceinline__ bool correlate_epoch_chip(const void* __restrict__ ri
                     // (an opaque point per sample: the sums must have read the pairs before their high words are written
                     // again, and the next sample must be built on THESE registers -- seen through, every sample would be
                     // rebuilt from the original pair, i.e. from a copy of its low word)
-                    if constexpr (SDR_BIASED_CVT) asm volatile("" : "+v"(pr), "+v"(pi), "+v"(zI), "+v"(zQ));
+                    if constexpr (SDR_BIASED_CVT) {
+                        if constexpr (kWalk && SDR_ALT_PAIRS && (k & 1)) asm volatile("" : "+v"(pr), "+v"(pi), "+v"(zI2), "+v"(zQ2));
+                        else asm volatile("" : "+v"(pr), "+v"(pi), "+v"(zI), "+v"(zQ));
+                    }
                 });
             } else if constexpr (KM != 0) {
                 // positions KM and KM + 1 are always events; the others (the taps' m_t, m_t + 1 < KM) are looked for
@@ -612,8 +786,28 @@ __device__ __forceinline__ bool correlate_epoch_chip(const void* __restrict__ ri
                 capr[2] -= biasc[iFirst], capi[2] -= biass[iFirst];      // first half: kHalf samples
                 if constexpr (KS != 0) capr[0] -= biasc[iFirst - 1], capi[0] -= biass[iFirst - 1];   // P_KS: kHalf - 1 samples
             }
+            // (straight-line forms) the block's flags, from its fraction and HERE: a flag made when the block was prepared is a
+            // lane mask in a scalar register pair for the length of a block, two blocks in flight, beside the 52 scalar
+            // registers of the rotations -- which then spill through v_readlane.  One add per flag, in the place of the compare.
+            bool dnf = false, dsf[NT];
+#pragma unroll
+            for (int t = 0; t < NT; ++t) dsf[t] = false;
+            if constexpr (kWalk) {
+                if (__builtin_expect(b.slow != 0, 0)) {
+                    dnf = b.dn != 0;
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) dsf[t] = b.ds[t] != 0;
+                    asm volatile("" : "+v"(pr), "+v"(pi));   // (stays a branch: as selects, both sides would be paid in every block)
+                } else {
+                    uint32_t f = b.f;
+                    asm volatile("" : "+v"(f), "+v"(pr), "+v"(pi));   // (... and behind the block's last sample)
+                    bool nr;
+                    chip_walk_flags<NT, KI>(f, T_lo, delta_lo, dnf, dsf, nr);
+                }
+            }
             if constexpr (kStatic) {
-                const double qr = b.dn ? pr : capr[1], qi = b.dn ? pi : capi[1];   // second half up to M or M + 1 samples
+                if constexpr (!kWalk) dnf = b.dn != 0;
+                const double qr = dnf ? pr : capr[1], qi = dnf ? pi : capi[1];   // second half up to M or M + 1 samples
                 ptot.x = __builtin_fma(-qi, urs[kHalf], __builtin_fma(qr, urc[kHalf], capr[2]));
                 ptot.y = __builtin_fma(qi, urc[kHalf], __builtin_fma(qr, urs[kHalf], capi[2]));
             } else {
@@ -626,7 +820,7 @@ __device__ __forceinline__ bool correlate_epoch_chip(const void* __restrict__ ri
             const int first = round * stride;           // (a lane beyond the last whole chip re-does the last one)
             const uint32_t* lq;                         // replica entry of the block's anchor chip
             if constexpr (kStatic)                      // (... against three zero words: it adds nothing, whatever its phasor)
-                lq = first + lane <= last_idx ? lut + q_lane + first : zero_lq;
+                lq = !kClamp || first + lane <= last_idx ? lut + q_lane + first : zero_lq;
             else
                 lq = lut + q_lane + (first + lane <= last_idx ? first : last_idx - lane);
             if constexpr (KI != 0) {
@@ -651,7 +845,7 @@ __device__ __forceinline__ bool correlate_epoch_chip(const void* __restrict__ ri
                 } else {
                     double2 ps;
                     if constexpr (kStatic)
-                        ps = b.ds[NT == 3 ? 0 : t] ? make_double2(capr[2], capi[2]) : make_double2(capr[0], capi[0]);
+                        ps = (kWalk ? dsf[NT == 3 ? 0 : t] : b.ds[NT == 3 ? 0 : t] != 0) ? make_double2(capr[2], capi[2]) : make_double2(capr[0], capi[0]);
                     else {
                         ps = strip[rank[t] + b.ds[t]];
                         if constexpr (SDR_BIASED_CVT) {
@@ -688,21 +882,76 @@ __device__ __forceinline__ bool correlate_epoch_chip(const void* __restrict__ ri
             }
         };
 
-        for (int it = 0; it < rounds / 2; ++it) {
-            const double sb0 = sb, cb0 = cb;
-            u_cur += (uint64_t)stride_fx;
-            prepare(2 * it + 1, u_cur, blk_b);
-            advance(blk_a, blk_b, 2 * it + 1);
-            if (wave_has_work(2 * it)) process(blk_a, 2 * it, sb0, cb0);
-            const double sb1 = sb, cb1 = cb;
-            if (2 * it + 2 < rounds) {
+        static_assert(SINGLE_WAVE || !kWalk, "the straight-line forms give a wave an epoch of its own");
+        if constexpr (kWalk) {
+            // The lane's next block and the rotation to it: dd is the carry of the walk's step.  A block that went through the
+            // exact re-evaluation may start a sample off the line: next to one, dd comes from the integers as before.
+            auto next_block = [&](auto clampc, const ChipBlock<NT>& from, ChipBlock<NT>& to, int to_round) {
+                constexpr bool kClamp = decltype(clampc)::value;
+                bool dd = chip_walk_step(walk, stride_lo, Dmin_v);
+                prepare_walk(clampc, to_round, walk, to);
+                if (__builtin_expect((from.slow | to.slow) != 0, 0)) {
+                    bool alive = true;
+                    int d = dd ? 1 : 0;                 // to.S - from.S - Dmin
+                    if constexpr (kClamp) {
+                        // (a lane beyond the last whole chip: its block is the last chip's, wherever the walk went)
+                        alive = to_round * stride + lane <= last_idx;
+                        const int S_last = (int)((uint64_t)(Ufx + (int64_t)(q0 + last_idx) * Tfx + (int64_t)two32) >> 32);
+                        d = alive ? d : S_last - (walk.S - d - Dmin_v) - Dmin_v;
+                    }
+                    if (to.slow) d += to.adj;
+                    if (from.slow) d -= from.adj;
+                    bad_v |= alive && (unsigned)d > 1u ? 1 : 0;
+                    dd = d != 0;
+                    asm volatile("");
+                }
+                const double rc_ = dd ? rd1c : rd0c, rs_ = dd ? rd1s : rd0s;
+                const double cbn = __builtin_fma(cb, rc_, -sb * rs_);
+                const double sbn = __builtin_fma(sb, rc_, cb * rs_);
+                cb = cbn, sb = sbn;                     // (a lane without a block correlates against zero replica words)
+                // (... done before the samples of the block at hand: floating down, the selects keep dd's mask for a block)
+                asm volatile("" : "+v"(cb), "+v"(sb));
+            };
+            // (a block's taps are combined before the next block's samples begin: left to float behind them, the
+            // combination holds the block's flags and four sums for the length of a block)
+            auto settle = [&]() {
+#pragma unroll
+                for (int t = 0; t < NT; ++t) asm volatile("" : "+v"(accr[t]), "+v"(acci[t]));
+            };
+            auto round_pair = [&](auto clampc, int it) {
+                const double sb0 = sb, cb0 = cb;
+                next_block(clampc, blk_a, blk_b, 2 * it + 1);
+                process(blk_a, 2 * it, sb0, cb0, clampc);
+                settle();
+                const double sb1 = sb, cb1 = cb;
+                if (!decltype(clampc)::value || 2 * it + 2 < rounds) next_block(clampc, blk_b, blk_a, 2 * it + 2);
+                process(blk_b, 2 * it + 1, sb1, cb1, clampc);
+                settle();
+            };
+            // Rounds 0 .. rounds - 2 hold a block for every lane (r * stride + lane <= last_idx by construction): the pairs
+            // that neither work on nor prepare the last round run without the clamp, `alive` and the zero replica words.
+            const int plain = rounds >= 2 ? (rounds - 2) / 2 : 0;
+            for (int it = 0; it < plain; ++it) round_pair(std::false_type{}, it);
+            for (int it = plain; it < rounds / 2; ++it) round_pair(std::true_type{}, it);
+            if (rounds & 1) process(blk_a, rounds - 1, sb, cb, std::true_type{});
+        } else {
+            for (int it = 0; it < rounds / 2; ++it) {
+                const double sb0 = sb, cb0 = cb;
                 u_cur += (uint64_t)stride_fx;
-                prepare(2 * it + 2, u_cur, blk_a);
-                advance(blk_b, blk_a, 2 * it + 2);
+                prepare(2 * it + 1, u_cur, blk_b);
+                advance(blk_a, blk_b, 2 * it + 1);
+                if (wave_has_work(2 * it)) process(blk_a, 2 * it, sb0, cb0, std::true_type{});
+                const double sb1 = sb, cb1 = cb;
+                if (2 * it + 2 < rounds) {
+                    u_cur += (uint64_t)stride_fx;
+                    prepare(2 * it + 2, u_cur, blk_a);
+                    advance(blk_b, blk_a, 2 * it + 2);
+                }
+                if (wave_has_work(2 * it + 1)) process(blk_b, 2 * it + 1, sb1, cb1, std::true_type{});
             }
-            if (wave_has_work(2 * it + 1)) process(blk_b, 2 * it + 1, sb1, cb1);
+            if ((rounds & 1) && wave_has_work(rounds - 1)) process(blk_a, rounds - 1, sb, cb, std::true_type{});
         }
-        if ((rounds & 1) && wave_has_work(rounds - 1)) process(blk_a, rounds - 1, sb, cb);
+        bad = bad || bad_v != 0;
     }
 
     if (__any(bad)) return false;
