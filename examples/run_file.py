@@ -2,7 +2,7 @@
 """Track an IQ recording with the reference's own configuration files.
 
     python examples/run_file.py receiver.ini [--ms 2000] [--block 80 | --read-ahead 50] [--csv out.csv]
-                                              [--profile N_TAPS]
+                                              [--profile N_TAPS] [--probe]
 
 `receiver.ini` is the reference's receiver configuration (config/receiver.ini: [DEFAULT] nb_channels /
 ms_to_process, [RFSIGNAL], [SATELLITES] include_prn, [CHANNELS] gps_l1ca = <channel ini>).  What the reference's
@@ -12,7 +12,10 @@ tracks, blocks of `--block` ms go through the closed-loop kernel (`ChannelManage
 the loop stays the reference's own (one millisecond per iteration: `addNewRFData(getMilliseconds(1)); run()`) and the
 manager tracks N ms ahead behind it (`enableReadAhead`).  Subframes the channels decode are printed as they complete
 (DECODING_UPDATE; needs a decoder: by default the reference's own, where `sydr` is importable).  Navigation,
-measurements, database and report stay the reference's business (feed them the packets this script prints / writes)."""
+measurements, database and report stay the reference's business (feed them the packets this script prints / writes).
+`--probe` looks at the front end first: the first second of the recording goes into a ring of its own length and
+`Engine.iq_probe` says what it holds -- levels, rails, DC offset, I/Q imbalance, the histogram's occupied bins, the noise
+floor and the bins that stand out of the spectrum -- before any channel is started."""
 import argparse
 import configparser
 import os
@@ -29,6 +32,33 @@ from sydr_amd.signal.iqsource import RFSignal                      # noqa: E402
 from sydr_amd.utils.enumerations import ChannelMessage, ChannelState  # noqa: E402
 
 
+def print_probe(rf):
+    """The first second of the recording (or all of it, when it is shorter), probed on the device."""
+    from sydr_amd.engine import FMT_CI16, FMT_CI8
+    from sydr_amd.runtime import get_engine
+    engine = get_engine()
+    n = min(rf.totalSamples, int(rf.samplingFrequency)) // 8 * 8
+    fmt = FMT_CI16 if rf.fileDataType is np.int16 else FMT_CI8
+    engine.iq_alloc(n, fmt)
+    if rf.packing is not None:
+        engine.iq_upload_packed(rf.samples(0, n), n, rf.packing, 0)
+    else:
+        engine.iq_upload(rf.samples(0, n), 0)
+    nfft = 1024 if n >= 1024 else 0
+    r = engine.iq_probe(0, n, nfft=nfft, fs=rf.samplingFrequency if nfft else None)
+    print(f"probe of the first {n} samples ({n / rf.samplingFrequency * 1e3:.0f} ms):")
+    for c, name in enumerate("IQ"):
+        used = np.flatnonzero(r.hist[c])
+        print(f"  {name}: min {r.min[c]:.0f} max {r.max[c]:.0f} mean {r.mean[c]:+.3f} rms {r.rms[c]:.3f} (DC / rms {r.dc_offset[c]:+.4f}), "
+              f"on the rails {100.0 * r.rail_fraction[c]:.3f} %, {used.size} histogram bins in use ({used[0] - 128} .. {used[-1] - 128})")
+    print(f"  I/Q gain imbalance {r.iq_imbalance_db:+.3f} dB, I/Q correlation {r.iq_correlation:+.4f}")
+    if nfft:
+        db = r.psd_db
+        print(f"  spectrum ({r.n_segments} segments of {nfft}): median {np.median(db):.2f} dB/Hz, peak {db.max():.2f} dB/Hz")
+        for f, over in r.spurs(10.0)[:8]:
+            print(f"    {f / 1e3:+10.1f} kHz stands {over:.1f} dB above the median bin")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("receiver_ini")
@@ -38,6 +68,7 @@ def main(argv=None):
     ap.add_argument("--csv", default=None, help="write one line per tracking epoch")
     ap.add_argument("--profile", type=int, default=0, metavar="N_TAPS",
                     help="print |correlation function| of every channel's last epoch at the end: N_TAPS taps across +-2 chips")
+    ap.add_argument("--probe", action="store_true", help="print what the first second of the recording holds (Engine.iq_probe) before tracking")
     args = ap.parse_args(argv)
 
     rcfg = configparser.ConfigParser()
@@ -52,6 +83,8 @@ def main(argv=None):
     prns = [int(p) for p in rcfg["SATELLITES"]["include_prn"].split(",") if p.strip()]
     ms_total = args.ms or int(rcfg["DEFAULT"]["ms_to_process"])
 
+    if args.probe:
+        print_probe(rf)
     mgr = ChannelManager(rf, keepCorrelationMap=False)
     mgr.addChannel(plugin, ccfg, max(len(prns), int(rcfg["DEFAULT"].get("nb_channels", len(prns)))))
     for p in prns:

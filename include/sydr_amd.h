@@ -39,7 +39,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define SDR_ABI_VERSION 5   /* 5 (still): + sdr_corr_profile, option "corr_profile_per_sample" (additive); 5 (still): + sdr_iq_packing, sdr_iq_packed_bytes, sdr_iq_upload_packed / _begin / _queue (additive); 5 (still): + sdr_acq_refine, sdr_acq_refine_bins (additive); 5: + sdr_bank_tick_mirrored_begin / _end, sdr_iq_upload_queue, sdr_host_alloc / _free, options "tick_server" + sdr_tick_server_stats, "bind_thread_to_device" (additive); 4: + sdr_build_id, sdr_epl_plan_create_dev, sdr_bank_tick_mirrored, sdr_iq_upload_begin, sdr_block_schedule, sdr_bank_step_begin / _end (additive) */
+#define SDR_ABI_VERSION 5   /* 5 (still): + sdr_iq_probe (additive); 5 (still): + sdr_corr_profile, option "corr_profile_per_sample" (additive); 5 (still): + sdr_iq_packing, sdr_iq_packed_bytes, sdr_iq_upload_packed / _begin / _queue (additive); 5 (still): + sdr_acq_refine, sdr_acq_refine_bins (additive); 5: + sdr_bank_tick_mirrored_begin / _end, sdr_iq_upload_queue, sdr_host_alloc / _free, options "tick_server" + sdr_tick_server_stats, "bind_thread_to_device" (additive); 4: + sdr_build_id, sdr_epl_plan_create_dev, sdr_bank_tick_mirrored, sdr_iq_upload_begin, sdr_block_schedule, sdr_bank_step_begin / _end (additive) */
 
 typedef struct sdr_engine sdr_engine;
 
@@ -587,6 +587,48 @@ int64_t sdr_iq_packed_bytes(const sdr_iq_packing* pk, int64_t n_samples);
 int sdr_iq_upload_packed(sdr_engine* e, const sdr_iq_packing* pk, const void* packed, int64_t n_samples, int64_t ring_offset);
 int sdr_iq_upload_packed_begin(sdr_engine* e, const sdr_iq_packing* pk, const void* packed, int64_t n_samples, int64_t ring_offset);
 int sdr_iq_upload_packed_queue(sdr_engine* e, const sdr_iq_packing* pk, const void* packed, int64_t n_samples, int64_t ring_offset);
+
+/* ------------------------------------------------- what the ring holds: levels, histogram, spectrum
+ * The first look at a new recording and the look a running receiver keeps taking at its front end -- are the bits used, is
+ * anything on the rails, is there a DC offset or an I/Q imbalance, is the level table of a packed file the right one, is there
+ * a carrier-wave interferer in the band, where does the noise floor sit -- taken where the samples lie: one pass over the
+ * window on the device, a few kilobytes back (the reference only had an off-line Welch plot, sydr/old/dsplib.py:100-110).
+ * The window is ring samples start_sample .. start_sample + n_samples - 1: any start_sample >= 0, taken modulo the capacity;
+ * the window may cross the ring's end; 1 <= n_samples <= min(capacity, 2^31).  Synchronous on the engine's stream, behind every
+ * ring write queued before it (sdr_iq_upload_begin / _queue, the packed uploads and their unpack kernels, a parked slab).  The
+ * call reads the ring and writes nothing into it; two identical calls return identical bits.  A probe is a call of its own,
+ * not a part of the tick's launch: like every non-tick call it tells a resident tick server to leave first.
+ * Moments, integer rings (ci8, ci16): every sum is the exact integer, accumulated in 64-bit integers and converted to double
+ * once at the end (round to nearest even); min / max exact; n_rail counts the components equal to -128 / 127 (ci8) or
+ * -32768 / 32767 (ci16).  A ci8 ring stores its bytes sign-flipped; the call reports the samples' values.
+ * Moments, float rings (cf32, cf64): a sample with a NaN / Inf component is counted in n_nonfinite and left out of everything
+ * else; the sums are fp64, added in a fixed order; min / max exact (NaN when no finite sample is left); n_rail = 0.
+ * Histogram (hist != NULL, integer rings only): hist[c][b] counts the components c (0 = I, 1 = Q) whose bin is
+ *   b = min(255, max(0, (value >> hist_shift) + 128))    (arithmetic shift; hist_shift 0 for ci8, 0..8 for ci16).
+ * Power spectral density (psd != NULL): Welch's method, segments of nfft samples (a power of two in 64..4096), hop nfft / 2:
+ *   S = (n_samples - nfft) / (nfft / 2) + 1 segments (integer division; what lies behind the last whole one is not used),
+ *   the periodic Hann window w[j] = 0.5 - 0.5*cos(2*pi*j/nfft), no detrending (a DC offset is something to see), fp64:
+ *   psd[k] = ( sum_s |FFT(w * x_s)[k]|^2 ) / (S * fs * sum_j w[j]^2),   k = 0..nfft-1 in FFT order
+ *   (bin k stands for k*fs/nfft below nfft/2 and for (k-nfft)*fs/nfft from there on) -- scipy.signal.welch(x, fs, 'hann',
+ *   nfft, nfft//2, detrend=False, return_onesided=False, scaling='density').  A non-finite sample in a used segment makes
+ *   every psd[k] NaN (reported, not guessed); the moments are still reported.
+ * SDR_ERR_INVALID: NULL e or res, n_samples < 1, a negative hist_shift or one too large for the ring, and with psd != NULL an
+ * nfft that is no power of two in 64..4096, fs <= 0 or non-finite, n_samples < nfft; SDR_ERR_UNSUPPORTED: hist != NULL on a
+ * float ring, n_samples > 2^31 (whatever the ring holds); SDR_ERR_RANGE: a negative start_sample, a window longer than the
+ * ring; SDR_ERR_STATE: no ring.  A refused call leaves res, hist and psd untouched.
+ * sdr_prof_enable scopes: "probe_moments_kernel", "probe_psd_kernel" (with its row reduction), "call_iq_probe". */
+typedef struct sdr_probe_result {
+    int64_t n_samples;      /* samples of the window                                                        */
+    int64_t n_segments;     /* Welch segments averaged (0 when psd == NULL)                                 */
+    int64_t n_nonfinite;    /* float rings: samples with a NaN / Inf component; they enter no sum, min, max  */
+    int64_t n_rail[2];      /* integer rings: I / Q components equal to the type's minimum or maximum        */
+    double  min[2], max[2]; /* I, Q                                                                          */
+    double  sum[2];         /* sum I, sum Q                                                                  */
+    double  sum_sq[2];      /* sum I*I, sum Q*Q                                                              */
+    double  sum_iq;         /* sum I*Q                                                                       */
+} sdr_probe_result;
+int sdr_iq_probe(sdr_engine* e, int64_t start_sample, int64_t n_samples, int hist_shift, int nfft, double fs,
+                 sdr_probe_result* res, int64_t* hist /* nullable [2][256] */, double* psd /* nullable [nfft] */);
 
 /* Host-only helper of a receiver that tracks ahead (no device work): `records[n_ch][n_cols]` hold `done[r]` epochs per channel
  * computed in one sdr_bank_step while the host still feeds its per-millisecond loop (receiver.py:120-131); this works out

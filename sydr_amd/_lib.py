@@ -62,6 +62,13 @@ class IqPacking(C.Structure):
 PACK_MSB_FIRST = 1
 
 
+class ProbeResultC(C.Structure):
+    """sdr_probe_result (include/sydr_amd.h): what sdr_iq_probe reports of a window of the ring."""
+    _fields_ = [("n_samples", C.c_int64), ("n_segments", C.c_int64), ("n_nonfinite", C.c_int64), ("n_rail", C.c_int64 * 2),
+                ("min", C.c_double * 2), ("max", C.c_double * 2), ("sum", C.c_double * 2), ("sum_sq", C.c_double * 2),
+                ("sum_iq", C.c_double)]
+
+
 class SynthSat(C.Structure):
     _fields_ = [("prn", C.c_int32), ("flags", C.c_int32), ("doppler_hz", C.c_double),
                 ("code_phase", C.c_double), ("carrier_phase", C.c_double), ("amplitude", C.c_double)]
@@ -184,6 +191,7 @@ _PROTOTYPES = {
     "sdr_acq_refine_bins": (C.c_int, [C.c_double, C.c_double]),
     "sdr_acq_refine": (C.c_int, [_VP, _VP, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double, _VP, _VP, _VP]),
     "sdr_corr_profile": (C.c_int, [_VP, _VP, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, _VP]),
+    "sdr_iq_probe": (C.c_int, [_VP, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_double, C.POINTER(ProbeResultC), _VP, _VP]),
     "sdr_track_cluster": (C.c_int, [_VP, C.c_int]),
     "sdr_track_closed_loop": (C.c_int, [_VP, C.c_int, _VP, C.POINTER(LoopCfg), C.c_int, _VP]),
     "sdr_track_closed_loop_bits": (C.c_int, [_VP, C.c_int, _VP, C.POINTER(LoopCfg), C.c_int, _VP, _VP, C.c_int, _VP]),

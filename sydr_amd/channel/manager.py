@@ -420,6 +420,16 @@ class ChannelManager:
         self._pending = False         # (the call waited for the engine's stream: a queued slab is in the ring)
         return {cid: out[k] for k, cid in enumerate(cids)}
 
+    def probeRFData(self, nbMilliseconds: int, nfft: int = 1024):
+        """What the newest `nbMilliseconds` of the ring hold (CircularBuffer.probe -> signal.probe.ProbeResult): levels, rails,
+        histogram, and the Welch spectrum at the recording's sampling frequency (nfft = 0: none) -- the front end looked at
+        where its samples lie, one library call, nothing written.  A slab that is only queued is in the ring before the probe
+        reads it; the channels are not touched."""
+        n = int(round(self._samples_per_ms * nbMilliseconds))
+        out = self.sharedBuffer.probe(n, nfft=nfft, fs=self.rfSignal.samplingFrequency if nfft else None)
+        self._pending = False         # (the call waited for the engine's stream: a queued slab is in the ring)
+        return out
+
     def close(self):
         self._flush_pending()
         if self._ahead is not None and self._ahead["bank"] is self.bank:

@@ -124,6 +124,10 @@ class MultiDeviceChannelManager:
                 out.update(part.correlationProfiles(first, step, n_taps))
         return dict(sorted(out.items()))
 
+    def probeRFData(self, nbMilliseconds: int, nfft: int = 1024):
+        """ChannelManager.probeRFData on the first device's ring (every device's ring holds the same stream)."""
+        return self.parts[0].probeRFData(nbMilliseconds, nfft)
+
     def close(self):
         for part in self.parts:
             part.close()

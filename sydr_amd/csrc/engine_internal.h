@@ -174,6 +174,13 @@ struct sdr_engine {
     std::vector<char> corr_host;  // the host image of its item list (the source of the upload)
     size_t corr_lds_allowed[8] = {0};   // dynamic LDS its kernels were last allowed, per (format, form)
     bool corr_per_sample = false; // "corr_profile_per_sample": the per-sample form at any rate (tests, A/B timing)
+
+    // sdr_iq_probe (probe.hip)
+    DevBuf probe_ws;              // [result block][histogram][moment rows][spectrum rows][spectrum]
+    DevBuf probe_tab;             // the transform's twiddles and the Hann window of probe_tab_nfft, sum of its squares
+    int probe_tab_nfft = 0;
+    double probe_sumw2 = 0.0;
+    std::vector<char> probe_host; // the host image of the result block and the histogram (the target of their download)
 };
 
 int sdr_devbuf_reserve(sdr_engine* e, DevBuf* b, size_t bytes);

@@ -399,6 +399,21 @@ class Engine:
         check(self._lib.sdr_iq_download(self._h, ptr(out), int(n_samples), int(ring_offset)))
         return out
 
+    def iq_probe(self, start: int, n_samples: int, nfft: int = 0, fs=None, hist: bool = True, hist_shift: int = 0):
+        """What ring samples start .. start + n_samples - 1 hold (sdr_iq_probe): level statistics, with `hist` a histogram
+        per component (integer rings), with `nfft` (a power of two in 64..4096) and `fs` a Welch spectrum -- one pass over
+        the window on the device, behind every upload queued so far.  -> signal.probe.ProbeResult (the NumPy statement of the
+        same: `signal.probe.probe`)."""
+        from .signal.probe import HIST_BINS, ProbeResult
+        res = _lib.ProbeResultC()
+        nfft = int(nfft)
+        table = np.zeros((2, HIST_BINS), dtype=np.int64) if hist else None
+        psd = np.empty(max(0, min(nfft, 4096)), dtype=np.float64) if nfft else None
+        check(self._lib.sdr_iq_probe(self._h, int(start), int(n_samples), int(hist_shift), nfft, float(fs) if fs is not None else 0.0,
+                                     C.byref(res), ptr(table) if hist else None, ptr(psd) if nfft else None))
+        return ProbeResult(res.n_samples, res.n_segments, res.n_nonfinite, tuple(res.n_rail), tuple(res.min), tuple(res.max),
+                           tuple(res.sum), tuple(res.sum_sq), res.sum_iq, hist=table, psd=psd, fs=float(fs) if nfft else None)
+
     def iq_synth(self, sats, fs, noise_sigma, seed, first_sample, n_samples):
         arr = (SynthSat * max(1, len(sats)))()
         for i, s in enumerate(sats):

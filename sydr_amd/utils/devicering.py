@@ -96,6 +96,17 @@ class CircularBuffer:
         raw = raw.astype(np.float64)
         return (raw[0::2] + 1j * raw[1::2]).reshape(1, -1)
 
+    def probe(self, nbSamples: int, nfft: int = 0, fs=None, hist=None, hist_shift: int = 0):
+        """What the newest `nbSamples` of the ring hold -- the samples that end at idxWrite (Engine.iq_probe: level statistics,
+        histogram, Welch spectrum, computed where the samples lie).  hist: None = where the ring has one (integer formats)."""
+        nbSamples = int(nbSamples)
+        if nbSamples < 1 or nbSamples > self.size:
+            raise ValueError(f"the ring holds {self.size} samples, {nbSamples} asked for")
+        if hist is None:
+            hist = self.fmt in (FMT_CI8, FMT_CI16)
+        return self.engine.iq_probe((self.idxWrite - nbSamples) % self.maxSize, nbSamples, nfft=nfft, fs=fs, hist=hist,
+                                    hist_shift=hist_shift)
+
     def getNbUnreadSamples(self, currentSample: int):
         if currentSample <= self.idxWrite:
             return self.idxWrite - currentSample
