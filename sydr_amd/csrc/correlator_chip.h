@@ -201,6 +201,62 @@ __host__ __device__ inline void chip_rotations(double dphi, int Dmin, ChipRot& r
     }
 }
 
+// ---- Half blocks summed as folded sample pairs.  A half block is summed against rotations that are the same in every
+// lane; taken about the CENTRE of the run of samples that is always summed, the rotations of the samples d before and d
+// after it are complex conjugates, so with a = x(-d), b = x(+d) and (c, s) = (cos, sin)(d * dphi)
+//     a (c + 1j s) + b (c - 1j s) = c (a + b) + 1j s (a - b):      Re += c SI - s DQ,    Im += c SQ + s DI
+// four FMAs for two samples.  S = a + b and D = a - b are sums of bytes: v_perm_b32 gathers G = [aI aQ bI bQ] from the two
+// raw dwords, G2 = G ^ 0xFFFF0000 holds 255 - u for the b half, and v_dot4_u32_u8 with the byte weight 128 on two of the
+// four bytes, added onto the high word 0x40C0_0000 of 8192.0 (one unit of that word is 2^-7), leaves the high words of
+// the exact doubles 8192 + ua + ub = 8448 + (xa + xb) and 8192 + ua + 255 - ub = 8447 + (xa - xb).  Ten instructions per
+// pair, four of them fp64, against twelve and eight.  The run's optional last sample -- the one a lane's select takes or
+// leaves -- stays a single biased sample (4224 + x), and so does the centre sample of a run of odd length, which starts
+// the sum.  Both halves are referred to their own centres: the lane's block phasor is evaluated at the first half's
+// centre instead of the block's first sample, and the second half is turned by the distance of the two centres.
+#ifndef SDR_FOLD_PAIRS
+#define SDR_FOLD_PAIRS 1     // (0: the direct sum of every form, the text of the kernels before folding -- for A/B runs)
+#endif
+constexpr int kFoldPairsMax = kStaticHalf / 2;  // pairs of the longest run
+constexpr double kFoldSumBias = 8192.0 + 256.0, kFoldDiffBias = 8192.0 + 255.0;
+// The runs of a geometry: half h (0: samples from 0, 1: samples from chip_half()) always sums `count` samples from `first`;
+// its optional last sample is first + count (the first half has one only where taps switch inside the block: KS).
+constexpr int chip_fold_first(int half, int h) { return h == 0 ? 0 : half; }
+constexpr int chip_fold_count(int KM, int half, bool ks, int h) { return h == 0 ? (ks ? half - 1 : half) : KM - half; }
+struct ChipFold {
+    double pc[2][kFoldPairsMax], ps[2][kFoldPairsMax];   // (cos, sin)(d * dphi) of pair i of half h, from the outside in: d = (count - 1) / 2 - i
+    double sc[2], ss[2];                                 // the optional last sample's rotation about its half's centre: (cos, sin)(-(count + 1) / 2 * dphi)
+    double tc, ts;                                       // second half onto the first half's centre: (cos, sin)(-(centre1 - centre0) * dphi)
+    double shc[4], shs[4];                               // the offsets' share of: first half, first half with its last sample, second half, ... with its last sample
+};
+__host__ __device__ inline void chip_fold_constants(double dphi, int KM, int half, bool ks, ChipFold& f) {
+    f = ChipFold{};
+    for (int h = 0; h < 2; ++h) {
+        const int count = chip_fold_count(KM, half, ks, h);
+        double re = (count & 1) ? kCvtBias : 0.0, im = re;      // (the centre sample of an odd run: rotation 1)
+        for (int i = 0; i < count / 2; ++i) {
+            const double d = 0.5 * (double)(count - 1 - 2 * i);  // (half-integers are exact)
+            sincos_reduced(d * dphi, &f.ps[h][i], &f.pc[h][i]);
+            re += f.pc[h][i] * kFoldSumBias - f.ps[h][i] * kFoldDiffBias;
+            im += f.pc[h][i] * kFoldSumBias + f.ps[h][i] * kFoldDiffBias;
+        }
+        sincos_reduced(-0.5 * (double)(count + 1) * dphi, &f.ss[h], &f.sc[h]);
+        f.shc[2 * h] = re, f.shs[2 * h] = im;
+        f.shc[2 * h + 1] = re + (f.sc[h] - f.ss[h]) * kCvtBias, f.shs[2 * h + 1] = im + (f.sc[h] + f.ss[h]) * kCvtBias;
+    }
+    const double turn = (double)chip_fold_first(half, 1) + 0.5 * (double)(chip_fold_count(KM, half, ks, 1) - 1) -
+                        0.5 * (double)(chip_fold_count(KM, half, ks, 0) - 1);
+    sincos_reduced(-turn * dphi, &f.ts, &f.tc);
+}
+// Which forms fold (per-form guard): a form that would lose a wave per SIMD or gain scratch by it keeps the direct sum.
+// Folding holds eight register pairs for the doubles where the direct sum holds four, + 9 .. 17 vector registers by the
+// compiler's count: the three-tap forms that run four waves per SIMD on at most 128 registers -- taps switching inside blocks
+// of up to 19 samples (126 - 128 registers direct, 135 - 137 folded), whole-chip taps on blocks of 18 and more (117 - 124
+// direct, 131 - 138 folded) -- would drop to three.  The other forms run three waves either way (docs/notes/K1.md).
+constexpr bool chip_folds(int NT, int KM, int KS, int KI) {
+    return SDR_FOLD_PAIRS != 0 && SDR_BIASED_CVT != 0 && KM != 0 && (KS != 0 || KI != 0) &&
+           (NT > 3 || (KS != 0 ? KM >= 20 : KM <= 17));
+}
+
 // One epoch of a plan as the straight-line kernels read it (device memory, one per item).
 template <int NT>
 struct ChipSetup {
@@ -209,6 +265,9 @@ struct ChipSetup {
     int64_t base;                               // start_sample % capacity; < 0: the chip-aligned routine does not apply (chip_variant_applies)
     ChipGeom<NT> g;
     ChipRot r;
+#if SDR_FOLD_PAIRS
+    ChipFold f;                                 // (the folded forms read these in the place of r's in-block rotations and shares)
+#endif
 };
 
 // ... and how one is made (one THREAD per item of a plan: epl.hip's chip_setup_kernel; the host builds of the tests).
@@ -234,6 +293,9 @@ __host__ __device__ inline void chip_setup(int n, int64_t start_sample, int64_t 
     if (applies) {
         chip_geometry<NT, KM, KS, KI>(n, S.shift, S.step, S.inv_step, S.g);
         chip_rotations(S.dphi, (int)(((int64_t)stride * S.g.Tfx) >> 32), S.r, chip_half(KM, KS, KI), KM - chip_half(KM, KS, KI));
+#if SDR_FOLD_PAIRS
+        if constexpr (chip_folds(NT, KM, KS, KI)) chip_fold_constants(S.dphi, KM, chip_half(KM, KS, KI), KS != 0, S.f);
+#endif
     }
 }
 
@@ -322,13 +384,15 @@ struct ChipBlock {
 // a sample, where the wave evaluates the reference expression exactly anyway) flags the epoch, which is redone per
 // sample.
 // G: chip_geometry() of the epoch, computed by the caller or read from the plan's ChipSetup; base = start_sample % capacity;
-// R (straight-line forms only): the plan's chip_rotations() of the epoch.
+// R (straight-line forms only): the plan's chip_rotations() of the epoch; RF (the forms that fold, chip_folds()): its
+// chip_fold_constants().
 template <int NT, bool SINGLE_WAVE, int KM = 0, int KS = 0, int KI = 0>
 __device__ __forceinline__ bool correlate_epoch_chip(const void* __restrict__ ring, const void* __restrict__ ring_flipped, int64_t capacity,
                                                      const EpochParams& ep, double dphi, const EpochConsts<NT>& K,
                                                      const ChipGeom<NT>& G, int64_t base, const ChipRot* R,
                                                      const uint32_t* lut, double2* strip_lds, double2* rot, int tid,
-                                                     int lane, int stride, int edge_lane, double* accr, double* acci) {
+                                                     int lane, int stride, int edge_lane, double* accr, double* acci,
+                                                     const ChipFold* RF = nullptr) {
     constexpr int A = NT / 2;                       // anchor tap: the centre one (prompt)
     constexpr int kSlots = chip_strip_slots<NT>();
     const int n = ep.n;
@@ -361,6 +425,11 @@ __device__ __forceinline__ bool correlate_epoch_chip(const void* __restrict__ ri
     // which the walk's vector registers would cost them, and keep the 64-bit line
     constexpr bool kWalk = kStatic && (KS != 0 || NT > 3);
     constexpr int kHalf = chip_half(KM, KS, KI);
+    // ... and of those, the forms that sum their half blocks as folded sample pairs (ChipFold)
+    constexpr bool kFold = kStatic && chip_folds(NT, KM, KS, KI);
+    constexpr int kFoldN0 = chip_fold_count(KM, kHalf, KS != 0, 0), kFoldN1 = chip_fold_count(KM, kHalf, KS != 0, 1);
+    double fpc[2][kFoldPairsMax], fps[2][kFoldPairsMax], fsc[2] = {1.0, 1.0}, fss[2] = {0.0, 0.0};   // (kFold) pair and last-sample rotations
+    double fshc[4] = {0.0, 0.0, 0.0, 0.0}, fshs[4] = {0.0, 0.0, 0.0, 0.0};                           // (kFold) the offsets' shares
     double urc[kStatic ? kHalf + 1 : 1], urs[kStatic ? kHalf + 1 : 1];
     double biasc[3] = {0.0, 0.0, 0.0}, biass[3] = {0.0, 0.0, 0.0};   // (biased conversion) the offset's share of a sum of kHalf - 2 / - 1 / - 0 samples
     // samples per chip as Q32.32, and the distance to a lane's next block: D or D + 1 samples
@@ -377,10 +446,27 @@ __device__ __forceinline__ bool correlate_epoch_chip(const void* __restrict__ ri
         if constexpr (kStatic) {
             // (worked out by the host with the plan: chip_rotations())
             static_assert(kHalf <= kStaticHalf, "the plan's rotations are laid out for half blocks of up to 13 samples");
+            if constexpr (kFold) {
+                static_assert(kFoldN0 / 2 <= kFoldPairsMax && kFoldN1 / 2 <= kFoldPairsMax, "the plan's pair rotations are laid out for runs of up to 13 samples");
 #pragma unroll
-            for (int k = 1; k <= kHalf; ++k) urc[k] = R->urc[k], urs[k] = R->urs[k];
+                for (int h = 0; h < 2; ++h) {
+#pragma unroll
+                    for (int i = 0; i < (h == 0 ? kFoldN0 : kFoldN1) / 2; ++i) fpc[h][i] = RF->pc[h][i], fps[h][i] = RF->ps[h][i];
+                    if (h == 1 || KS != 0) fsc[h] = RF->sc[h], fss[h] = RF->ss[h];
+                }
+                urc[kHalf] = RF->tc, urs[kHalf] = RF->ts;       // (the second half onto the first half's centre)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    if (i == 1 && KS == 0) continue;
+                    fshc[i] = RF->shc[i], fshs[i] = RF->shs[i];
+                    if constexpr (kWalk && (kHalf >= 12 || NT > 3)) asm volatile("" : "+v"(fshc[i]), "+v"(fshs[i]));   // (as biasc / biass below)
+                }
+            } else {
+#pragma unroll
+                for (int k = 1; k <= kHalf; ++k) urc[k] = R->urc[k], urs[k] = R->urs[k];
+            }
             rd0c = R->rd0c, rd0s = R->rd0s, rd1c = R->rd1c, rd1s = R->rd1s;
-            if constexpr (SDR_BIASED_CVT) {
+            if constexpr (SDR_BIASED_CVT && !kFold) {
 #pragma unroll
                 for (int i = 0; i < 3; ++i) {
                     biasc[i] = R->biasc[i], biass[i] = R->biass[i];
@@ -625,7 +711,12 @@ __device__ __forceinline__ bool correlate_epoch_chip(const void* __restrict__ ri
         }
         // carrier phase at the lane's first block: one exact evaluation; later blocks by a fixed rotation
         double sb, cb;
-        sincos_reduced(__builtin_fma(-(double)blk_a.S, dphi_u, rem_carrier_u), &sb, &cb);
+        // (folded forms: at the centre of the first half's run, which the block's sums are referred to)
+        constexpr double kRefSample = kFold ? 0.5 * (double)(kFoldN0 - 1) : 0.0;
+        if constexpr (kFold)
+            sincos_reduced(__builtin_fma(-((double)blk_a.S + kRefSample), dphi_u, rem_carrier_u), &sb, &cb);
+        else
+            sincos_reduced(__builtin_fma(-(double)blk_a.S, dphi_u, rem_carrier_u), &sb, &cb);
         if constexpr (!kStatic) {
             sb = lane <= last_idx ? sb : 0.0;
             cb = lane <= last_idx ? cb : 0.0;
@@ -643,12 +734,17 @@ __device__ __forceinline__ bool correlate_epoch_chip(const void* __restrict__ ri
         // just in front of it has read, and the hazard recognizer puts an s_nop between the two -- one per sample; with the
         // pairs alternating, the pair that is rewritten was last read two samples ago and the pads are gone)
         sdr_u32x2 zI2 = {0u, 0u}, zQ2 = {0u, 0u};
-        if constexpr (kWalk) asm volatile("" : "+v"(zI2), "+v"(zQ2));
+        if constexpr (kWalk || kFold) asm volatile("" : "+v"(zI2), "+v"(zQ2));
+        // (folded forms: the differences of a pair beside its sums -- zI / zQ and zI2 / zQ2 hold the sums, and the single
+        // samples in between -- and the high word of 8192.0 the byte sums are added onto)
+        sdr_u32x2 zDI = {0u, 0u}, zDQ = {0u, 0u}, zDI2 = {0u, 0u}, zDQ2 = {0u, 0u};
+        uint32_t hi_fold = 0x40C00000u;
+        if constexpr (kFold) asm volatile("" : "+v"(zDI), "+v"(zDQ), "+v"(zDI2), "+v"(zDQ2), "+v"(hi_fold));
 
         // (straight-line forms: the biased conversion's high-word constant, a vector register for the whole epoch -- v_perm_b32
         // takes one scalar operand, the selector; made opaque per block it was a move per block)
         uint32_t hi_epoch = 0x40B00000u;
-        if constexpr (kWalk && SDR_BIASED_CVT) asm volatile("" : "+v"(hi_epoch));
+        if constexpr ((kWalk || kFold) && SDR_BIASED_CVT) asm volatile("" : "+v"(hi_epoch));
         auto process = [&](const ChipBlock<NT>& b, int round, double sbk, double cbk, auto clampc) {
             constexpr bool kClamp = decltype(clampc)::value;   // (straight-line forms) the round may be the epoch's last one
             double pr = 0.0, pi = 0.0;
@@ -707,10 +803,77 @@ __device__ __forceinline__ bool correlate_epoch_chip(const void* __restrict__ ri
                 uint32_t flipped[kChipRawDwords];
                 uint32_t hi_const = hi_epoch;
                 if constexpr (SDR_BIASED_CVT) {
-                    if constexpr (!kWalk) asm volatile("" : "+v"(hi_const));   // (v_perm_b32 takes one scalar operand: the selector)
+                    if constexpr (!kWalk && !kFold) asm volatile("" : "+v"(hi_const));   // (v_perm_b32 takes one scalar operand: the selector)
 #pragma unroll
                     for (int i = 0; i < kChipRawDwords; ++i) flipped[i] = b.raw[i];   // (the ring holds the flipped bytes)
                 }
+                if constexpr (kFold) {
+                    // Each half: the centre sample of an odd run starts the sum, then the pairs from the outside in, then the
+                    // optional last sample.  `seq` counts these steps through the block: odd steps build their doubles in the
+                    // second register set (see SDR_ALT_PAIRS: a high word is rewritten two steps after it was last read).
+                    auto single = [&](auto kc, auto seqc, bool start, double rc, double rs) {
+                        constexpr int k = decltype(kc)::value;
+                        constexpr bool alt = SDR_ALT_PAIRS && (decltype(seqc)::value & 1);
+                        const double ar = biased_sample(alt ? zI2 : zI, flipped[k >> 1], cvt_selector((k & 1) ? 2 : 0), hi_const);
+                        const double ai = biased_sample(alt ? zQ2 : zQ, flipped[k >> 1], cvt_selector((k & 1) ? 3 : 1), hi_const);
+                        if (start) {
+                            pr = ar, pi = ai;
+                        } else {
+                            pr = __builtin_fma(-ai, rs, __builtin_fma(ar, rc, pr));
+                            pi = __builtin_fma(ai, rc, __builtin_fma(ar, rs, pi));
+                        }
+                        if constexpr (alt) asm volatile("" : "+v"(pr), "+v"(pi), "+v"(zI2), "+v"(zQ2));
+                        else asm volatile("" : "+v"(pr), "+v"(pi), "+v"(zI), "+v"(zQ));
+                    };
+                    auto pair = [&](auto kac, auto kbc, auto seqc, bool start, double c, double sn) {
+                        constexpr int ka = decltype(kac)::value, kb = decltype(kbc)::value;
+                        constexpr bool alt = SDR_ALT_PAIRS && (decltype(seqc)::value & 1);
+                        // G = [aI aQ bI bQ], lowest byte first (selector bytes 4 .. 7: the first operand, 0 .. 3: the second)
+                        constexpr uint32_t ia = 4u + 2u * (ka & 1), ib = 2u * (kb & 1);
+                        const uint32_t g = __builtin_amdgcn_perm(flipped[ka >> 1], flipped[kb >> 1], ((ib + 1u) << 24) | (ib << 16) | ((ia + 1u) << 8) | ia);
+                        const uint32_t g2 = g ^ 0xFFFF0000u;
+                        sdr_u32x2& SI = alt ? zI2 : zI;
+                        sdr_u32x2& SQ = alt ? zQ2 : zQ;
+                        sdr_u32x2& DI = alt ? zDI2 : zDI;
+                        sdr_u32x2& DQ = alt ? zDQ2 : zDQ;
+                        SI.y = __builtin_amdgcn_udot4(g, 0x00800080u, hi_fold, false);
+                        SQ.y = __builtin_amdgcn_udot4(g, 0x80008000u, hi_fold, false);
+                        DI.y = __builtin_amdgcn_udot4(g2, 0x00800080u, hi_fold, false);
+                        DQ.y = __builtin_amdgcn_udot4(g2, 0x80008000u, hi_fold, false);
+                        const double si = __builtin_bit_cast(double, SI), sq = __builtin_bit_cast(double, SQ);
+                        const double di = __builtin_bit_cast(double, DI), dq = __builtin_bit_cast(double, DQ);
+                        if (start) {
+                            pr = __builtin_fma(-sn, dq, c * si);
+                            pi = __builtin_fma(sn, di, c * sq);
+                        } else {
+                            pr = __builtin_fma(-sn, dq, __builtin_fma(c, si, pr));
+                            pi = __builtin_fma(sn, di, __builtin_fma(c, sq, pi));
+                        }
+                        if constexpr (alt) asm volatile("" : "+v"(pr), "+v"(pi), "+v"(zI2), "+v"(zQ2), "+v"(zDI2), "+v"(zDQ2));
+                        else asm volatile("" : "+v"(pr), "+v"(pi), "+v"(zI), "+v"(zQ), "+v"(zDI), "+v"(zDQ));
+                    };
+                    static_for<0, 2>([&](auto hc) {
+                        constexpr int h = decltype(hc)::value;
+                        constexpr int first = chip_fold_first(kHalf, h), count = h == 0 ? kFoldN0 : kFoldN1;
+                        constexpr int odd = count & 1;
+                        constexpr int seq0 = h == 0 ? 0 : (kFoldN0 & 1) + kFoldN0 / 2 + (KS != 0 ? 1 : 0);
+                        if constexpr (odd) single(std::integral_constant<int, first + count / 2>{}, std::integral_constant<int, seq0>{}, true, 1.0, 0.0);
+                        static_for<0, count / 2>([&](auto ic) {
+                            constexpr int i = decltype(ic)::value;
+                            pair(std::integral_constant<int, first + i>{}, std::integral_constant<int, first + count - 1 - i>{},
+                                 std::integral_constant<int, seq0 + odd + i>{}, !odd && i == 0, fpc[h][i], fps[h][i]);
+                        });
+                        if constexpr (h == 0) {
+                            capr[0] = pr, capi[0] = pi;                                // the first half before its last sample
+                            if constexpr (KS != 0)
+                                single(std::integral_constant<int, first + count>{}, std::integral_constant<int, seq0 + odd + count / 2>{}, false, fsc[0], fss[0]);
+                            capr[2] = pr, capi[2] = pi;                                // ... and with it (whole-chip taps: the same sum)
+                        } else {
+                            capr[1] = pr, capi[1] = pi;                                // the second half up to the M-th sample
+                            single(std::integral_constant<int, first + count>{}, std::integral_constant<int, seq0 + odd + count / 2>{}, false, fsc[1], fss[1]);
+                        }
+                    });
+                } else
                 static_for<0, KM + 1>([&](auto kc) {
                     constexpr int k = decltype(kc)::value;
                     constexpr int j = k < kHalf ? k : k - kHalf;
@@ -777,7 +940,13 @@ __device__ __forceinline__ bool correlate_epoch_chip(const void* __restrict__ ri
                 }
             }
             double2 ptot;
-            if constexpr (kStatic && SDR_BIASED_CVT) {
+            if constexpr (kFold) {
+                // what the offsets -- 8448 and 8447 per pair, 4224 per single sample -- put into each sum that is read
+                pr -= fshc[3], pi -= fshs[3];
+                capr[1] -= fshc[2], capi[1] -= fshs[2];
+                capr[2] -= fshc[KS != 0 ? 1 : 0], capi[2] -= fshs[KS != 0 ? 1 : 0];
+                if constexpr (KS != 0) capr[0] -= fshc[0], capi[0] -= fshs[0];
+            } else if constexpr (kStatic && SDR_BIASED_CVT) {
                 // what the offset of 4224 per sample put into each sum that is read (its first sample has rotation 1:
                 // the sums start from the biased sample itself, and sum_{k<n} r_k includes that r_0 = 1)
                 constexpr int iFirst = 2 * kHalf - KM;             // (biasc[i]: a sum of KM - kHalf + i samples)

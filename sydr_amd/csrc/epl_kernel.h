@@ -88,6 +88,7 @@ __global__ __launch_bounds__(kWaveThreads * WPW, (KS != 0 ? SDR_EPL_KS_WAVES : (
     EpochConsts<NT> K;
     ChipGeom<NT> G;
     const ChipRot* rot_plan = nullptr;
+    const ChipFold* fold_plan = nullptr;
     int64_t base = -1;
     if constexpr (kPre) {
         // everything wave-uniform that is not a sincos was worked out by the host when the plan was made: scalar loads
@@ -102,6 +103,9 @@ __global__ __launch_bounds__(kWaveThreads * WPW, (KS != 0 ? SDR_EPL_KS_WAVES : (
         }
         G = S.g;
         rot_plan = &S.r;
+#if SDR_FOLD_PAIRS
+        fold_plan = &S.f;
+#endif
         base = S.base;
     } else if constexpr (W == kChipMax && FMT == SDR_FMT_CI8) {
         compute_tap_constants<NT>(K, ep, spacing + tap0);   // (the chip-aligned core evaluates its own rotations)
@@ -128,12 +132,12 @@ __global__ __launch_bounds__(kWaveThreads * WPW, (KS != 0 ? SDR_EPL_KS_WAVES : (
                                                                  tid, lane, kWaveThreads, lane, accr, acci);
             else if (base >= 0 && M == KM2)
                 done = correlate_epoch_chip<NT, true, KM2, 0, 0>(ring, ring_flipped, capacity, ep, dphi, K, G, base, rot_plan, lut, prefix, rot,
-                                                                  tid, lane, kWaveThreads, lane, accr, acci);
+                                                                  tid, lane, kWaveThreads, lane, accr, acci, fold_plan);
         } else {
             done = base >= 0 &&
                    correlate_epoch_chip<NT, true, KM, KS, KI>(ring, ring_flipped, capacity, ep, dphi, K, G, base, rot_plan, lut, prefix,
                                                               prefix + kThreads * chip_strip_slots<NT>() + wave * kChipRotSlots,
-                                                              tid, lane, kWaveThreads, lane, accr, acci);
+                                                              tid, lane, kWaveThreads, lane, accr, acci, fold_plan);
         }
         if (!done) {
             // (its own copy of the per-epoch constants: the in-group rotations the per-sample routine wants would
