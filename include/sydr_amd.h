@@ -39,7 +39,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define SDR_ABI_VERSION 5   /* 5 (still): + sdr_iq_probe (additive); 5 (still): + sdr_corr_profile, option "corr_profile_per_sample" (additive); 5 (still): + sdr_iq_packing, sdr_iq_packed_bytes, sdr_iq_upload_packed / _begin / _queue (additive); 5 (still): + sdr_acq_refine, sdr_acq_refine_bins (additive); 5: + sdr_bank_tick_mirrored_begin / _end, sdr_iq_upload_queue, sdr_host_alloc / _free, options "tick_server" + sdr_tick_server_stats, "bind_thread_to_device" (additive); 4: + sdr_build_id, sdr_epl_plan_create_dev, sdr_bank_tick_mirrored, sdr_iq_upload_begin, sdr_block_schedule, sdr_bank_step_begin / _end (additive) */
+#define SDR_ABI_VERSION 5   /* 5 (still): + sdr_ddc_cfg, sdr_ddc_create / _destroy / _reset / _push / _push_queue / _out_count (additive); 5 (still): + sdr_iq_probe (additive); 5 (still): + sdr_corr_profile, option "corr_profile_per_sample" (additive); 5 (still): + sdr_iq_packing, sdr_iq_packed_bytes, sdr_iq_upload_packed / _begin / _queue (additive); 5 (still): + sdr_acq_refine, sdr_acq_refine_bins (additive); 5: + sdr_bank_tick_mirrored_begin / _end, sdr_iq_upload_queue, sdr_host_alloc / _free, options "tick_server" + sdr_tick_server_stats, "bind_thread_to_device" (additive); 4: + sdr_build_id, sdr_epl_plan_create_dev, sdr_bank_tick_mirrored, sdr_iq_upload_begin, sdr_block_schedule, sdr_bank_step_begin / _end (additive) */
 
 typedef struct sdr_engine sdr_engine;
 
@@ -587,6 +587,56 @@ int64_t sdr_iq_packed_bytes(const sdr_iq_packing* pk, int64_t n_samples);
 int sdr_iq_upload_packed(sdr_engine* e, const sdr_iq_packing* pk, const void* packed, int64_t n_samples, int64_t ring_offset);
 int sdr_iq_upload_packed_begin(sdr_engine* e, const sdr_iq_packing* pk, const void* packed, int64_t n_samples, int64_t ring_offset);
 int sdr_iq_upload_packed_queue(sdr_engine* e, const sdr_iq_packing* pk, const void* packed, int64_t n_samples, int64_t ring_offset);
+
+/* ------------------------------------------------- down-conversion and decimation into the ring
+ * A digital down-converter (mixer, FIR low-pass, decimator) between the host's slab and the ring, for real or complex
+ * recordings at an intermediate frequency and for wide-band recordings (50 MHz where the channels need 10 MHz): converted where
+ * the samples enter the ring, nothing downstream of the ring changes.  The NumPy form of what follows is
+ * sydr_amd/signal/downconvert.py `statement`; it is the only yardstick.
+ * A converter has an input format, a decimation D in 1..64, T in 1..512 taps h[0..T-1] (doubles), a frequency word and a gain:
+ *   fcw = round(shift_hz / fs_in * 2^64) mod 2^64      (unsigned, 2^-64 turns per INPUT sample; exact rational arithmetic)
+ * Inputs are counted j = 0, 1, ... from creation or reset, across pushes; x_j is the sample as a complex number (imaginary part
+ * 0 for real formats), x_j = 0 for j < 0:
+ *   p_j = (j * fcw) mod 2^64                           (uint64 wrap)
+ *   t_j = (p_j >> 11) * 2^-53                          (exact in a double, in [0, 1))
+ *   z_j = x_j * (cos 2 pi t_j - i sin 2 pi t_j)
+ *   v_m = gain * sum_{k < T} h_k * z_{m D - k}         m = 0, 1, ...   (fp64; k ascending, product then sum)
+ * A push of n_in inputs whose first has index N writes exactly the outputs m with N <= m D < N + n_in, in order, at ring samples
+ * (ring_offset + i) mod capacity, and nothing else.  A cf64 ring stores v, a cf32 ring v rounded to nearest float, an integer
+ * ring clip(rint(v)) (ties to even; clip +-127 for ci8, +-32767 for ci16).  T = 1, h = {1}, D = 1, fcw = 0, gain = 1 leaves a
+ * real recording as (r, 0) exactly.  The converter keeps the last T - 1 RAW inputs as its history and the phasor is a function
+ * of j alone: what the ring holds does not depend on how the stream was cut into pushes, bit for bit, float rings included.
+ * The group delay (T - 1) / 2 input samples of a symmetric filter is the caller's to account for.
+ * sdr_ddc_push keeps sdr_iq_upload's host-buffer contract (synchronous; `in` is the caller's again on return),
+ * sdr_ddc_push_queue that of sdr_iq_upload_queue (one copy command into a staging buffer of the engine in HBM, the kernels
+ * behind it on the engine's stream, no wait: `in` stays valid and unchanged until sdr_engine_sync or a later synchronous call
+ * returns).  *n_out (nullable) = the outputs written = what sdr_ddc_out_count said before the call (host arithmetic on the
+ * converter's count of inputs).  Like every call but the tick's own, a push sends a resident tick server away and puts a parked
+ * slab into the ring first.
+ * SDR_ERR_INVALID: NULL arguments, D outside 1..64, T outside 1..512, a non-finite tap or gain, an unknown format, non-zero
+ * flags, n_in < 0, a converter of another engine; SDR_ERR_STATE: no ring; SDR_ERR_RANGE: more outputs than the ring holds,
+ * ring_offset outside 0 .. capacity - 1.  n_in = 0 succeeds and writes nothing.  A refused push changes neither the ring nor
+ * the converter.  sdr_prof_enable scopes: "ddc_kernel", "ddc_history_kernel", "call_ddc_push". */
+enum sdr_ddc_input {
+    SDR_DDC_IN_R8 = 0,   /* real int8                 */
+    SDR_DDC_IN_R16 = 1,  /* real int16                */
+    SDR_DDC_IN_CI8 = 2,  /* int8  I, int8  Q          */
+    SDR_DDC_IN_CI16 = 3  /* int16 I, int16 Q          */
+};
+typedef struct sdr_ddc_cfg {
+    int32_t in_fmt, decimation, n_taps, flags;   /* flags: 0 */
+    uint64_t fcw;
+    double gain;
+    const double* taps;                          /* [n_taps]; copied by sdr_ddc_create */
+} sdr_ddc_cfg;
+typedef struct sdr_ddc sdr_ddc;
+int sdr_ddc_create(sdr_engine* e, const sdr_ddc_cfg* cfg, sdr_ddc** out);
+void sdr_ddc_destroy(sdr_engine* e, sdr_ddc* d);
+/* History zero, j = 0 (ordered behind the pushes queued so far). */
+int sdr_ddc_reset(sdr_engine* e, sdr_ddc* d);
+int sdr_ddc_push(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in, int64_t ring_offset, int64_t* n_out);
+int sdr_ddc_push_queue(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in, int64_t ring_offset, int64_t* n_out);
+int64_t sdr_ddc_out_count(const sdr_ddc* d, int64_t n_in);
 
 /* ------------------------------------------------- what the ring holds: levels, histogram, spectrum
  * The first look at a new recording and the look a running receiver keeps taking at its front end -- are the bits used, is

@@ -69,6 +69,15 @@ class ProbeResultC(C.Structure):
                 ("sum_iq", C.c_double)]
 
 
+class DdcCfg(C.Structure):
+    """sdr_ddc_cfg (include/sydr_amd.h): input format, decimation, taps, frequency word and gain of a down-converter."""
+    _fields_ = [("in_fmt", C.c_int32), ("decimation", C.c_int32), ("n_taps", C.c_int32), ("flags", C.c_int32),
+                ("fcw", C.c_uint64), ("gain", C.c_double), ("taps", C.POINTER(C.c_double))]
+
+
+DDC_IN_R8, DDC_IN_R16, DDC_IN_CI8, DDC_IN_CI16 = 0, 1, 2, 3
+
+
 class SynthSat(C.Structure):
     _fields_ = [("prn", C.c_int32), ("flags", C.c_int32), ("doppler_hz", C.c_double),
                 ("code_phase", C.c_double), ("carrier_phase", C.c_double), ("amplitude", C.c_double)]
@@ -213,6 +222,12 @@ _PROTOTYPES = {
     "sdr_iq_upload_packed": (C.c_int, [_VP, C.POINTER(IqPacking), _VP, C.c_int64, C.c_int64]),
     "sdr_iq_upload_packed_begin": (C.c_int, [_VP, C.POINTER(IqPacking), _VP, C.c_int64, C.c_int64]),
     "sdr_iq_upload_packed_queue": (C.c_int, [_VP, C.POINTER(IqPacking), _VP, C.c_int64, C.c_int64]),
+    "sdr_ddc_create": (C.c_int, [_VP, C.POINTER(DdcCfg), C.POINTER(_VP)]),
+    "sdr_ddc_destroy": (None, [_VP, _VP]),
+    "sdr_ddc_reset": (C.c_int, [_VP, _VP]),
+    "sdr_ddc_push": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
+    "sdr_ddc_push_queue": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
+    "sdr_ddc_out_count": (C.c_int64, [_VP, C.c_int64]),
     "sdr_tick_server_stats": (C.c_int, [_VP, C.POINTER(C.c_int64)]),
     "sdr_tick_server_phases": (C.c_int, [_VP, C.POINTER(C.c_double)]),
     "sdr_tick_server_tracker_phases": (C.c_int, [_VP, C.POINTER(C.c_double)]),

@@ -44,6 +44,8 @@ class ChannelManager:
     PREFETCH = True               # read-ahead: the next block is queued on the device while the current one is handed out
 
     def __new__(cls, rfSignal=None, *args, devices=None, engines=None, **kwargs):
+        if getattr(rfSignal, "frontEnd", None) is not None and (engines is not None or (devices is not None and len(devices) != 1)):
+            raise ValueError("a recording with a front end (down-conversion into the ring) is received on one device")
         # ChannelManager(rfSignal, devices=[0, 1, ..., 7]) -- ONE manager, as the reference's receiver builds it
         # (receiver.py:86), over the GPUs of a node: multidevice.py
         if cls is ChannelManager and (engines is not None or (devices is not None and len(devices) != 1)):
@@ -70,7 +72,16 @@ class ChannelManager:
         self._packing = getattr(rfSignal, "packing", None)
         if self._packing is not None:
             fmt = FMT_CI8
+        # a recording with a front end (signal/iqsource.py FrontEnd) enters the ring through the device's down-converter: the
+        # ring runs at the OUTPUT rate in the output format, and this instance's slab routes are the converting ones --
+        # decided here once; a manager without one runs the class's own methods, not a line more per tick
+        self._frontEnd = getattr(rfSignal, "frontEnd", None)
+        if self._frontEnd is not None:
+            fmt = FMT_CI8 if self._frontEnd.outputBits == 8 else FMT_CI16
+            self.addNewRFData = self._addNewRFData_converted
+            self._upload_block = self._upload_block_converted
         self.sharedBuffer = CircularBuffer(buffersize, rfSignal.dtype, engine=engine, fmt=fmt)
+        self._ddc = engine.ddc_create(self._frontEnd.config) if self._frontEnd is not None else None
         self.resultQueue = None
         self.keepCorrelationMap = keepCorrelationMap
         self._slots = 0
@@ -144,6 +155,8 @@ class ChannelManager:
         recording's next millisecond is refused while a block is being replayed.  0 switches it off (once the
         epochs already computed have been handed out)."""
         from .readahead import EpochSchedule
+        if self._frontEnd is not None and int(nbMilliseconds) > 0:
+            raise ValueError("read-ahead over a recording with a front end is not supported: its slabs are not the ring's bytes")
         self._ra_ms = max(0, int(nbMilliseconds))
         self._EpochSchedule = EpochSchedule
 
@@ -374,6 +387,50 @@ class ChannelManager:
         else:
             self.engine.iq_upload(block, offset)
 
+    # ------------------------------------------------------------------ recordings with a front end (signal/downconvert.py)
+    def _raw_input(self, data):
+        """A slab of raw input as the converter takes it: contiguous, the recording's integer type, whole samples."""
+        cfg = self._frontEnd.config
+        from ..signal.downconvert import input_dtype, input_is_complex
+        data = np.ascontiguousarray(data, dtype=input_dtype(cfg.in_fmt)).reshape(-1) if not (
+            type(data) is np.ndarray and data.ndim == 1 and data.flags.c_contiguous and data.dtype == input_dtype(cfg.in_fmt)) else data
+        per = 2 if input_is_complex(cfg.in_fmt) else 1
+        if data.size % per:
+            raise ValueError("interleaved I,Q data needs an even number of elements")
+        return data, data.size // per
+
+    def _addNewRFData_converted(self, data):
+        """addNewRFData of a recording with a front end: `data` is raw INPUT (rfSignal.getMilliseconds), which the device's
+        down-converter mixes, filters and decimates into the ring -- queued on the engine's stream, ordered ahead of the tick's
+        launch.  The ring advances by the outputs: n_in / D.  Nothing is parked for the tick's own launch or a resident tick
+        server (those pull the ring's own bytes), and there is no read-ahead over such a recording."""
+        if self._pending:
+            self._flush_pending()
+        ring = self.sharedBuffer
+        data, n_in = self._raw_input(data)
+        D = self._frontEnd.decimation
+        if n_in == 0 or n_in % D:
+            raise ValueError(f"a slab of {n_in} input samples is not a whole multiple of decimation {D}")
+        count = n_in // D
+        if ring.maxSize % count:
+            raise ValueError("Data shift need to be a multiple from the max buffer size.")
+        if ring.full and (self._unread_max is None or self._unread_max + count > ring.maxSize):
+            self._guard_unread(count)
+        self._unread_max = None
+        if data.nbytes > self.DEFER_BYTES or not hasattr(self.engine, "ddc_push_queue"):
+            written = self.engine.ddc_push(self._ddc, data, ring.idxWrite)
+        else:
+            written = self.engine.ddc_push_queue(self._ddc, data, ring.idxWrite)
+            self._pending, self._queued_input = True, data       # (the input stays alive until the stream has been waited for)
+        if written != count:
+            raise RuntimeError(f"the down-converter wrote {written} samples where {count} were expected")
+        ring.shiftIdxWrite(count)
+
+    def _upload_block_converted(self, block, n_samples: int, offset: int):
+        """A block of raw input through the converter into the ring at `offset`, waited for."""
+        block, _ = self._raw_input(block)
+        self.engine.ddc_push(self._ddc, block, offset)
+
     def _guard_unread(self, count: int):
         """Refuse to overwrite samples a tracking channel has not consumed yet (the reference would silently wrap:
         circularbuffer.py:54-82 -- and then track garbage)."""
@@ -432,6 +489,9 @@ class ChannelManager:
 
     def close(self):
         self._flush_pending()
+        if self._ddc is not None:
+            self.engine.ddc_destroy(self._ddc)
+            self._ddc = None
         if self._ahead is not None and self._ahead["bank"] is self.bank:
             self.bank.device.step_end()                       # (a block queued ahead: let it finish before the bank goes)
         self._ahead = None

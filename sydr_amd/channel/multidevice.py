@@ -42,6 +42,8 @@ class MultiDeviceChannelManager:
     def __init__(self, rfSignal, *, devices=None, engines=None, keepCorrelationMap: bool = True, ring_ms: int = 100):
         """devices: HIP device numbers, one part each (a number may repeat: a second engine on the same card -- how the
         one-GPU test box rehearses two devices); engines: ready-made engines instead (not closed by close())."""
+        if getattr(rfSignal, "frontEnd", None) is not None:
+            raise ValueError("a recording with a front end (down-conversion into the ring) is received on one device")
         self.rfSignal = rfSignal
         self._owned = []
         if engines is None:

@@ -1,0 +1,237 @@
+// Digital down-converter between the host's slab and the ring (sdr_ddc_*): mixer, FIR low-pass, decimator.  Real or complex
+// recordings at an intermediate frequency and wide-band recordings are converted where they enter the ring; nothing
+// downstream of the ring knows.  What the ring must hold is stated in include/sydr_amd.h and, as NumPy, in
+// sydr_amd/signal/downconvert.py: the phasor is a pure function of the absolute input index, every output is the same T
+// products added in the same order whatever tile or push it falls into -- so the ring does not depend on how the stream was
+// cut into pushes, bit for bit.
+#include "engine_internal.h"
+#include "ddc_tiles.h"
+#include "sincos_reduced.h"
+
+#include <cmath>
+#include <new>
+
+using namespace sdr;
+
+struct sdr_ddc {
+    sdr_engine* engine = nullptr;
+    int in_fmt = 0, D = 1, T = 1;
+    uint64_t fcw = 0;
+    double gain = 1.0;
+    double* taps = nullptr;      // device [T]
+    void* hist = nullptr;        // device [max(T-1, 1)] raw inputs, oldest first
+    int64_t n_seen = 0;          // inputs since creation / reset
+};
+
+static inline size_t ddc_in_bytes(int in_fmt) {
+    switch (in_fmt) {
+        case SDR_DDC_IN_R8: return 1;
+        case SDR_DDC_IN_R16: return 2;
+        case SDR_DDC_IN_CI8: return 2;
+        case SDR_DDC_IN_CI16: return 4;
+    }
+    return 0;
+}
+
+__device__ __forceinline__ void ddc_load(const void* __restrict__ p, int64_t i, int in_fmt, double* re, double* im) {
+    switch (in_fmt) {
+        case SDR_DDC_IN_R8: *re = (double)((const int8_t*)p)[i], *im = 0.0; break;
+        case SDR_DDC_IN_R16: *re = (double)((const int16_t*)p)[i], *im = 0.0; break;
+        case SDR_DDC_IN_CI8: {
+            const uint16_t w = ((const uint16_t*)p)[i];
+            *re = (double)(int8_t)(w & 0xff), *im = (double)(int8_t)(w >> 8);
+            break;
+        }
+        default: {
+            const uint32_t w = ((const uint32_t*)p)[i];
+            *re = (double)(int16_t)(w & 0xffff), *im = (double)(int16_t)(w >> 16);
+            break;
+        }
+    }
+}
+
+__device__ __forceinline__ double ddc_clip_rint(double v, double lim) { return fmin(fmax(rint(v), -lim), lim); }
+
+// One workgroup per tile of outputs (ddc_tiles.h).  Phase 1: the tile's inputs, each mixed once, into LDS as fp64 complex.
+// Phase 2: a lane per output, the taps by wave-uniform (scalar) loads, k ascending, product then sum (no contraction: the
+// NumPy statement's own operations); the store in the ring's format, a ci8 ring's bytes sign-flipped.
+__global__ __launch_bounds__(kDdcThreads) void ddc_kernel(const void* __restrict__ in, const void* __restrict__ hist,
+                                                          const double* __restrict__ taps, void* __restrict__ ring, DdcPush push, int tile,
+                                                          int in_fmt, int out_fmt, uint64_t fcw, double gain, int64_t ring_offset,
+                                                          int64_t capacity) {
+    extern __shared__ __attribute__((aligned(16))) char ddc_smem[];
+    double2* z = (double2*)ddc_smem;
+    const DdcTile t = ddc_tile(push, tile, blockIdx.x);
+    for (int i = threadIdx.x; i < t.span; i += kDdcThreads) {
+        const int64_t j = t.j0 + i;
+        const int64_t src = ddc_source(push, j);
+        double xr = 0.0, xi = 0.0;
+        if (src < 0) ddc_load(hist, ~src, in_fmt, &xr, &xi);
+        else if (src < push.n_in) ddc_load(in, src, in_fmt, &xr, &xi);
+        const uint64_t p = (uint64_t)j * fcw;                       // (j < 0: x = 0 whatever the phasor)
+        const double turn = (double)(p >> 11) * 0x1p-53;
+        double s, c;
+        sincos_reduced(6.283185307179586 * turn, &s, &c);
+        z[i] = make_double2(xr * c + xi * s, xi * c - xr * s);
+    }
+    __syncthreads();
+    const int T = push.T, D = push.D;
+    for (int o = threadIdx.x; o < t.count; o += kDdcThreads) {
+        const double2* zo = z + (o * D + (T - 1));
+        double ar = 0.0, ai = 0.0;
+        for (int k = 0; k < T; ++k) {
+            const double h = taps[k];
+            const double2 v = zo[-k];
+            ar += h * v.x;
+            ai += h * v.y;
+        }
+        ar *= gain, ai *= gain;
+        const int64_t pos = ddc_ring_pos(ring_offset, t.i0 + o, capacity);
+        switch (out_fmt) {
+            case SDR_FMT_CI8: {
+                const int re = (int)ddc_clip_rint(ar, 127.0), im = (int)ddc_clip_rint(ai, 127.0);
+                ((uint16_t*)ring)[pos] = (uint16_t)((((unsigned)re & 0xffu) | (((unsigned)im & 0xffu) << 8)) ^ 0x8080u);
+                break;
+            }
+            case SDR_FMT_CI16: {
+                const int re = (int)ddc_clip_rint(ar, 32767.0), im = (int)ddc_clip_rint(ai, 32767.0);
+                ((uint32_t*)ring)[pos] = ((unsigned)re & 0xffffu) | (((unsigned)im & 0xffffu) << 16);
+                break;
+            }
+            case SDR_FMT_CF32: ((float2*)ring)[pos] = make_float2((float)ar, (float)ai); break;
+            default: ((double2*)ring)[pos] = make_double2(ar, ai); break;
+        }
+    }
+}
+
+// The history after a push: one workgroup, every lane reads its element (out of the block, or -- a push shorter than T-1 --
+// further up the old history) before any lane writes.  `unit` = bytes per raw input.
+__global__ __launch_bounds__(kDdcMaxTaps) void ddc_history_kernel(const void* __restrict__ in, void* hist, int64_t n_in, int T, int unit) {
+    const int i = threadIdx.x;
+    uint32_t v = 0;
+    if (i < T - 1) {
+        const int64_t src = ddc_hist_source(n_in, T, i);
+        const void* from = src >= 0 ? in : (const void*)hist;
+        const int64_t at = src >= 0 ? src : ~src;
+        v = unit == 1 ? ((const uint8_t*)from)[at] : unit == 2 ? ((const uint16_t*)from)[at] : ((const uint32_t*)from)[at];
+    }
+    __syncthreads();
+    if (i < T - 1) {
+        if (unit == 1) ((uint8_t*)hist)[i] = (uint8_t)v;
+        else if (unit == 2) ((uint16_t*)hist)[i] = (uint16_t)v;
+        else ((uint32_t*)hist)[i] = v;
+    }
+}
+
+static int ddc_check(sdr_engine* e, const sdr_ddc* d) {
+    if (!d) return sdr_fail(SDR_ERR_INVALID, "converter is NULL");
+    if (d->engine != e) return sdr_fail(SDR_ERR_INVALID, "the converter belongs to another engine");
+    return SDR_OK;
+}
+
+static int ddc_push_impl(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in, int64_t off, int64_t* n_out, bool wait) {
+    if (int rc = sdr_set_device(e)) return rc;
+    if (int rc = ddc_check(e, d)) return rc;
+    if (!e->iq) return sdr_fail(SDR_ERR_STATE, "IQ ring not allocated");
+    if (n_in < 0) return sdr_fail(SDR_ERR_INVALID, "negative input count");
+    if (!in && n_in > 0) return sdr_fail(SDR_ERR_INVALID, "host pointer is NULL");
+    const int64_t cap = e->iq_capacity;
+    if (off < 0 || off >= cap) return sdr_fail(SDR_ERR_RANGE, "ring offset %lld outside the ring of %lld samples", (long long)off, (long long)cap);
+    if (n_in / d->D > cap) return sdr_fail(SDR_ERR_RANGE, "%lld inputs make more outputs than the ring of %lld samples holds", (long long)n_in, (long long)cap);
+    const DdcPush push = ddc_push(d->n_seen, n_in, d->D, d->T);
+    if (push.n_out > cap)
+        return sdr_fail(SDR_ERR_RANGE, "%lld outputs exceed the ring capacity %lld", (long long)push.n_out, (long long)cap);
+    if (n_out) *n_out = push.n_out;
+    if (n_in == 0) return SDR_OK;
+    ProfScope whole(e, "call_ddc_push");
+    const size_t unit = ddc_in_bytes(d->in_fmt), bytes = (size_t)n_in * unit;
+    // one copy command brings the raw inputs into the engine's staging buffer in HBM (no kernel reads host memory), the
+    // kernels follow it on the same stream -- whose order is all the guard the buffer and the history need
+    if (int rc = sdr_devbuf_reserve(e, &e->ddc_stage, bytes)) return rc;
+    SDR_HIP(hipMemcpyAsync(e->ddc_stage.ptr, in, bytes, hipMemcpyHostToDevice, e->stream));
+    if (push.n_out > 0) {
+        sdr_iq_mark_written(e, off, push.n_out);
+        const int tile = ddc_tile_outputs(d->D, d->T);
+        const int64_t tiles = ddc_tiles(push, tile);
+        const size_t lds = (size_t)((tile - 1) * d->D + d->T) * sizeof(double2);
+        ProfScope ps(e, "ddc_kernel");
+        hipLaunchKernelGGL(ddc_kernel, dim3((unsigned)tiles), dim3(kDdcThreads), lds, e->stream, (const void*)e->ddc_stage.ptr,
+                           (const void*)d->hist, (const double*)d->taps, e->iq, push, tile, d->in_fmt, e->iq_fmt, d->fcw, d->gain, off, cap);
+    }
+    if (d->T > 1) {
+        ProfScope ps(e, "ddc_history_kernel");
+        hipLaunchKernelGGL(ddc_history_kernel, dim3(1), dim3(kDdcMaxTaps), 0, e->stream, (const void*)e->ddc_stage.ptr, d->hist, n_in, d->T,
+                           (int)unit);
+    }
+    SDR_HIP(hipGetLastError());
+    d->n_seen += n_in;
+    if (wait) SDR_HIP(hipStreamSynchronize(e->stream));
+    return SDR_OK;
+}
+
+extern "C" {
+
+int sdr_ddc_create(sdr_engine* e, const sdr_ddc_cfg* cfg, sdr_ddc** out) {
+    if (int rc = sdr_set_device(e)) return rc;
+    if (!cfg || !out) return sdr_fail(SDR_ERR_INVALID, "NULL configuration or result pointer");
+    *out = nullptr;
+    if (cfg->in_fmt < SDR_DDC_IN_R8 || cfg->in_fmt > SDR_DDC_IN_CI16) return sdr_fail(SDR_ERR_INVALID, "unknown input format %d", cfg->in_fmt);
+    if (cfg->decimation < 1 || cfg->decimation > kDdcMaxDecimation)
+        return sdr_fail(SDR_ERR_INVALID, "decimation %d outside 1..%d", cfg->decimation, kDdcMaxDecimation);
+    if (cfg->n_taps < 1 || cfg->n_taps > kDdcMaxTaps) return sdr_fail(SDR_ERR_INVALID, "%d taps outside 1..%d", cfg->n_taps, kDdcMaxTaps);
+    if (cfg->flags) return sdr_fail(SDR_ERR_INVALID, "unknown flags 0x%x", cfg->flags);
+    if (!cfg->taps) return sdr_fail(SDR_ERR_INVALID, "taps is NULL");
+    if (!std::isfinite(cfg->gain)) return sdr_fail(SDR_ERR_INVALID, "gain is not finite");
+    for (int k = 0; k < cfg->n_taps; ++k)
+        if (!std::isfinite(cfg->taps[k])) return sdr_fail(SDR_ERR_INVALID, "tap %d is not finite", k);
+    sdr_ddc* d = new (std::nothrow) sdr_ddc();
+    if (!d) return sdr_fail(SDR_ERR_NOMEM, "host allocation failed");
+    d->engine = e, d->in_fmt = cfg->in_fmt, d->D = cfg->decimation, d->T = cfg->n_taps, d->fcw = cfg->fcw, d->gain = cfg->gain;
+    const size_t hist_bytes = (size_t)(d->T > 1 ? d->T - 1 : 1) * ddc_in_bytes(d->in_fmt);
+    hipError_t err = hipMalloc((void**)&d->taps, (size_t)d->T * sizeof(double));
+    if (err == hipSuccess) err = hipMalloc(&d->hist, hist_bytes);
+    if (err == hipSuccess) err = hipMemcpyAsync(d->taps, cfg->taps, (size_t)d->T * sizeof(double), hipMemcpyHostToDevice, e->stream);
+    if (err == hipSuccess) err = hipMemsetAsync(d->hist, 0, hist_bytes, e->stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);     // (cfg->taps is the caller's again)
+    if (err != hipSuccess) {
+        if (d->taps) (void)hipFree(d->taps);
+        if (d->hist) (void)hipFree(d->hist);
+        delete d;
+        return sdr_fail(SDR_ERR_HIP, "sdr_ddc_create: %s", hipGetErrorString(err));
+    }
+    *out = d;
+    return SDR_OK;
+}
+
+void sdr_ddc_destroy(sdr_engine* e, sdr_ddc* d) {
+    if (!d) return;
+    if (e && sdr_set_device(e) == SDR_OK) (void)hipStreamSynchronize(e->stream);     // (a queued push may still read them)
+    if (d->taps) (void)hipFree(d->taps);
+    if (d->hist) (void)hipFree(d->hist);
+    delete d;
+}
+
+int sdr_ddc_reset(sdr_engine* e, sdr_ddc* d) {
+    if (int rc = sdr_set_device(e)) return rc;
+    if (int rc = ddc_check(e, d)) return rc;
+    const size_t hist_bytes = (size_t)(d->T > 1 ? d->T - 1 : 1) * ddc_in_bytes(d->in_fmt);
+    SDR_HIP(hipMemsetAsync(d->hist, 0, hist_bytes, e->stream));
+    d->n_seen = 0;
+    return SDR_OK;
+}
+
+int sdr_ddc_push(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in, int64_t ring_offset, int64_t* n_out) {
+    return ddc_push_impl(e, d, in, n_in, ring_offset, n_out, true);
+}
+
+int sdr_ddc_push_queue(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in, int64_t ring_offset, int64_t* n_out) {
+    return ddc_push_impl(e, d, in, n_in, ring_offset, n_out, false);
+}
+
+int64_t sdr_ddc_out_count(const sdr_ddc* d, int64_t n_in) {
+    if (!d) return sdr_fail(SDR_ERR_INVALID, "converter is NULL");
+    if (n_in < 0) return sdr_fail(SDR_ERR_INVALID, "negative input count");
+    return ddc_push(d->n_seen, n_in, d->D, d->T).n_out;
+}
+
+}  // extern "C"

@@ -181,6 +181,9 @@ struct sdr_engine {
     int probe_tab_nfft = 0;
     double probe_sumw2 = 0.0;
     std::vector<char> probe_host; // the host image of the result block and the histogram (the target of their download)
+
+    // sdr_ddc_push / _queue (ddc.hip)
+    DevBuf ddc_stage;             // the raw inputs of a push in HBM, read by the converter's kernels behind their copy command on `stream`
 };
 
 int sdr_devbuf_reserve(sdr_engine* e, DevBuf* b, size_t bytes);

@@ -244,6 +244,14 @@ class Bank:
             pass
 
 
+class _Ddc:
+    """Handle of a device-resident down-converter (Engine.ddc_create)."""
+    __slots__ = ("handle", "in_fmt")
+
+    def __init__(self, handle, in_fmt):
+        self.handle, self.in_fmt = handle, in_fmt
+
+
 class Engine:
     def __init__(self, device_id: int = 0):
         self._lib = _lib.load()
@@ -376,6 +384,54 @@ class Engine:
         unchanged until `sync()`."""
         pk, address, n = self._packed_args(packed, n_samples, packing)
         check(self._lib.sdr_iq_upload_packed_queue(self._h, C.byref(pk), address, n, int(ring_offset)))
+
+    # ------------------------------------------------------------------ down-conversion into the ring (signal/downconvert.py)
+    def ddc_create(self, cfg):
+        """A device-resident down-converter (sdr_ddc_create) of a signal.downconvert.DownConverterConfig -> its handle."""
+        taps = np.ascontiguousarray(cfg.taps, dtype=np.float64)
+        c = _lib.DdcCfg(int(cfg.in_fmt), int(cfg.decimation), int(taps.size), 0, int(cfg.fcw), float(cfg.gain),
+                        taps.ctypes.data_as(C.POINTER(C.c_double)))
+        h = C.c_void_p()
+        check(self._lib.sdr_ddc_create(self._h, C.byref(c), C.byref(h)))
+        return _Ddc(h, int(cfg.in_fmt))
+
+    def _ddc_push(self, call, ddc, raw, ring_offset):
+        from .signal.downconvert import input_dtype, input_is_complex
+        if not (isinstance(raw, np.ndarray) and raw.ndim == 1 and raw.flags.c_contiguous and raw.dtype == input_dtype(ddc.in_fmt)):
+            raise ValueError("a push takes a contiguous 1-D array of raw inputs in the converter's input type")
+        n_in = raw.size
+        if input_is_complex(ddc.in_fmt):
+            if n_in & 1:
+                raise ValueError("interleaved IQ needs an even number of elements")
+            n_in >>= 1
+        n_out = C.c_int64(0)
+        status = call(self._h, ddc.handle, raw.ctypes.data, n_in, int(ring_offset), C.byref(n_out))
+        if status:
+            check(status)
+        return n_out.value
+
+    def ddc_push(self, ddc, raw: np.ndarray, ring_offset: int = 0) -> int:
+        """Raw inputs (real: one integer each; complex: interleaved I,Q) through the converter into the ring at ring_offset
+        (sdr_ddc_push, synchronous) -> the outputs written."""
+        return self._ddc_push(self._lib.sdr_ddc_push, ddc, raw, ring_offset)
+
+    def ddc_push_queue(self, ddc, raw: np.ndarray, ring_offset: int = 0) -> int:
+        """ddc_push without the wait (sdr_ddc_push_queue): `raw` stays alive and unchanged until `sync()`."""
+        return self._ddc_push(self._lib.sdr_ddc_push_queue, ddc, raw, ring_offset)
+
+    def ddc_out_count(self, ddc, n_in: int) -> int:
+        n = self._lib.sdr_ddc_out_count(ddc.handle, int(n_in))
+        if n < 0:
+            check(int(n))
+        return int(n)
+
+    def ddc_reset(self, ddc):
+        check(self._lib.sdr_ddc_reset(self._h, ddc.handle))
+
+    def ddc_destroy(self, ddc):
+        if ddc.handle:
+            self._lib.sdr_ddc_destroy(self._h, ddc.handle)
+            ddc.handle = None
 
     def host_alloc(self, n_elements: int, dtype=np.int8) -> np.ndarray:
         """Page-locked host memory as a NumPy array (sdr_host_alloc); `host_free(array)` gives it back -- the array must not

@@ -7,6 +7,11 @@ integers (int8 / int16 I,Q -- 2 or 4 bytes per sample), which is byte for byte w
 Packed recordings (`data_size` 1, 2 or 4 bits per component, several samples to a byte: packing.py; optional keys
 `sample_levels` -- comma-separated, `1 << data_size` integers -- and `bit_order` -- `lsb` / `msb`) are served as `uint8`
 views of their packed bytes, which the engine widens on the device.
+A recording at an intermediate frequency or at a wider band than the channels need -- real-valued ones included (`is_complex`
+empty) -- goes through the device's down-converter (downconvert.py) when the key `decimation` is present (optional keys
+`baseband_shift`, `filter_taps`, `filter_cutoff`, `output_gain`, `output_bits`): the front-end attributes the channels read
+(`samplingFrequency`, `samplesPerMs`, `interFrequency`) are then the RING's, the slabs handed out are raw input, and
+`frontEnd` says how the one becomes the other.
 The reference instead reads 120 ms chunks and inflates every sample to complex128 (16 bytes) before anything
 else touches it (rfsignal.py:58-132).  Only what the hot path's callers use is kept of that class's surface:
 the front-end attributes, `getMilliseconds`, and `readFile` / `readFileBySamples` / `closeFile` /
@@ -19,6 +24,18 @@ import os
 import numpy as np
 
 from .packing import Packing, unpack
+
+
+class FrontEnd:
+    """How a recording's raw input becomes the ring's samples: the down-converter's settings (downconvert.py), its group delay in
+    INPUT samples -- common to all channels; reported, not compensated --, the ring's sample width and the shift in Hz."""
+
+    def __init__(self, config, output_bits: int, shift_hz: float):
+        self.config = config
+        self.decimation = config.decimation
+        self.groupDelay = config.group_delay
+        self.outputBits = int(output_bits)
+        self.shift = float(shift_hz)
 
 
 class RFSignal:
@@ -41,7 +58,10 @@ class RFSignal:
                 raise ValueError(f"bit_order is 'lsb' or 'msb', not {order!r}")
             self.packing = Packing(bits, levels, msb_first=order == "msb")
         self.fileDataType = np.uint8 if bits < 8 else np.int8 if bits == 8 else np.int16
-        if not self.isComplex:
+        self.frontEnd = None                            # recordings that go through the down-converter: FrontEnd
+        if "decimation" in configuration:
+            self._front_end(configuration, bits)
+        if not self.isComplex and self.frontEnd is None:
             raise ValueError("real-valued recordings are not supported: the correlators take I,Q samples")
         self.dtype = np.complex128                      # what a sample IS (the reference's rfSignal.dtype); storage stays integer
         self.samplesPerMs = int(self.samplingFrequency * 1e-3)
@@ -50,6 +70,34 @@ class RFSignal:
         self._map = None
         self._next = 0                                  # samples handed out so far
         self._open = False                              # the reference's `file_id is not None` (readFile keep_open)
+
+    def _front_end(self, configuration, bits: int):
+        """The opt-in keys of a recording that is down-converted and decimated on its way into the ring."""
+        from . import downconvert as dc
+        if self.packing is not None:
+            raise ValueError("packed recordings cannot be down-converted: `decimation` needs data_size 8 or 16")
+        D = int(configuration["decimation"])
+        if not 1 <= D <= dc.MAX_DECIMATION:
+            raise ValueError(f"decimation {D} outside 1..{dc.MAX_DECIMATION}")
+        fs_in, if_in = self.samplingFrequency, self.interFrequency
+        self.inputSamplingFrequency = fs_in
+        self.inputSamplesPerMs = int(fs_in * 1e-3)
+        if self.inputSamplesPerMs % D:
+            raise ValueError(f"a millisecond of {self.inputSamplesPerMs} input samples is not a whole multiple of decimation {D}")
+        shift = float(configuration["baseband_shift"]) if "baseband_shift" in configuration else if_in
+        n_taps = int(configuration["filter_taps"]) if "filter_taps" in configuration else 16 * D + 1
+        cutoff = float(configuration["filter_cutoff"]) if "filter_cutoff" in configuration else 0.45 / D
+        gain = float(configuration["output_gain"]) if "output_gain" in configuration else 1.0
+        out_bits = int(configuration["output_bits"]) if "output_bits" in configuration else bits
+        if out_bits not in (8, 16):
+            raise ValueError(f"output_bits is 8 or 16, not {out_bits}")
+        in_fmt = {(False, 8): dc.IN_R8, (False, 16): dc.IN_R16, (True, 8): dc.IN_CI8, (True, 16): dc.IN_CI16}[(self.isComplex, bits)]
+        config = dc.DownConverterConfig(in_fmt, D, dc.design_lowpass(n_taps, cutoff), dc.frequency_word(shift, fs_in), gain)
+        self.frontEnd = FrontEnd(config, out_bits, shift)
+        # what the channels read is the ring's: its rate, and the carrier's residual offset there
+        self.samplingFrequency = fs_in / D
+        self.interFrequency = if_in - shift
+        self._per_sample = 2 if self.isComplex else 1   # elements of the file per input sample
 
     # ------------------------------------------------------------------ the recording
     def _recording(self) -> np.ndarray:
@@ -64,6 +112,8 @@ class RFSignal:
     @property
     def totalSamples(self) -> int:
         rec = self._recording()
+        if self.frontEnd is not None:                   # (INPUT samples: what `samples` and `getMilliseconds` hand out)
+            return rec.size // self._per_sample
         return rec.size * self.packing.samples_per_byte if self.packing is not None else rec.size // 2
 
     def samples(self, first: int, n_samples: int) -> np.ndarray:
@@ -71,6 +121,8 @@ class RFSignal:
         the packed bytes (which then have to be whole: both numbers multiples of the samples per byte)."""
         rec = self._recording()
         first, n_samples = int(first), int(n_samples)
+        if self.frontEnd is not None:                   # raw input: real recordings hold one element per sample
+            return rec[self._per_sample * first:self._per_sample * (first + n_samples)]
         if self.packing is None:
             return rec[2 * first:2 * (first + n_samples)]
         spb = self.packing.samples_per_byte
@@ -81,6 +133,8 @@ class RFSignal:
     def _complex(self, first: int, n_samples: int) -> np.ndarray:
         """Samples [first, first + n_samples) as complex128, the reference's sample type -- any two numbers: of a packed
         recording the bytes that cover them are unpacked and the samples cut out."""
+        if self.frontEnd is not None and not self.isComplex:
+            return self.samples(first, n_samples).astype(np.float64) + 0j
         if self.packing is None:
             block = self.samples(first, n_samples)
         else:
@@ -114,8 +168,10 @@ class RFSignal:
     # ------------------------------------------------------------------ the reference's call (receiver.py:124)
     def getMilliseconds(self, nbMilliseconds: int = 1, raw: bool = True):
         """Next `nbMilliseconds` of signal.  raw=True (default): interleaved integers (packed bytes) for the device ring;
-        raw=False: complex128 like the reference's RFSignal.getMilliseconds (rfsignal.py:58-88)."""
-        return self.slab(self.samplesPerMs * int(nbMilliseconds), raw)
+        raw=False: complex128 like the reference's RFSignal.getMilliseconds (rfsignal.py:58-88).  Of a recording with a
+        front end: raw INPUT (a real recording's integers one per sample), a millisecond being `inputSamplesPerMs` of them."""
+        per_ms = self.samplesPerMs if self.frontEnd is None else self.inputSamplesPerMs
+        return self.slab(per_ms * int(nbMilliseconds), raw)
 
     # ------------------------------------------------------------------ the reference's file readers (rfsignal.py:92-204)
     def _read(self, n_samples: int, skip: int, keep_open: bool, raw: bool):
@@ -134,7 +190,8 @@ class RFSignal:
 
     def readFile(self, timeLength, skip=0, keep_open=False, raw=False):
         """`timeLength` milliseconds of signal (complex128 like the reference; raw=True: the interleaved integers)."""
-        return self._read(int((timeLength * 1e-3) * self.samplingFrequency), skip, keep_open, raw)
+        fs = self.samplingFrequency if self.frontEnd is None else self.inputSamplingFrequency
+        return self._read(int((timeLength * 1e-3) * fs), skip, keep_open, raw)
 
     def readFileBySamples(self, nb_values, skip=0, keep_open=False, raw=False):
         return self._read(int(nb_values), skip, keep_open, raw)
