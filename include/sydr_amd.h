@@ -638,6 +638,53 @@ int sdr_ddc_push(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in, int64_
 int sdr_ddc_push_queue(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in, int64_t ring_offset, int64_t* n_out);
 int64_t sdr_ddc_out_count(const sdr_ddc* d, int64_t n_in);
 
+/* ------------------------------------------------- pulse blanking and narrow-band excision in front of the ring
+ * An opt-in stage of a converter, between the filter's fp64 output v and the ring's format: a threshold blanker against pulsed
+ * interference (DME, radar, a switching supply) and a frequency-domain excisor with windowed overlap-add against carrier-wave
+ * interferers.  Nothing downstream of the ring learns of it; a converter without it makes the launches and writes the bytes it
+ * always did.  The NumPy form of what follows is sydr_amd/signal/mitigate.py `Statement`; it is the only yardstick.
+ * v_m is the converter's output m = 0, 1, ... since creation or reset (above), v_m = 0 for m < 0.
+ * Blanker (blank_level > 0; blank_lead, blank_hold in 0..1024 samples, taken as 0 without a blanker):
+ *   p_m = re*re + im*im                               (two products, one sum, each rounded)
+ *   t_m = p_m > blank_level * blank_level             (the square formed once, on the host)
+ *   b_m = any t_j with m - blank_hold <= j <= m + blank_lead
+ *   u_m = 0 where b_m, else v_m
+ * Excisor (nfft = N, a power of two in 64..4096; limit[k] >= 0, k < N in FFT order, +inf allowed), hop H = N / 2, periodic Hann
+ * window w[j] = 0.5 - 0.5 cos(2 pi j / N) (sdr_iq_probe's; w[j] + w[j + H] = 1), segment s >= -1 = u[s H .. s H + N):
+ *   A_s = FFT(w * u_s);  P = re^2 + im^2 of A_s[k];  G[k] = 0 where P > limit[k], else 1;  B_s = IFFT(G * A_s)   (1 / N included)
+ *   y_m = B_{q-1}[m - (q-1) H] + B_q[m - q H],  q = floor(m / H)        (y = u without the excisor)
+ * Delay L = (N with the excisor, else 0) + blank_lead: output i of the stream is format(y_{i - L}) and format(0) for i < L, format
+ * being the converter's (cf64 as is, cf32 rounded, integer rings clip(rint), a ci8 ring's bytes sign-flipped).  A push of n_in
+ * inputs writes exactly the outputs the converter alone would (sdr_ddc_out_count unchanged) at the same ring samples; the
+ * constant delay of L ring samples, common to all channels, is reported (sdr_ddc_delay) and not compensated -- as the filter's
+ * group delay.  The tail of a stream comes out when the caller pushes L more zeros; there is no flush call.  The mitigator keeps
+ * the last 2 N - 1 + blank_lead + blank_hold values of v (blank_lead + blank_hold without the excisor) and a segment's transform
+ * is a function of its N inputs alone: what the ring holds does not depend on how the stream was cut into pushes, bit for bit.
+ * Against the statement the device's y differs by at most 16 log2(N) N 2^-53 max|u| per component (two radix-2 transforms
+ * against NumPy's) plus what the converter's own tolerance becomes; a gate is a discontinuity, so a bin or a sample within
+ * that of its limit may fall on either side.
+ * Counters, since creation or reset, functions of the number n of outputs delivered alone (so they do not depend on the cut):
+ *   n_outputs = n;  n_triggers = #{0 <= j < n - L : t_j};  n_blanked = #{0 <= m < n - L : b_m};
+ *   n_segments = #{s >= -1 : s H + N <= n - L} (finished segments);  bins[k] = #{finished segments with G[k] = 0};
+ *   n_bins_excised = sum of bins.
+ * sdr_ddc_mitigate attaches a mitigator (cfg is copied, limit included) or, with cfg == NULL, detaches it; either only while the
+ * converter has seen no input since creation or reset (SDR_ERR_STATE otherwise).  sdr_ddc_reset clears the mitigator's state and
+ * counters too.  sdr_ddc_mitigation_stats waits for the engine's stream; SDR_ERR_STATE without a mitigator.
+ * SDR_ERR_INVALID: nfft neither 0 nor a power of two in 64..4096, blank_lead or blank_hold outside 0..1024, a negative or NaN
+ * limit or blank_level, nfft > 0 with limit == NULL, non-zero flags, both stages off (nfft = 0 and blank_level = 0).  A refused
+ * call changes nothing.  sdr_prof_enable scopes: "mit_blank_kernel", "mit_excise_kernel", "mit_combine_kernel". */
+typedef struct sdr_mit_cfg {
+    int32_t nfft, blank_lead, blank_hold, flags; /* flags: 0 */
+    double blank_level;
+    const double* limit;                         /* [nfft]; copied by sdr_ddc_mitigate */
+} sdr_mit_cfg;
+typedef struct sdr_mit_stats {
+    int64_t n_outputs, n_triggers, n_blanked, n_segments, n_bins_excised;
+} sdr_mit_stats;
+int sdr_ddc_mitigate(sdr_engine* e, sdr_ddc* d, const sdr_mit_cfg* cfg);   /* NULL detaches */
+int64_t sdr_ddc_delay(const sdr_ddc* d);                                   /* L; 0 without a mitigator */
+int sdr_ddc_mitigation_stats(sdr_engine* e, sdr_ddc* d, sdr_mit_stats* stats, int64_t* bins /* nullable [nfft] */);
+
 /* ------------------------------------------------- what the ring holds: levels, histogram, spectrum
  * The first look at a new recording and the look a running receiver keeps taking at its front end -- are the bits used, is
  * anything on the rails, is there a DC offset or an I/Q imbalance, is the level table of a packed file the right one, is there

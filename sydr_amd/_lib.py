@@ -78,6 +78,18 @@ class DdcCfg(C.Structure):
 DDC_IN_R8, DDC_IN_R16, DDC_IN_CI8, DDC_IN_CI16 = 0, 1, 2, 3
 
 
+class MitCfg(C.Structure):
+    """sdr_mit_cfg (include/sydr_amd.h): the blanker's level, lead and hold, the excisor's transform length and limits."""
+    _fields_ = [("nfft", C.c_int32), ("blank_lead", C.c_int32), ("blank_hold", C.c_int32), ("flags", C.c_int32),
+                ("blank_level", C.c_double), ("limit", C.POINTER(C.c_double))]
+
+
+class MitStats(C.Structure):
+    """sdr_mit_stats (include/sydr_amd.h): a mitigator's counters since creation or reset."""
+    _fields_ = [("n_outputs", C.c_int64), ("n_triggers", C.c_int64), ("n_blanked", C.c_int64), ("n_segments", C.c_int64),
+                ("n_bins_excised", C.c_int64)]
+
+
 class SynthSat(C.Structure):
     _fields_ = [("prn", C.c_int32), ("flags", C.c_int32), ("doppler_hz", C.c_double),
                 ("code_phase", C.c_double), ("carrier_phase", C.c_double), ("amplitude", C.c_double)]
@@ -228,6 +240,9 @@ _PROTOTYPES = {
     "sdr_ddc_push": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
     "sdr_ddc_push_queue": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
     "sdr_ddc_out_count": (C.c_int64, [_VP, C.c_int64]),
+    "sdr_ddc_mitigate": (C.c_int, [_VP, _VP, C.POINTER(MitCfg)]),
+    "sdr_ddc_delay": (C.c_int64, [_VP]),
+    "sdr_ddc_mitigation_stats": (C.c_int, [_VP, _VP, C.POINTER(MitStats), _VP]),
     "sdr_tick_server_stats": (C.c_int, [_VP, C.POINTER(C.c_int64)]),
     "sdr_tick_server_phases": (C.c_int, [_VP, C.POINTER(C.c_double)]),
     "sdr_tick_server_tracker_phases": (C.c_int, [_VP, C.POINTER(C.c_double)]),

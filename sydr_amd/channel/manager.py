@@ -82,6 +82,8 @@ class ChannelManager:
             self._upload_block = self._upload_block_converted
         self.sharedBuffer = CircularBuffer(buffersize, rfSignal.dtype, engine=engine, fmt=fmt)
         self._ddc = engine.ddc_create(self._frontEnd.config) if self._frontEnd is not None else None
+        if self._ddc is not None and self._frontEnd.mitigation is not None:
+            engine.ddc_mitigate(self._ddc, self._frontEnd.mitigation)   # (pulse blanker / excisor: signal/mitigate.py)
         self.resultQueue = None
         self.keepCorrelationMap = keepCorrelationMap
         self._slots = 0
@@ -484,6 +486,15 @@ class ChannelManager:
         reads it; the channels are not touched."""
         n = int(round(self._samples_per_ms * nbMilliseconds))
         out = self.sharedBuffer.probe(n, nfft=nfft, fs=self.rfSignal.samplingFrequency if nfft else None)
+        self._pending = False         # (the call waited for the engine's stream: a queued slab is in the ring)
+        return out
+
+    def mitigationStats(self):
+        """The counters of the front end's pulse blanker and excisor since the recording began (signal.mitigate.Stats), or
+        None when the recording has none.  Waits for a slab that is only queued."""
+        if self._ddc is None or self._frontEnd.mitigation is None:
+            return None
+        out = self.engine.ddc_mitigation_stats(self._ddc)
         self._pending = False         # (the call waited for the engine's stream: a queued slab is in the ring)
         return out
 

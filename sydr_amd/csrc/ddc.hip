@@ -4,8 +4,12 @@
 // sydr_amd/signal/downconvert.py: the phasor is a pure function of the absolute input index, every output is the same T
 // products added in the same order whatever tile or push it falls into -- so the ring does not depend on how the stream was
 // cut into pushes, bit for bit.
+// A converter with a mitigator attached (sdr_ddc_mitigate: pulse blanker, narrow-band excisor -- mitigate.hip) has the same
+// ddc_kernel write its outputs as cf64 into the mitigator's work buffer in place of the ring; without one a push makes the
+// launches it always made.
 #include "engine_internal.h"
 #include "ddc_tiles.h"
+#include "mitigate.h"
 #include "sincos_reduced.h"
 
 #include <cmath>
@@ -21,6 +25,7 @@ struct sdr_ddc {
     double* taps = nullptr;      // device [T]
     void* hist = nullptr;        // device [max(T-1, 1)] raw inputs, oldest first
     int64_t n_seen = 0;          // inputs since creation / reset
+    Mitigator* mit = nullptr;    // between the filter's output and the ring's format (sdr_ddc_mitigate), or none
 };
 
 static inline size_t ddc_in_bytes(int in_fmt) {
@@ -148,6 +153,14 @@ static int ddc_push_impl(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in
     // one copy command brings the raw inputs into the engine's staging buffer in HBM (no kernel reads host memory), the
     // kernels follow it on the same stream -- whose order is all the guard the buffer and the history need
     if (int rc = sdr_devbuf_reserve(e, &e->ddc_stage, bytes)) return rc;
+    // with a mitigator the kernel's destination is its linear cf64 work buffer, the first output behind the kept state
+    void* dst = e->iq;
+    int dst_fmt = e->iq_fmt;
+    int64_t dst_off = off, dst_cap = cap;
+    if (d->mit && push.n_out > 0) {
+        if (int rc = mit_push_begin(e, d->mit, push.m_first, push.n_out, &dst, &dst_off, &dst_cap)) return rc;
+        dst_fmt = SDR_FMT_CF64;
+    }
     SDR_HIP(hipMemcpyAsync(e->ddc_stage.ptr, in, bytes, hipMemcpyHostToDevice, e->stream));
     if (push.n_out > 0) {
         sdr_iq_mark_written(e, off, push.n_out);
@@ -156,8 +169,10 @@ static int ddc_push_impl(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in
         const size_t lds = (size_t)((tile - 1) * d->D + d->T) * sizeof(double2);
         ProfScope ps(e, "ddc_kernel");
         hipLaunchKernelGGL(ddc_kernel, dim3((unsigned)tiles), dim3(kDdcThreads), lds, e->stream, (const void*)e->ddc_stage.ptr,
-                           (const void*)d->hist, (const double*)d->taps, e->iq, push, tile, d->in_fmt, e->iq_fmt, d->fcw, d->gain, off, cap);
+                           (const void*)d->hist, (const double*)d->taps, dst, push, tile, d->in_fmt, dst_fmt, d->fcw, d->gain, dst_off, dst_cap);
     }
+    if (d->mit && push.n_out > 0)
+        if (int rc = mit_push_finish(e, d->mit, push.m_first, push.n_out, off)) return rc;
     if (d->T > 1) {
         ProfScope ps(e, "ddc_history_kernel");
         hipLaunchKernelGGL(ddc_history_kernel, dim3(1), dim3(kDdcMaxTaps), 0, e->stream, (const void*)e->ddc_stage.ptr, d->hist, n_in, d->T,
@@ -208,6 +223,7 @@ void sdr_ddc_destroy(sdr_engine* e, sdr_ddc* d) {
     if (e && sdr_set_device(e) == SDR_OK) (void)hipStreamSynchronize(e->stream);     // (a queued push may still read them)
     if (d->taps) (void)hipFree(d->taps);
     if (d->hist) (void)hipFree(d->hist);
+    mit_destroy(nullptr, d->mit);
     delete d;
 }
 
@@ -216,6 +232,8 @@ int sdr_ddc_reset(sdr_engine* e, sdr_ddc* d) {
     if (int rc = ddc_check(e, d)) return rc;
     const size_t hist_bytes = (size_t)(d->T > 1 ? d->T - 1 : 1) * ddc_in_bytes(d->in_fmt);
     SDR_HIP(hipMemsetAsync(d->hist, 0, hist_bytes, e->stream));
+    if (d->mit)
+        if (int rc = mit_reset(e, d->mit)) return rc;
     d->n_seen = 0;
     return SDR_OK;
 }
@@ -232,6 +250,31 @@ int64_t sdr_ddc_out_count(const sdr_ddc* d, int64_t n_in) {
     if (!d) return sdr_fail(SDR_ERR_INVALID, "converter is NULL");
     if (n_in < 0) return sdr_fail(SDR_ERR_INVALID, "negative input count");
     return ddc_push(d->n_seen, n_in, d->D, d->T).n_out;
+}
+
+int sdr_ddc_mitigate(sdr_engine* e, sdr_ddc* d, const sdr_mit_cfg* cfg) {
+    if (int rc = sdr_set_device(e)) return rc;
+    if (int rc = ddc_check(e, d)) return rc;
+    if (d->n_seen != 0) return sdr_fail(SDR_ERR_STATE, "the converter has seen %lld inputs since its creation or reset", (long long)d->n_seen);
+    Mitigator* fresh = nullptr;
+    if (cfg)
+        if (int rc = mit_create(e, cfg, &fresh)) return rc;
+    mit_destroy(e, d->mit);
+    d->mit = fresh;
+    return SDR_OK;
+}
+
+int64_t sdr_ddc_delay(const sdr_ddc* d) {
+    if (!d) return sdr_fail(SDR_ERR_INVALID, "converter is NULL");
+    return d->mit ? mit_delay_of(d->mit) : 0;
+}
+
+int sdr_ddc_mitigation_stats(sdr_engine* e, sdr_ddc* d, sdr_mit_stats* stats, int64_t* bins) {
+    if (int rc = sdr_set_device(e)) return rc;
+    if (int rc = ddc_check(e, d)) return rc;
+    if (!stats) return sdr_fail(SDR_ERR_INVALID, "no result block for the counters");
+    if (!d->mit) return sdr_fail(SDR_ERR_STATE, "the converter has no mitigator");
+    return mit_stats(e, d->mit, ddc_ceil_div(d->n_seen, d->D), stats, bins);
 }
 
 }  // extern "C"

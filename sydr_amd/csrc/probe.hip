@@ -29,6 +29,7 @@
 #include <limits>
 
 #include "correlator.h"
+#include "fft_lds.h"
 #include "probe_window.h"
 
 namespace {
@@ -302,7 +303,7 @@ __global__ __launch_bounds__(kThreads) void probe_moments_finish_kernel(const do
     *dst = t;
 }
 
-constexpr int kMaxNfft = 4096, kMinNfft = 64;
+constexpr int kMaxNfft = kFftLdsMax, kMinNfft = kFftLdsMin;
 constexpr int kPsdRegs = kMaxNfft / kThreads;   // LDS positions of a lane: tid + 256 * r
 
 template <int FMT>
@@ -313,7 +314,6 @@ __global__ __launch_bounds__(kThreads) void probe_psd_kernel(const void* __restr
     extern __shared__ __attribute__((aligned(16))) char probe_lds[];
     double2* x = reinterpret_cast<double2*>(probe_lds);
     const int tid = threadIdx.x;
-    const int half = nfft >> 1;
     double acc[kPsdRegs];
 #pragma unroll
     for (int r = 0; r < kPsdRegs; ++r) acc[r] = 0.0;
@@ -327,20 +327,7 @@ __global__ __launch_bounds__(kThreads) void probe_psd_kernel(const void* __restr
             x[j] = make_double2(w * xr, w * xi);
         }
         __syncthreads();
-        // decimation in frequency, in place: X[k] ends at position bitrev(k)
-#pragma unroll 1
-        for (int h = half, step = 1; h >= 1; h >>= 1, step <<= 1) {
-            for (int t = tid; t < half; t += kThreads) {
-                const int k = t & (h - 1);
-                const int i = ((t - k) << 1) + k;
-                const double2 a = x[i], b = x[i + h];
-                const double2 w = tw[k * step];
-                const double dr = a.x - b.x, di = a.y - b.y;
-                x[i] = make_double2(a.x + b.x, a.y + b.y);
-                x[i + h] = make_double2(__builtin_fma(-di, w.y, dr * w.x), __builtin_fma(di, w.x, dr * w.y));
-            }
-            __syncthreads();
-        }
+        fft_lds_forward<kThreads>(x, nfft, tw, tid);   // X[k] ends at position bitrev(k)
 #pragma unroll
         for (int r = 0; r < kPsdRegs; ++r) {
             const int j = tid + kThreads * r;
@@ -377,17 +364,7 @@ int probe_tables(sdr_engine* e, int nfft) {
     const size_t b_tw = (size_t)(nfft / 2) * sizeof(double2), b_win = (size_t)nfft * sizeof(double);
     if (int rc = sdr_devbuf_reserve(e, &e->probe_tab, b_tw + b_win)) return rc;
     std::vector<double> host(nfft + nfft);
-    for (int k = 0; k < nfft / 2; ++k) {
-        const double a = 2.0 * M_PI * (double)k / (double)nfft;
-        host[2 * k] = std::cos(a);
-        host[2 * k + 1] = -std::sin(a);
-    }
-    double sumw2 = 0.0;
-    for (int j = 0; j < nfft; ++j) {
-        const double w = 0.5 - 0.5 * std::cos(2.0 * M_PI * (double)j / (double)nfft);
-        host[nfft + j] = w;
-        sumw2 += w * w;
-    }
+    const double sumw2 = fft_lds_fill_tables(nfft, host.data());
     SDR_HIP(hipStreamSynchronize(e->stream));
     SDR_HIP(hipMemcpy(e->probe_tab.ptr, host.data(), b_tw + b_win, hipMemcpyHostToDevice));
     e->probe_sumw2 = sumw2;

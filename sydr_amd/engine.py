@@ -246,10 +246,11 @@ class Bank:
 
 class _Ddc:
     """Handle of a device-resident down-converter (Engine.ddc_create)."""
-    __slots__ = ("handle", "in_fmt")
+    __slots__ = ("handle", "in_fmt", "nfft")
 
     def __init__(self, handle, in_fmt):
         self.handle, self.in_fmt = handle, in_fmt
+        self.nfft = 0                 # of the attached mitigator's excisor (Engine.ddc_mitigate)
 
 
 class Engine:
@@ -427,6 +428,34 @@ class Engine:
 
     def ddc_reset(self, ddc):
         check(self._lib.sdr_ddc_reset(self._h, ddc.handle))
+
+    def ddc_mitigate(self, ddc, cfg):
+        """Attach a pulse blanker / narrow-band excisor (sdr_ddc_mitigate) of a signal.mitigate.MitigationConfig to the
+        converter, or detach it (cfg None); only before the converter's first input or after a reset."""
+        if cfg is None:
+            check(self._lib.sdr_ddc_mitigate(self._h, ddc.handle, None))
+            ddc.nfft = 0
+            return
+        limit = np.ascontiguousarray(cfg.limit, dtype=np.float64) if cfg.nfft else None
+        c = _lib.MitCfg(int(cfg.nfft), int(cfg.blank_lead), int(cfg.blank_hold), 0, float(cfg.blank_level),
+                        limit.ctypes.data_as(C.POINTER(C.c_double)) if limit is not None else None)
+        check(self._lib.sdr_ddc_mitigate(self._h, ddc.handle, C.byref(c)))
+        ddc.nfft = int(cfg.nfft)
+
+    def ddc_delay(self, ddc) -> int:
+        """The attached mitigator's delay L in ring samples (sdr_ddc_delay); 0 without one."""
+        n = self._lib.sdr_ddc_delay(ddc.handle)
+        if n < 0:
+            check(int(n))
+        return int(n)
+
+    def ddc_mitigation_stats(self, ddc):
+        """The mitigator's counters (sdr_ddc_mitigation_stats) -> signal.mitigate.Stats."""
+        from .signal.mitigate import Stats
+        st = _lib.MitStats()
+        bins = np.zeros(ddc.nfft, dtype=np.int64)
+        check(self._lib.sdr_ddc_mitigation_stats(self._h, ddc.handle, C.byref(st), bins.ctypes.data if ddc.nfft else None))
+        return Stats(st.n_outputs, st.n_triggers, st.n_blanked, st.n_segments, st.n_bins_excised, bins)
 
     def ddc_destroy(self, ddc):
         if ddc.handle:

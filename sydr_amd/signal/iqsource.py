@@ -12,6 +12,11 @@ empty) -- goes through the device's down-converter (downconvert.py) when the key
 `baseband_shift`, `filter_taps`, `filter_cutoff`, `output_gain`, `output_bits`): the front-end attributes the channels read
 (`samplingFrequency`, `samplesPerMs`, `interFrequency`) are then the RING's, the slabs handed out are raw input, and
 `frontEnd` says how the one becomes the other.
+Such a recording may also ask for interference mitigation between the converter and the ring (mitigate.py; keys
+`blanking_factor` with `blanking_lead`, `blanking_hold`, and `excision_nfft` with `excision_margin_db`; `calibration_ms`):
+the blanker's level and the excisor's limits are measured once, on the host, over the converter's output of the recording's
+first `calibration_ms` milliseconds.  `decimation = 1` with `filter_taps = 1` is the identity converter for a plain complex
+recording.
 The reference instead reads 120 ms chunks and inflates every sample to complex128 (16 bytes) before anything
 else touches it (rfsignal.py:58-132).  Only what the hot path's callers use is kept of that class's surface:
 the front-end attributes, `getMilliseconds`, and `readFile` / `readFileBySamples` / `closeFile` /
@@ -26,16 +31,35 @@ import numpy as np
 from .packing import Packing, unpack
 
 
+MITIGATION_KEYS = ("blanking_factor", "blanking_lead", "blanking_hold", "excision_nfft", "excision_margin_db", "calibration_ms")
+
+
 class FrontEnd:
     """How a recording's raw input becomes the ring's samples: the down-converter's settings (downconvert.py), its group delay in
     INPUT samples -- common to all channels; reported, not compensated --, the ring's sample width and the shift in Hz."""
 
-    def __init__(self, config, output_bits: int, shift_hz: float):
+    def __init__(self, config, output_bits: int, shift_hz: float, calibrate=None):
         self.config = config
         self.decimation = config.decimation
         self.groupDelay = config.group_delay
         self.outputBits = int(output_bits)
         self.shift = float(shift_hz)
+        self._calibrate = calibrate                     # () -> mitigate.MitigationConfig, run when first asked for
+        self._mitigation = None
+
+    @property
+    def mitigation(self):
+        """The pulse blanker's and excisor's settings (mitigate.MitigationConfig) or None: measured on the recording's
+        first milliseconds when first asked for, then kept."""
+        if self._calibrate is not None:
+            self._mitigation, self._calibrate = self._calibrate(), None
+        return self._mitigation
+
+    @property
+    def delay(self) -> int:
+        """The mitigator's delay in RING samples -- common to all channels; reported, not compensated."""
+        m = self.mitigation
+        return m.delay if m is not None else 0
 
 
 class RFSignal:
@@ -61,6 +85,10 @@ class RFSignal:
         self.frontEnd = None                            # recordings that go through the down-converter: FrontEnd
         if "decimation" in configuration:
             self._front_end(configuration, bits)
+        else:
+            for key in MITIGATION_KEYS:
+                if key in configuration:
+                    raise ValueError(f"`{key}` needs a front end: set `decimation` (1 with `filter_taps = 1` converts nothing)")
         if not self.isComplex and self.frontEnd is None:
             raise ValueError("real-valued recordings are not supported: the correlators take I,Q samples")
         self.dtype = np.complex128                      # what a sample IS (the reference's rfSignal.dtype); storage stays integer
@@ -93,11 +121,42 @@ class RFSignal:
             raise ValueError(f"output_bits is 8 or 16, not {out_bits}")
         in_fmt = {(False, 8): dc.IN_R8, (False, 16): dc.IN_R16, (True, 8): dc.IN_CI8, (True, 16): dc.IN_CI16}[(self.isComplex, bits)]
         config = dc.DownConverterConfig(in_fmt, D, dc.design_lowpass(n_taps, cutoff), dc.frequency_word(shift, fs_in), gain)
-        self.frontEnd = FrontEnd(config, out_bits, shift)
+        self.frontEnd = FrontEnd(config, out_bits, shift, self._mitigation_keys(configuration, config))
         # what the channels read is the ring's: its rate, and the carrier's residual offset there
         self.samplingFrequency = fs_in / D
         self.interFrequency = if_in - shift
         self._per_sample = 2 if self.isComplex else 1   # elements of the file per input sample
+
+    def _mitigation_keys(self, configuration, config):
+        """The opt-in mitigation keys -> the calibration to run when the front end's `mitigation` is first asked for (None
+        without `blanking_factor` and `excision_nfft`).  Everything but the measurement is checked here."""
+        from . import mitigate as mt
+        factor = float(configuration["blanking_factor"]) if "blanking_factor" in configuration else None
+        nfft = int(configuration["excision_nfft"]) if "excision_nfft" in configuration else 0
+        if factor is None and not nfft:
+            for key in MITIGATION_KEYS:
+                if key in configuration:
+                    raise ValueError(f"`{key}` without `blanking_factor` or `excision_nfft`")
+            return None
+        lead = int(configuration["blanking_lead"]) if "blanking_lead" in configuration else 0
+        hold = int(configuration["blanking_hold"]) if "blanking_hold" in configuration else 0
+        margin = float(configuration["excision_margin_db"]) if "excision_margin_db" in configuration else 10.0
+        ms = int(configuration["calibration_ms"]) if "calibration_ms" in configuration else 8
+        if factor is not None and not factor > 0.0:
+            raise ValueError("blanking_factor is a positive multiple of the noise amplitude")
+        if ms < 1:
+            raise ValueError("calibration_ms is at least 1")
+        # (the ranges of nfft, lead and hold: MitigationConfig's own checks, on a stand-in that needs no measurement)
+        mt.MitigationConfig(1.0 if factor is not None else 0.0, lead, hold, nfft, np.full(nfft, np.inf) if nfft else None)
+
+        def calibrate():
+            from . import downconvert as dc
+            n_in = min(ms * self.inputSamplesPerMs, self.totalSamples)
+            v = dc.statement(config, [self.samples(0, n_in)])
+            level = mt.blanking_level(v, factor) if factor is not None else 0.0
+            limit = mt.excision_limits(v, nfft, margin) if nfft else None
+            return mt.MitigationConfig(level, lead, hold, nfft, limit)
+        return calibrate
 
     # ------------------------------------------------------------------ the recording
     def _recording(self) -> np.ndarray:
