@@ -1,6 +1,8 @@
 """Randomised GPU-vs-oracle stress of PCPS acquisition: arbitrary code lengths in samples (four-step, per-pass and
 generic-radix transforms), IF, Doppler grids, coherent / non-coherent integrations, present and absent satellites.
-Peak indices must be identical, maps within 1e-9 of the map maximum.  Usage: python tests/stress_pcps.py [rounds] [seed]"""
+Peak indices must be identical, maps within 1e-9 of the map maximum.  Every third round (one of those with a single
+block) asks again without the map -- the map-free sweeps, or the 10 MHz kernel -- for the same indices and the oracle's
+ratio.  Usage: python tests/stress_pcps.py [rounds] [seed]"""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -40,6 +42,9 @@ def run(rounds, seed, eng=None):
             pb, pc, pr, cmap = eng.pcps(np.arange(3), start, fs, if_hz, drange, dstep, coh, noncoh, want_map=True)
         except SdrError as e:     # (no size is refused any more: unfactorable lengths take the chirp-z path)
             raise AssertionError(f"n_code={n_code}: {e}")
+        # the same request for indices and ratio only: three PRNs reach the map-free sweeps (any four-step length) and
+        # the fused search at n_code = 10000 with 11 bins or more, never a round of the fused sweep
+        free = eng.pcps(np.arange(3), start, fs, if_hz, drange, dstep, coh, noncoh) if r % 3 == 1 else None
         spc = round(fs / orc.CODE_RATE)
         x = rf[start:start + n_code * coh * noncoh].reshape(1, -1)
         for s, p in enumerate(prns):
@@ -48,6 +53,11 @@ def run(rounds, seed, eng=None):
             err = float(np.max(np.abs(cmap[s] - m)) / m.max())
             worst = max(worst, err)
             ok = peak == [int(pb[s]), int(pc[s])] and abs(ratio - pr[s]) <= 1e-9 * ratio and err <= 1e-9
+            if ok and free is not None and not (int(free[0][s]) == int(pb[s]) and int(free[1][s]) == int(pc[s])
+                                                and abs(ratio - free[2][s]) <= 1e-9 * ratio):
+                raise AssertionError(str(dict(round=r, n_code=n_code, prn=p, if_hz=if_hz, drange=drange, dstep=dstep, start=start,
+                                              without_map=(int(free[0][s]), int(free[1][s]), float(free[2][s])),
+                                              with_map=(int(pb[s]), int(pc[s]), float(pr[s])), want=(peak, ratio))))
             if not ok:
                 raise AssertionError(str(dict(round=r, n_code=n_code, prn=p, coh=coh, noncoh=noncoh, if_hz=if_hz, drange=drange,
                                               dstep=dstep, start=start, got=(int(pb[s]), int(pc[s]), float(pr[s])),
