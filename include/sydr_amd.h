@@ -638,6 +638,27 @@ int sdr_ddc_push(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in, int64_
 int sdr_ddc_push_queue(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in, int64_t ring_offset, int64_t* n_out);
 int64_t sdr_ddc_out_count(const sdr_ddc* d, int64_t n_in);
 
+/* ------------------------------------------------- rational-rate resampling in the converter (interpolate by L, decimate by M)
+ * sdr_ddc_create_rational makes a converter that moves a recording between rates whose ratio is L / M: a 16.368 MHz recording
+ * enters the ring at 12 MHz with L / M = 250 / 341.  cfg->decimation is M, cfg->n_taps is T, the length of the prototype filter
+ * h[0..T-1] at the UP-SAMPLED rate (L times the input's); everything else of cfg is as above.  The mixer is unchanged: p_j, t_j and
+ * z_j are functions of the INPUT index j alone.  For output m = 0, 1, ...:
+ *   u = m * M      q = u div L      p = u mod L      K_p = ceil((T - p) / L)   (0 when p >= T)
+ *   v_m = gain * sum_{k < K_p} h[p + k L] * z_{q - k}   (fp64; k ascending, product then sum, no contraction; z_j = 0 for j < 0)
+ * -- zero-stuffing by L, the filter, every M-th sample kept, of which only the non-zero products are formed, in a fixed order;
+ * K_p = 0 gives gain * 0.0.  A push of n_in inputs whose first has index N writes exactly the outputs m with
+ * N L <= m M < (N + n_in) L (that is N <= q_m < N + n_in): sdr_ddc_out_count = ceil((N + n_in) L / M) - ceil(N L / M), in host
+ * arithmetic.  The history is the last ceil(T / L) - 1 RAW inputs; the ring does not depend on how the stream was cut into pushes,
+ * bit for bit.  The group delay of a symmetric prototype is (T - 1) / (2 L) input samples = (T - 1) / (2 M) output samples.
+ * Limits: L in 1..1024, M in 1..1024 with M <= 64 L, T in 1..32768 with ceil(T / L) <= 512 (SDR_ERR_INVALID otherwise, on top of
+ * sdr_ddc_create's causes).  interpolation == 1 IS sdr_ddc_create(e, cfg, out): the same limits, kernels, launches and bytes.
+ * Every other sdr_ddc_* call takes the handle as it takes sdr_ddc_create's -- reset, push, push_queue, out_count, destroy, and
+ * sdr_ddc_mitigate / _delay / _mitigation_stats below, the mitigator sitting on the stream v_m.  A push that would take
+ * (N + n_in) * L to 2^62 is refused with SDR_ERR_RANGE (sdr_ddc_out_count returns it too); a refused call changes nothing.
+ * sdr_prof_enable scopes of a converter with L > 1: "resample_kernel", "ddc_history_kernel" (the integer converter's, saving
+ * ceil(T / L) - 1 inputs), "call_ddc_push". */
+int sdr_ddc_create_rational(sdr_engine* e, const sdr_ddc_cfg* cfg, int interpolation, sdr_ddc** out);
+
 /* ------------------------------------------------- pulse blanking and narrow-band excision in front of the ring
  * An opt-in stage of a converter, between the filter's fp64 output v and the ring's format: a threshold blanker against pulsed
  * interference (DME, radar, a switching supply) and a frequency-domain excisor with windowed overlap-add against carrier-wave

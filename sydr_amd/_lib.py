@@ -235,6 +235,7 @@ _PROTOTYPES = {
     "sdr_iq_upload_packed_begin": (C.c_int, [_VP, C.POINTER(IqPacking), _VP, C.c_int64, C.c_int64]),
     "sdr_iq_upload_packed_queue": (C.c_int, [_VP, C.POINTER(IqPacking), _VP, C.c_int64, C.c_int64]),
     "sdr_ddc_create": (C.c_int, [_VP, C.POINTER(DdcCfg), C.POINTER(_VP)]),
+    "sdr_ddc_create_rational": (C.c_int, [_VP, C.POINTER(DdcCfg), C.c_int, C.POINTER(_VP)]),
     "sdr_ddc_destroy": (None, [_VP, _VP]),
     "sdr_ddc_reset": (C.c_int, [_VP, _VP]),
     "sdr_ddc_push": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),

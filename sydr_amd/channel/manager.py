@@ -404,16 +404,17 @@ class ChannelManager:
     def _addNewRFData_converted(self, data):
         """addNewRFData of a recording with a front end: `data` is raw INPUT (rfSignal.getMilliseconds), which the device's
         down-converter mixes, filters and decimates into the ring -- queued on the engine's stream, ordered ahead of the tick's
-        launch.  The ring advances by the outputs: n_in / D.  Nothing is parked for the tick's own launch or a resident tick
-        server (those pull the ring's own bytes), and there is no read-ahead over such a recording."""
+        launch.  The ring advances by the outputs: n_in L / D (L = 1 without `interpolation`).  Nothing is parked for the tick's
+        own launch or a resident tick server (those pull the ring's own bytes), and there is no read-ahead over such a recording."""
         if self._pending:
             self._flush_pending()
         ring = self.sharedBuffer
         data, n_in = self._raw_input(data)
-        D = self._frontEnd.decimation
-        if n_in == 0 or n_in % D:
-            raise ValueError(f"a slab of {n_in} input samples is not a whole multiple of decimation {D}")
-        count = n_in // D
+        D, L = self._frontEnd.decimation, self._frontEnd.interpolation
+        if n_in == 0 or n_in * L % D:
+            raise ValueError(f"a slab of {n_in} input samples" + (f" times interpolation {L}" if L != 1 else "")
+                             + f" is not a whole multiple of decimation {D}")
+        count = n_in * L // D
         if ring.maxSize % count:
             raise ValueError("Data shift need to be a multiple from the max buffer size.")
         if ring.full and (self._unread_max is None or self._unread_max + count > ring.maxSize):

@@ -7,55 +7,18 @@
 // A converter with a mitigator attached (sdr_ddc_mitigate: pulse blanker, narrow-band excisor -- mitigate.hip) has the same
 // ddc_kernel write its outputs as cf64 into the mitigator's work buffer in place of the ring; without one a push makes the
 // launches it always made.
+// A converter made by sdr_ddc_create_rational with interpolation L > 1 keeps its handle here and its kernels in resample.hip.
 #include "engine_internal.h"
+#include "ddc_handle.h"
 #include "ddc_tiles.h"
 #include "mitigate.h"
+#include "resample_tiles.h"
 #include "sincos_reduced.h"
 
 #include <cmath>
 #include <new>
 
 using namespace sdr;
-
-struct sdr_ddc {
-    sdr_engine* engine = nullptr;
-    int in_fmt = 0, D = 1, T = 1;
-    uint64_t fcw = 0;
-    double gain = 1.0;
-    double* taps = nullptr;      // device [T]
-    void* hist = nullptr;        // device [max(T-1, 1)] raw inputs, oldest first
-    int64_t n_seen = 0;          // inputs since creation / reset
-    Mitigator* mit = nullptr;    // between the filter's output and the ring's format (sdr_ddc_mitigate), or none
-};
-
-static inline size_t ddc_in_bytes(int in_fmt) {
-    switch (in_fmt) {
-        case SDR_DDC_IN_R8: return 1;
-        case SDR_DDC_IN_R16: return 2;
-        case SDR_DDC_IN_CI8: return 2;
-        case SDR_DDC_IN_CI16: return 4;
-    }
-    return 0;
-}
-
-__device__ __forceinline__ void ddc_load(const void* __restrict__ p, int64_t i, int in_fmt, double* re, double* im) {
-    switch (in_fmt) {
-        case SDR_DDC_IN_R8: *re = (double)((const int8_t*)p)[i], *im = 0.0; break;
-        case SDR_DDC_IN_R16: *re = (double)((const int16_t*)p)[i], *im = 0.0; break;
-        case SDR_DDC_IN_CI8: {
-            const uint16_t w = ((const uint16_t*)p)[i];
-            *re = (double)(int8_t)(w & 0xff), *im = (double)(int8_t)(w >> 8);
-            break;
-        }
-        default: {
-            const uint32_t w = ((const uint32_t*)p)[i];
-            *re = (double)(int16_t)(w & 0xffff), *im = (double)(int16_t)(w >> 16);
-            break;
-        }
-    }
-}
-
-__device__ __forceinline__ double ddc_clip_rint(double v, double lim) { return fmin(fmax(rint(v), -lim), lim); }
 
 // One workgroup per tile of outputs (ddc_tiles.h).  Phase 1: the tile's inputs, each mixed once, into LDS as fp64 complex.
 // Phase 2: a lane per output, the taps by wave-uniform (scalar) loads, k ascending, product then sum (no contraction: the
@@ -128,15 +91,16 @@ __global__ __launch_bounds__(kDdcMaxTaps) void ddc_history_kernel(const void* __
     }
 }
 
-static int ddc_check(sdr_engine* e, const sdr_ddc* d) {
-    if (!d) return sdr_fail(SDR_ERR_INVALID, "converter is NULL");
-    if (d->engine != e) return sdr_fail(SDR_ERR_INVALID, "the converter belongs to another engine");
-    return SDR_OK;
+void sdr::ddc_history_launch(sdr_engine* e, sdr_ddc* d, int64_t n_in) {
+    ProfScope ps(e, "ddc_history_kernel");
+    hipLaunchKernelGGL(ddc_history_kernel, dim3(1), dim3(kDdcMaxTaps), 0, e->stream, (const void*)e->ddc_stage.ptr, d->hist, n_in, d->Tp,
+                       (int)ddc_in_bytes(d->in_fmt));
 }
 
 static int ddc_push_impl(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in, int64_t off, int64_t* n_out, bool wait) {
     if (int rc = sdr_set_device(e)) return rc;
     if (int rc = ddc_check(e, d)) return rc;
+    if (d->L != 1) return rs_push_impl(e, d, in, n_in, off, n_out, wait);     // a rational resampler: resample.hip
     if (!e->iq) return sdr_fail(SDR_ERR_STATE, "IQ ring not allocated");
     if (n_in < 0) return sdr_fail(SDR_ERR_INVALID, "negative input count");
     if (!in && n_in > 0) return sdr_fail(SDR_ERR_INVALID, "host pointer is NULL");
@@ -202,6 +166,7 @@ int sdr_ddc_create(sdr_engine* e, const sdr_ddc_cfg* cfg, sdr_ddc** out) {
     sdr_ddc* d = new (std::nothrow) sdr_ddc();
     if (!d) return sdr_fail(SDR_ERR_NOMEM, "host allocation failed");
     d->engine = e, d->in_fmt = cfg->in_fmt, d->D = cfg->decimation, d->T = cfg->n_taps, d->fcw = cfg->fcw, d->gain = cfg->gain;
+    d->Tp = d->T;
     const size_t hist_bytes = (size_t)(d->T > 1 ? d->T - 1 : 1) * ddc_in_bytes(d->in_fmt);
     hipError_t err = hipMalloc((void**)&d->taps, (size_t)d->T * sizeof(double));
     if (err == hipSuccess) err = hipMalloc(&d->hist, hist_bytes);
@@ -230,7 +195,7 @@ void sdr_ddc_destroy(sdr_engine* e, sdr_ddc* d) {
 int sdr_ddc_reset(sdr_engine* e, sdr_ddc* d) {
     if (int rc = sdr_set_device(e)) return rc;
     if (int rc = ddc_check(e, d)) return rc;
-    const size_t hist_bytes = (size_t)(d->T > 1 ? d->T - 1 : 1) * ddc_in_bytes(d->in_fmt);
+    const size_t hist_bytes = (size_t)(d->Tp > 1 ? d->Tp - 1 : 1) * ddc_in_bytes(d->in_fmt);
     SDR_HIP(hipMemsetAsync(d->hist, 0, hist_bytes, e->stream));
     if (d->mit)
         if (int rc = mit_reset(e, d->mit)) return rc;
@@ -249,6 +214,10 @@ int sdr_ddc_push_queue(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in, 
 int64_t sdr_ddc_out_count(const sdr_ddc* d, int64_t n_in) {
     if (!d) return sdr_fail(SDR_ERR_INVALID, "converter is NULL");
     if (n_in < 0) return sdr_fail(SDR_ERR_INVALID, "negative input count");
+    if (d->L != 1) {
+        if (!rs_in_range(d->n_seen, n_in, d->L)) return sdr_fail(SDR_ERR_RANGE, "%lld inputs take the up-sampled index past 2^62", (long long)n_in);
+        return rs_push(d->n_seen, n_in, d->L, d->D, d->T).n_out;
+    }
     return ddc_push(d->n_seen, n_in, d->D, d->T).n_out;
 }
 
@@ -274,7 +243,7 @@ int sdr_ddc_mitigation_stats(sdr_engine* e, sdr_ddc* d, sdr_mit_stats* stats, in
     if (int rc = ddc_check(e, d)) return rc;
     if (!stats) return sdr_fail(SDR_ERR_INVALID, "no result block for the counters");
     if (!d->mit) return sdr_fail(SDR_ERR_STATE, "the converter has no mitigator");
-    return mit_stats(e, d->mit, ddc_ceil_div(d->n_seen, d->D), stats, bins);
+    return mit_stats(e, d->mit, ddc_ceil_div(d->n_seen * d->L, d->D), stats, bins);
 }
 
 }  // extern "C"

@@ -1,0 +1,66 @@
+// The converter's handle and what ddc.hip (mixer, FIR low-pass, integer decimation) and resample.hip (interpolation by L,
+// decimation by M) share of its kernels: the raw input's formats and the rounding of an integer ring.
+#pragma once
+
+#include "engine_internal.h"
+#include "mitigate.h"
+
+struct sdr_ddc {
+    sdr_engine* engine = nullptr;
+    int in_fmt = 0, D = 1, T = 1;
+    uint64_t fcw = 0;
+    double gain = 1.0;
+    double* taps = nullptr;      // device [T]
+    void* hist = nullptr;        // device [max(T-1, 1)] raw inputs, oldest first
+    int64_t n_seen = 0;          // inputs since creation / reset
+    sdr::Mitigator* mit = nullptr;    // between the filter's output and the ring's format (sdr_ddc_mitigate), or none
+    // a rational resampler (sdr_ddc_create_rational with L > 1, resample.hip): D is M, T the prototype's length, `taps` the
+    // table [Tp][L'] of resample_tiles.h and `hist` the last Tp - 1 raw inputs
+    int L = 1;
+    int Tp = 1;                  // ceil(T / L): the history holds Tp - 1 inputs (L = 1: T)
+};
+
+inline size_t ddc_in_bytes(int in_fmt) {
+    switch (in_fmt) {
+        case SDR_DDC_IN_R8: return 1;
+        case SDR_DDC_IN_R16: return 2;
+        case SDR_DDC_IN_CI8: return 2;
+        case SDR_DDC_IN_CI16: return 4;
+    }
+    return 0;
+}
+
+__device__ __forceinline__ void ddc_load(const void* __restrict__ p, int64_t i, int in_fmt, double* re, double* im) {
+    switch (in_fmt) {
+        case SDR_DDC_IN_R8: *re = (double)((const int8_t*)p)[i], *im = 0.0; break;
+        case SDR_DDC_IN_R16: *re = (double)((const int16_t*)p)[i], *im = 0.0; break;
+        case SDR_DDC_IN_CI8: {
+            const uint16_t w = ((const uint16_t*)p)[i];
+            *re = (double)(int8_t)(w & 0xff), *im = (double)(int8_t)(w >> 8);
+            break;
+        }
+        default: {
+            const uint32_t w = ((const uint32_t*)p)[i];
+            *re = (double)(int16_t)(w & 0xffff), *im = (double)(int16_t)(w >> 16);
+            break;
+        }
+    }
+}
+
+__device__ __forceinline__ double ddc_clip_rint(double v, double lim) { return fmin(fmax(rint(v), -lim), lim); }
+
+inline int ddc_check(sdr_engine* e, const sdr_ddc* d) {
+    if (!d) return sdr_fail(SDR_ERR_INVALID, "converter is NULL");
+    if (d->engine != e) return sdr_fail(SDR_ERR_INVALID, "the converter belongs to another engine");
+    return SDR_OK;
+}
+
+namespace sdr {
+
+// resample.hip: the push of a converter with L > 1 (the arguments already checked against NULL and the engine by the caller).
+// ddc.hip: the history launch behind a push's kernel -- the last d->Tp - 1 of the raw inputs in the staging buffer and the old
+// history, under the scope "ddc_history_kernel".
+void ddc_history_launch(sdr_engine* e, sdr_ddc* d, int64_t n_in);
+int rs_push_impl(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in, int64_t off, int64_t* n_out, bool wait);
+
+}  // namespace sdr

@@ -388,12 +388,17 @@ class Engine:
 
     # ------------------------------------------------------------------ down-conversion into the ring (signal/downconvert.py)
     def ddc_create(self, cfg):
-        """A device-resident down-converter (sdr_ddc_create) of a signal.downconvert.DownConverterConfig -> its handle."""
+        """A device-resident down-converter (sdr_ddc_create; with cfg.interpolation != 1 sdr_ddc_create_rational) of a
+        signal.downconvert.DownConverterConfig -> its handle."""
         taps = np.ascontiguousarray(cfg.taps, dtype=np.float64)
         c = _lib.DdcCfg(int(cfg.in_fmt), int(cfg.decimation), int(taps.size), 0, int(cfg.fcw), float(cfg.gain),
                         taps.ctypes.data_as(C.POINTER(C.c_double)))
         h = C.c_void_p()
-        check(self._lib.sdr_ddc_create(self._h, C.byref(c), C.byref(h)))
+        interpolation = int(cfg.interpolation)
+        if interpolation != 1:            # a rational resampler by L / M (sdr_ddc_create_rational): decimation is M
+            check(self._lib.sdr_ddc_create_rational(self._h, C.byref(c), interpolation, C.byref(h)))
+        else:
+            check(self._lib.sdr_ddc_create(self._h, C.byref(c), C.byref(h)))
         return _Ddc(h, int(cfg.in_fmt))
 
     def _ddc_push(self, call, ddc, raw, ring_offset):

@@ -11,7 +11,9 @@ A recording at an intermediate frequency or at a wider band than the channels ne
 empty) -- goes through the device's down-converter (downconvert.py) when the key `decimation` is present (optional keys
 `baseband_shift`, `filter_taps`, `filter_cutoff`, `output_gain`, `output_bits`): the front-end attributes the channels read
 (`samplingFrequency`, `samplesPerMs`, `interFrequency`) are then the RING's, the slabs handed out are raw input, and
-`frontEnd` says how the one becomes the other.
+`frontEnd` says how the one becomes the other.  The optional key `interpolation` (L; only beside `decimation`, which is then
+M) makes the converter a rational resampler: the ring's rate is `sampling_frequency * L / M` (16.368 MHz -> 12 MHz with 250 / 341),
+the default filter comes from `design_resampler` and `filter_cutoff` is a fraction of the UP-SAMPLED rate.
 Such a recording may also ask for interference mitigation between the converter and the ring (mitigate.py; keys
 `blanking_factor` with `blanking_lead`, `blanking_hold`, and `excision_nfft` with `excision_margin_db`; `calibration_ms`):
 the blanker's level and the excisor's limits are measured once, on the host, over the converter's output of the recording's
@@ -41,6 +43,7 @@ class FrontEnd:
     def __init__(self, config, output_bits: int, shift_hz: float, calibrate=None):
         self.config = config
         self.decimation = config.decimation
+        self.interpolation = config.interpolation
         self.groupDelay = config.group_delay
         self.outputBits = int(output_bits)
         self.shift = float(shift_hz)
@@ -86,6 +89,8 @@ class RFSignal:
         if "decimation" in configuration:
             self._front_end(configuration, bits)
         else:
+            if "interpolation" in configuration:
+                raise ValueError("`interpolation` needs `decimation` beside it: the ring's rate is sampling_frequency * L / M")
             for key in MITIGATION_KEYS:
                 if key in configuration:
                     raise ValueError(f"`{key}` needs a front end: set `decimation` (1 with `filter_taps = 1` converts nothing)")
@@ -105,25 +110,32 @@ class RFSignal:
         if self.packing is not None:
             raise ValueError("packed recordings cannot be down-converted: `decimation` needs data_size 8 or 16")
         D = int(configuration["decimation"])
-        if not 1 <= D <= dc.MAX_DECIMATION:
-            raise ValueError(f"decimation {D} outside 1..{dc.MAX_DECIMATION}")
+        L = int(configuration["interpolation"]) if "interpolation" in configuration else 1
+        if not 1 <= L <= dc.MAX_INTERPOLATION:
+            raise ValueError(f"interpolation {L} outside 1..{dc.MAX_INTERPOLATION}")
+        d_max = min(dc.MAX_DECIMATION * L, dc.MAX_RATIONAL_DECIMATION)
+        if not 1 <= D <= d_max:
+            raise ValueError(f"decimation {D} outside 1..{d_max}")
         fs_in, if_in = self.samplingFrequency, self.interFrequency
         self.inputSamplingFrequency = fs_in
         self.inputSamplesPerMs = int(fs_in * 1e-3)
-        if self.inputSamplesPerMs % D:
-            raise ValueError(f"a millisecond of {self.inputSamplesPerMs} input samples is not a whole multiple of decimation {D}")
+        if self.inputSamplesPerMs * L % D:
+            raise ValueError(f"a millisecond of {self.inputSamplesPerMs} input samples" + (f" times interpolation {L}" if L != 1 else "")
+                             + f" is not a whole multiple of decimation {D}")
         shift = float(configuration["baseband_shift"]) if "baseband_shift" in configuration else if_in
-        n_taps = int(configuration["filter_taps"]) if "filter_taps" in configuration else 16 * D + 1
-        cutoff = float(configuration["filter_cutoff"]) if "filter_cutoff" in configuration else 0.45 / D
+        # (L > 1: the prototype at the up-sampled rate, design_resampler's own defaults -- 16 max(L, M) + 1 taps, 0.45 / max(L, M))
+        n_taps = int(configuration["filter_taps"]) if "filter_taps" in configuration else 16 * D + 1 if L == 1 else None
+        cutoff = float(configuration["filter_cutoff"]) if "filter_cutoff" in configuration else 0.45 / D if L == 1 else None
         gain = float(configuration["output_gain"]) if "output_gain" in configuration else 1.0
         out_bits = int(configuration["output_bits"]) if "output_bits" in configuration else bits
         if out_bits not in (8, 16):
             raise ValueError(f"output_bits is 8 or 16, not {out_bits}")
         in_fmt = {(False, 8): dc.IN_R8, (False, 16): dc.IN_R16, (True, 8): dc.IN_CI8, (True, 16): dc.IN_CI16}[(self.isComplex, bits)]
-        config = dc.DownConverterConfig(in_fmt, D, dc.design_lowpass(n_taps, cutoff), dc.frequency_word(shift, fs_in), gain)
+        taps = dc.design_lowpass(n_taps, cutoff) if L == 1 else dc.design_resampler(L, D, n_taps, cutoff)
+        config = dc.DownConverterConfig(in_fmt, D, taps, dc.frequency_word(shift, fs_in), gain, L)
         self.frontEnd = FrontEnd(config, out_bits, shift, self._mitigation_keys(configuration, config))
         # what the channels read is the ring's: its rate, and the carrier's residual offset there
-        self.samplingFrequency = fs_in / D
+        self.samplingFrequency = fs_in * L / D
         self.interFrequency = if_in - shift
         self._per_sample = 2 if self.isComplex else 1   # elements of the file per input sample
 
