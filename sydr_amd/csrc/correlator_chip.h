@@ -209,12 +209,15 @@ __host__ __device__ inline void chip_rotations(double dphi, int Dmin, ChipRot& r
 // raw dwords, G2 = G ^ 0xFFFF0000 holds 255 - u for the b half, and v_dot4_u32_u8 with the byte weight 128 on two of the
 // four bytes, added onto the high word 0x40C0_0000 of 8192.0 (one unit of that word is 2^-7), leaves the high words of
 // the exact doubles 8192 + ua + ub = 8448 + (xa + xb) and 8192 + ua + 255 - ub = 8447 + (xa - xb).  Ten instructions per
-// pair, four of them fp64, against twelve and eight.  The run's optional last sample -- the one a lane's select takes or
-// leaves -- stays a single biased sample (4224 + x), and so does the centre sample of a run of odd length, which starts
-// the sum.  Both halves are referred to their own centres: the lane's block phasor is evaluated at the first half's
+// pair, four of them fp64, against twelve and eight.  The run's optional last sample -- the one a lane's flag masks, see
+// chip_mask_shares() -- stays a single biased sample (4224 + x), and so does the centre sample of a run of odd length, which
+// starts the sum.  Both halves are referred to their own centres: the lane's block phasor is evaluated at the first half's
 // centre instead of the block's first sample, and the second half is turned by the distance of the two centres.
 #ifndef SDR_FOLD_PAIRS
 #define SDR_FOLD_PAIRS 1     // (0: the direct sum of every form, the text of the kernels before folding -- for A/B runs)
+#endif
+#ifndef SDR_TURN_ONCE
+#define SDR_TURN_ONCE 1      // (0: every tap's share of a block turned by the block phasor on its own, as before -- for A/B runs)
 #endif
 constexpr int kFoldPairsMax = kStaticHalf / 2;  // pairs of the longest run
 constexpr double kFoldSumBias = 8192.0 + 256.0, kFoldDiffBias = 8192.0 + 255.0;
@@ -255,6 +258,31 @@ __host__ __device__ inline void chip_fold_constants(double dphi, int KM, int hal
 constexpr bool chip_folds(int NT, int KM, int KS, int KI) {
     return SDR_FOLD_PAIRS != 0 && SDR_BIASED_CVT != 0 && KM != 0 && (KS != 0 || KI != 0) &&
            (NT > 3 || (KS != 0 ? KM >= 20 : KM <= 17));
+}
+
+// ---- Optional samples are masked, not selected.  Each half block has one or two samples that only some lanes sum: the
+// block's sample KM where the block is M + 1 long, and (taps switching inside the block, KS) sample KS, which belongs to the
+// first half where the lane's taps switch a sample late and to the second half otherwise.  A lane takes such a sample's raw
+// dword or 0x80808080 (x = 0) by its flag, so every lane sums the conversion's offset in that place and a half's sum can
+// START from minus the offsets' share of all its samples: c1 / s1 for the first half, c2 / s2 for the second.  From the
+// plan's constants: the folded forms pair samples KS and KM about the second half's centre (rotations (sc, -+ss)[1]); the
+// direct ones meet sample KS one step in front of the second half's rotation 0.
+struct ChipShares {
+    double c1, s1, c2, s2;
+};
+__host__ __device__ __forceinline__ ChipShares chip_mask_shares(const ChipFold& f, bool ks) {
+    if (!ks) return ChipShares{f.shc[0], f.shs[0], f.shc[3], f.shs[3]};
+    return ChipShares{f.shc[1], f.shs[1], f.shc[2] + (f.sc[1] * kFoldSumBias + f.ss[1] * kFoldDiffBias),
+                      f.shs[2] + (f.sc[1] * kFoldSumBias - f.ss[1] * kFoldDiffBias)};
+}
+__host__ __device__ __forceinline__ ChipShares chip_mask_shares(const ChipRot& r, int KM, int half, bool ks) {
+    const int i_first = 2 * half - KM;              // (biasc[i]: a sum of KM - half + i samples)
+    ChipShares sh{r.biasc[i_first], r.biass[i_first], r.biasc[1], r.biass[1]};
+    if (ks) {
+        sh.c2 = sh.c2 + (r.urc[1] + r.urs[1]) * kCvtBias;
+        sh.s2 = sh.s2 + (r.urc[1] - r.urs[1]) * kCvtBias;
+    }
+    return sh;
 }
 
 // One epoch of a plan as the straight-line kernels read it (device memory, one per item).
@@ -374,7 +402,8 @@ struct ChipBlock {
 // the anchor at 24.4 samples per chip -- the reference's default correlator spacing at 25 MHz; the host checked it for
 // every epoch of the launch, and an epoch that disagrees is flagged and redone per sample).  All four positions
 // somebody reads -- P_KS, P_(KS+1), P_KM, P_(KM+1) -- are then compile-time: they stay in registers, the sample loop
-// is one straight line (no strip stores, no bit tests, no branches) and a lane picks its pair member with selects.
+// is one straight line (no strip stores, no bit tests, no branches) and a lane masks the two samples it may not own
+// (chip_mask_shares()).
 // KI = 1 (with KM > 0): the taps sit whole chips apart -- tap t on chip q + (t - A) for ALL of the anchor's block of
 // chip q (the five taps VE/E/P/L/VL at -1, -0.5, 0, +0.5, +1 chip of BASELINE configs 4-5 on the half-chip view of
 // their replicas: -2 .. +2 half-chips at 24.4 samples per half-chip).  No tap switches inside a block, so the block
@@ -428,10 +457,14 @@ __device__ __forceinline__ bool correlate_epoch_chip(const void* __restrict__ ri
     // ... and of those, the forms that sum their half blocks as folded sample pairs (ChipFold)
     constexpr bool kFold = kStatic && chip_folds(NT, KM, KS, KI);
     constexpr int kFoldN0 = chip_fold_count(KM, kHalf, KS != 0, 0), kFoldN1 = chip_fold_count(KM, kHalf, KS != 0, 1);
+    // ... and the three-tap forms whose taps switch inside the block turn a block's two sums by its phasor once and add them
+    // into P, E - P and L - P (see process())
+    constexpr bool kTurnOnce = SDR_TURN_ONCE != 0 && kStatic && KS != 0 && NT == 3;
     double fpc[2][kFoldPairsMax], fps[2][kFoldPairsMax], fsc[2] = {1.0, 1.0}, fss[2] = {0.0, 0.0};   // (kFold) pair and last-sample rotations
-    double fshc[4] = {0.0, 0.0, 0.0, 0.0}, fshs[4] = {0.0, 0.0, 0.0, 0.0};                           // (kFold) the offsets' shares
     double urc[kStatic ? kHalf + 1 : 1], urs[kStatic ? kHalf + 1 : 1];
-    double biasc[3] = {0.0, 0.0, 0.0}, biass[3] = {0.0, 0.0, 0.0};   // (biased conversion) the offset's share of a sum of kHalf - 2 / - 1 / - 0 samples
+    // (straight-line forms, biased conversion) the offsets' share of each half's sum WITH its optional samples: a half starts
+    // from minus its share, and a lane without an optional sample sums the offset alone in its place (see process())
+    double sh1c = 0.0, sh1s = 0.0, sh2c = 0.0, sh2s = 0.0;
     // samples per chip as Q32.32, and the distance to a lane's next block: D or D + 1 samples
     const double two32 = 4294967296.0;
     int64_t Tfx = G.Tfx;
@@ -455,27 +488,24 @@ __device__ __forceinline__ bool correlate_epoch_chip(const void* __restrict__ ri
                     if (h == 1 || KS != 0) fsc[h] = RF->sc[h], fss[h] = RF->ss[h];
                 }
                 urc[kHalf] = RF->tc, urs[kHalf] = RF->ts;       // (the second half onto the first half's centre)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    if (i == 1 && KS == 0) continue;
-                    fshc[i] = RF->shc[i], fshs[i] = RF->shs[i];
-                    if constexpr (kWalk && (kHalf >= 12 || NT > 3)) asm volatile("" : "+v"(fshc[i]), "+v"(fshs[i]));   // (as biasc / biass below)
-                }
+                const ChipShares sh = chip_mask_shares(*RF, KS != 0);
+                sh1c = sh.c1, sh1s = sh.s1, sh2c = sh.c2, sh2s = sh.s2;
             } else {
 #pragma unroll
                 for (int k = 1; k <= kHalf; ++k) urc[k] = R->urc[k], urs[k] = R->urs[k];
-            }
-            rd0c = R->rd0c, rd0s = R->rd0s, rd1c = R->rd1c, rd1s = R->rd1s;
-            if constexpr (SDR_BIASED_CVT && !kFold) {
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-                    biasc[i] = R->biasc[i], biass[i] = R->biass[i];
-                    // (they feed v_add_f64 alone, which takes them from vector registers as well: twelve scalar registers less
-                    // beside the 48 - 52 of the in-block rotations of the long blocks' forms that are short of them; the forms
-                    // that are not keep their vector registers, some of them for a fourth wave per SIMD)
-                    if constexpr (kWalk && (kHalf >= 12 || NT > 3)) asm volatile("" : "+v"(biasc[i]), "+v"(biass[i]));
+                if constexpr (SDR_BIASED_CVT) {
+                    const ChipShares sh = chip_mask_shares(*R, KM, kHalf, KS != 0);
+                    sh1c = sh.c1, sh1s = sh.s1, sh2c = sh.c2, sh2s = sh.s2;
                 }
             }
+            rd0c = R->rd0c, rd0s = R->rd0s, rd1c = R->rd1c, rd1s = R->rd1s;
+            // (the shares start fused multiply-adds and additions, which take them from vector registers as well: scalar
+            // registers less beside the 48 - 52 of the in-block rotations of the long blocks' forms that are short of them; the
+            // forms that are not keep their vector registers, some of them for a fourth wave per SIMD)
+            if constexpr (SDR_BIASED_CVT && kWalk && (kHalf >= 12 || NT > 3)) asm volatile("" : "+v"(sh1c), "+v"(sh1s), "+v"(sh2c), "+v"(sh2s));
+            // (the three-tap whole-chip form of 24 samples holds 52 scalar registers of rotations and runs four waves on 120 - 122
+            // vector ones: one share fits there, and with both in scalar registers a spill slot stays in the frame)
+            if constexpr (SDR_BIASED_CVT && !kWalk && !kFold && KM == 24) asm volatile("" : "+v"(sh2c), "+v"(sh2s));
         } else {
             if (wlane < kChipMax) {
                 sincos_reduced(-(double)wlane * dphi_u, &sn, &cs);
@@ -793,31 +823,62 @@ __device__ __forceinline__ bool correlate_epoch_chip(const void* __restrict__ ri
                 pi = __builtin_fma(ai, r.x, __builtin_fma(ar, r.y, pi));
                 if constexpr (SDR_BIASED_CVT) asm volatile("" : "+v"(pr), "+v"(pi), "+v"(zI), "+v"(zQ));   // (see the straight-line loop below)
             };
-            double capr[3] = {0.0, 0.0, 0.0}, capi[3] = {0.0, 0.0, 0.0};   // KS: P_KS, second half before its last sample, second half
+            double hr = 0.0, hi = 0.0;                    // (straight-line forms) the first half's sum
             if constexpr (kStatic) {
                 static_assert(2 * kHalf >= KM + 1 && kHalf < KM, "two halves of at most KS + 1 samples cover the block");
-                // first half: samples 0 .. KS (P_KS is its running sum before the last one, P_(KS+1) its total);
-                // second half: samples KS+1 .. KM summed from rotation 0 again, turned by exp(-1j*(KS+1)*dphi) where read
+                // The block is summed in two halves, each from rotation 0 (folded forms: about its own centre); the second one is
+                // turned onto the first where the block's sum is formed.  KS: the first half is the tap's part of the block in
+                // front of its switch -- samples 0 .. KS - 1 and, where the lane's switch comes a sample late, KS -- and the second
+                // half everything behind it: sample KS where the first half left it, KS + 1 .. KM - 1, and KM where the lane's block
+                // is M + 1 long.  KI: samples 0 .. kHalf - 1, then kHalf .. KM - 1 and KM likewise.  An optional sample is MASKED,
+                // not selected: the lane's flag picks the sample's raw dword or 0x80808080 (x = 0), so a lane without the sample
+                // sums the conversion's offset times the sample's rotation, the same amount in every lane -- and each half starts
+                // from minus the offsets' share of ALL its samples (sh1 / sh2).  Two sums per block, no captures, no 64-bit selects.
                 static_assert(!SDR_BIASED_CVT || (2 * kHalf - KM >= 1 && 2 * kHalf - KM <= 2 && (KS == 0 || KS == kHalf - 1)),
                               "the offset's shares are kept for sums of KM - kHalf, + 1 and + 2 samples: kHalf must be one of the last two");
+                static_assert(KS == 0 || NT == 3, "one switch flag serves the taps either side of the anchor");
                 uint32_t flipped[kChipRawDwords];
                 uint32_t hi_const = hi_epoch;
                 if constexpr (SDR_BIASED_CVT) {
                     if constexpr (!kWalk && !kFold) asm volatile("" : "+v"(hi_const));   // (v_perm_b32 takes one scalar operand: the selector)
-#pragma unroll
-                    for (int i = 0; i < kChipRawDwords; ++i) flipped[i] = b.raw[i];   // (the ring holds the flipped bytes)
                 }
+#pragma unroll
+                for (int i = 0; i < kChipRawDwords; ++i) flipped[i] = b.raw[i];   // (the ring holds the flipped bytes)
+                // The masked copies (copies: a dword's other sample belongs to the other half).  The flags are the carries of the
+                // block's fraction, taken HERE: a flag made when the block was prepared is a lane mask in a scalar register pair
+                // for the length of a block, two blocks in flight, beside the 52 scalar registers of the rotations -- which then
+                // spill through v_readlane.  A block that went through the exact re-evaluation brings its flags as integers.
+                constexpr uint32_t kNoSample = 0x80808080u;
+                constexpr int kWordS = (kHalf - 1) >> 1, kWordM = KM >> 1;
+                bool dnf = false, swf = false;
+                if constexpr (kWalk) {
+                    if (__builtin_expect(b.slow != 0, 0)) {
+                        dnf = b.dn != 0;
+                        if constexpr (KS != 0) swf = b.ds[0] != 0;
+                        asm volatile("");                       // (stays a branch: as selects, both sides would be paid in every block)
+                    } else {
+                        uint32_t f = b.f, fsum;
+                        asm volatile("" : "+v"(f));
+                        dnf = chip_carry(f, T_lo, fsum);
+                        if constexpr (KS != 0) swf = chip_carry(f, delta_lo[0], fsum);
+                    }
+                } else {
+                    dnf = b.dn != 0;
+                }
+                // sample KM, and sample KS for the first half / for the second
+                const uint32_t w_last = dnf ? flipped[kWordM] : kNoSample;
+                const uint32_t w_first = swf ? flipped[kWordS] : kNoSample, w_rest = swf ? kNoSample : flipped[kWordS];
                 if constexpr (kFold) {
                     // Each half: the centre sample of an odd run starts the sum, then the pairs from the outside in, then the
-                    // optional last sample.  `seq` counts these steps through the block: odd steps build their doubles in the
+                    // optional samples.  `seq` counts these steps through the block: odd steps build their doubles in the
                     // second register set (see SDR_ALT_PAIRS: a high word is rewritten two steps after it was last read).
-                    auto single = [&](auto kc, auto seqc, bool start, double rc, double rs) {
-                        constexpr int k = decltype(kc)::value;
+                    auto single = [&](auto highc, auto seqc, uint32_t w, bool start, double rc, double rs, double shr, double shi) {
+                        constexpr bool high = decltype(highc)::value != 0;     // the dword's second sample
                         constexpr bool alt = SDR_ALT_PAIRS && (decltype(seqc)::value & 1);
-                        const double ar = biased_sample(alt ? zI2 : zI, flipped[k >> 1], cvt_selector((k & 1) ? 2 : 0), hi_const);
-                        const double ai = biased_sample(alt ? zQ2 : zQ, flipped[k >> 1], cvt_selector((k & 1) ? 3 : 1), hi_const);
+                        const double ar = biased_sample(alt ? zI2 : zI, w, cvt_selector(high ? 2 : 0), hi_const);
+                        const double ai = biased_sample(alt ? zQ2 : zQ, w, cvt_selector(high ? 3 : 1), hi_const);
                         if (start) {
-                            pr = ar, pi = ai;
+                            pr = ar - shr, pi = ai - shi;
                         } else {
                             pr = __builtin_fma(-ai, rs, __builtin_fma(ar, rc, pr));
                             pi = __builtin_fma(ai, rc, __builtin_fma(ar, rs, pi));
@@ -825,12 +886,11 @@ __device__ __forceinline__ bool correlate_epoch_chip(const void* __restrict__ ri
                         if constexpr (alt) asm volatile("" : "+v"(pr), "+v"(pi), "+v"(zI2), "+v"(zQ2));
                         else asm volatile("" : "+v"(pr), "+v"(pi), "+v"(zI), "+v"(zQ));
                     };
-                    auto pair = [&](auto kac, auto kbc, auto seqc, bool start, double c, double sn) {
-                        constexpr int ka = decltype(kac)::value, kb = decltype(kbc)::value;
+                    auto pair = [&](auto highac, auto highbc, auto seqc, uint32_t wa, uint32_t wb, bool start, double c, double sn, double shr, double shi) {
                         constexpr bool alt = SDR_ALT_PAIRS && (decltype(seqc)::value & 1);
                         // G = [aI aQ bI bQ], lowest byte first (selector bytes 4 .. 7: the first operand, 0 .. 3: the second)
-                        constexpr uint32_t ia = 4u + 2u * (ka & 1), ib = 2u * (kb & 1);
-                        const uint32_t g = __builtin_amdgcn_perm(flipped[ka >> 1], flipped[kb >> 1], ((ib + 1u) << 24) | (ib << 16) | ((ia + 1u) << 8) | ia);
+                        constexpr uint32_t ia = 4u + 2u * (decltype(highac)::value & 1), ib = 2u * (decltype(highbc)::value & 1);
+                        const uint32_t g = __builtin_amdgcn_perm(wa, wb, ((ib + 1u) << 24) | (ib << 16) | ((ia + 1u) << 8) | ia);
                         const uint32_t g2 = g ^ 0xFFFF0000u;
                         sdr_u32x2& SI = alt ? zI2 : zI;
                         sdr_u32x2& SQ = alt ? zQ2 : zQ;
@@ -843,8 +903,8 @@ __device__ __forceinline__ bool correlate_epoch_chip(const void* __restrict__ ri
                         const double si = __builtin_bit_cast(double, SI), sq = __builtin_bit_cast(double, SQ);
                         const double di = __builtin_bit_cast(double, DI), dq = __builtin_bit_cast(double, DQ);
                         if (start) {
-                            pr = __builtin_fma(-sn, dq, c * si);
-                            pi = __builtin_fma(sn, di, c * sq);
+                            pr = __builtin_fma(-sn, dq, __builtin_fma(c, si, -shr));
+                            pi = __builtin_fma(sn, di, __builtin_fma(c, sq, -shi));
                         } else {
                             pr = __builtin_fma(-sn, dq, __builtin_fma(c, si, pr));
                             pi = __builtin_fma(sn, di, __builtin_fma(c, sq, pi));
@@ -857,52 +917,81 @@ __device__ __forceinline__ bool correlate_epoch_chip(const void* __restrict__ ri
                         constexpr int first = chip_fold_first(kHalf, h), count = h == 0 ? kFoldN0 : kFoldN1;
                         constexpr int odd = count & 1;
                         constexpr int seq0 = h == 0 ? 0 : (kFoldN0 & 1) + kFoldN0 / 2 + (KS != 0 ? 1 : 0);
-                        if constexpr (odd) single(std::integral_constant<int, first + count / 2>{}, std::integral_constant<int, seq0>{}, true, 1.0, 0.0);
+                        constexpr int last = first + count;                            // the half's optional last sample
+                        const double shr = h == 0 ? sh1c : sh2c, shi = h == 0 ? sh1s : sh2s;
+                        if constexpr (odd)
+                            single(std::integral_constant<int, (first + count / 2) & 1>{}, std::integral_constant<int, seq0>{},
+                                   flipped[(first + count / 2) >> 1], true, 1.0, 0.0, shr, shi);
                         static_for<0, count / 2>([&](auto ic) {
                             constexpr int i = decltype(ic)::value;
-                            pair(std::integral_constant<int, first + i>{}, std::integral_constant<int, first + count - 1 - i>{},
-                                 std::integral_constant<int, seq0 + odd + i>{}, !odd && i == 0, fpc[h][i], fps[h][i]);
+                            constexpr int ka = first + i, kb = first + count - 1 - i;
+                            pair(std::integral_constant<int, ka & 1>{}, std::integral_constant<int, kb & 1>{}, std::integral_constant<int, seq0 + odd + i>{},
+                                 flipped[ka >> 1], flipped[kb >> 1], !odd && i == 0, fpc[h][i], fps[h][i], shr, shi);
                         });
+                        constexpr auto seql = std::integral_constant<int, seq0 + odd + count / 2>{};
                         if constexpr (h == 0) {
-                            capr[0] = pr, capi[0] = pi;                                // the first half before its last sample
-                            if constexpr (KS != 0)
-                                single(std::integral_constant<int, first + count>{}, std::integral_constant<int, seq0 + odd + count / 2>{}, false, fsc[0], fss[0]);
-                            capr[2] = pr, capi[2] = pi;                                // ... and with it (whole-chip taps: the same sum)
+                            if constexpr (KS != 0) single(std::integral_constant<int, last & 1>{}, seql, w_first, false, fsc[0], fss[0], 0.0, 0.0);
+                            hr = pr, hi = pi;
+                        } else if constexpr (KS != 0) {
+                            // (samples KS and KM lie (count + 1) / 2 either side of the second half's centre: one more pair)
+                            pair(std::integral_constant<int, (kHalf - 1) & 1>{}, std::integral_constant<int, last & 1>{}, seql, w_rest, w_last, false,
+                                 fsc[1], -fss[1], 0.0, 0.0);
                         } else {
-                            capr[1] = pr, capi[1] = pi;                                // the second half up to the M-th sample
-                            single(std::integral_constant<int, first + count>{}, std::integral_constant<int, seq0 + odd + count / 2>{}, false, fsc[1], fss[1]);
+                            single(std::integral_constant<int, last & 1>{}, seql, w_last, false, fsc[1], fss[1], 0.0, 0.0);
                         }
                     });
-                } else
-                static_for<0, KM + 1>([&](auto kc) {
-                    constexpr int k = decltype(kc)::value;
-                    constexpr int j = k < kHalf ? k : k - kHalf;
-                    const int w = ci8_native((int)b.raw[k >> 1]);
-                    double ar, ai;
-                    if constexpr (SDR_BIASED_CVT) {
-                        ar = biased_sample(kWalk && SDR_ALT_PAIRS && (k & 1) ? zI2 : zI, flipped[k >> 1], cvt_selector((k & 1) ? 2 : 0), hi_const);
-                        ai = biased_sample(kWalk && SDR_ALT_PAIRS && (k & 1) ? zQ2 : zQ, flipped[k >> 1], cvt_selector((k & 1) ? 3 : 1), hi_const);
-                    } else {
-                        ar = (k & 1) ? (double)(int)(int8_t)(w >> 16) : (double)(int)(int8_t)w;
-                        ai = (k & 1) ? (double)(w >> 24) : (double)(int)(int8_t)(w >> 8);
+                } else {
+                    // mode 0: the sum starts from this sample (rotation 1) and minus the share; 1: rotation 1; 2: rotation (rc, rs)
+                    auto direct = [&](auto highc, auto seqc, uint32_t w, auto modec, double rc, double rs, double shr, double shi) {
+                        constexpr bool high = decltype(highc)::value != 0;
+                        constexpr int mode = decltype(modec)::value;
+                        constexpr bool alt = kWalk && SDR_ALT_PAIRS && (decltype(seqc)::value & 1);
+                        double ar, ai;
+                        if constexpr (SDR_BIASED_CVT) {
+                            ar = biased_sample(alt ? zI2 : zI, w, cvt_selector(high ? 2 : 0), hi_const);
+                            ai = biased_sample(alt ? zQ2 : zQ, w, cvt_selector(high ? 3 : 1), hi_const);
+                        } else {
+                            const int wn = ci8_native((int)w);
+                            ar = high ? (double)(int)(int8_t)(wn >> 16) : (double)(int)(int8_t)wn;
+                            ai = high ? (double)(wn >> 24) : (double)(int)(int8_t)(wn >> 8);
+                        }
+                        if constexpr (mode == 0) {
+                            pr = ar - shr, pi = ai - shi;
+                        } else if constexpr (mode == 1) {
+                            pr = pr + ar, pi = pi + ai;
+                        } else {
+                            pr = __builtin_fma(-ai, rs, __builtin_fma(ar, rc, pr));
+                            pi = __builtin_fma(ai, rc, __builtin_fma(ar, rs, pi));
+                        }
+                        // (an opaque point per sample: the sums must have read the pairs before their high words are written
+                        // again, and the next sample must be built on THESE registers -- seen through, every sample would be
+                        // rebuilt from the original pair, i.e. from a copy of its low word)
+                        if constexpr (SDR_BIASED_CVT) {
+                            if constexpr (alt) asm volatile("" : "+v"(pr), "+v"(pi), "+v"(zI2), "+v"(zQ2));
+                            else asm volatile("" : "+v"(pr), "+v"(pi), "+v"(zI), "+v"(zQ));
+                        }
+                    };
+                    constexpr int kExtra = KS != 0 ? 1 : 0;       // (KS: sample KS is summed once per half)
+                    static_for<0, kHalf>([&](auto kc) {
+                        constexpr int k = decltype(kc)::value;
+                        const uint32_t w = KS != 0 && k == kHalf - 1 ? w_first : flipped[k >> 1];
+                        direct(std::integral_constant<int, k & 1>{}, kc, w, std::integral_constant<int, k == 0 ? 0 : 2>{}, k == 0 ? 1.0 : urc[k], k == 0 ? 0.0 : urs[k], sh1c, sh1s);
+                    });
+                    hr = pr, hi = pi;
+                    if constexpr (KS != 0) {
+                        // (one sample in front of the second half's rotation 0: the conjugate of one sample behind it)
+                        pr = -sh2c, pi = -sh2s;
+                        direct(std::integral_constant<int, (kHalf - 1) & 1>{}, std::integral_constant<int, kHalf>{}, w_rest, std::integral_constant<int, 2>{},
+                               urc[1], -urs[1], 0.0, 0.0);
                     }
-                    if constexpr (KS != 0 && k == KS) capr[0] = pr, capi[0] = pi;
-                    if constexpr (k == KM) capr[1] = pr, capi[1] = pi;
-                    if constexpr (k == kHalf) capr[2] = pr, capi[2] = pi;          // first half's total
-                    if constexpr (j == 0) {
-                        pr = ar, pi = ai;
-                    } else {
-                        pr = __builtin_fma(-ai, urs[j], __builtin_fma(ar, urc[j], pr));
-                        pi = __builtin_fma(ai, urc[j], __builtin_fma(ar, urs[j], pi));
-                    }
-                    // (an opaque point per sample: the sums must have read the pairs before their high words are written
-                    // again, and the next sample must be built on THESE registers -- seen through, every sample would be
-                    // rebuilt from the original pair, i.e. from a copy of its low word)
-                    if constexpr (SDR_BIASED_CVT) {
-                        if constexpr (kWalk && SDR_ALT_PAIRS && (k & 1)) asm volatile("" : "+v"(pr), "+v"(pi), "+v"(zI2), "+v"(zQ2));
-                        else asm volatile("" : "+v"(pr), "+v"(pi), "+v"(zI), "+v"(zQ));
-                    }
-                });
+                    static_for<kHalf, KM + 1>([&](auto kc) {
+                        constexpr int k = decltype(kc)::value;
+                        constexpr int j = k - kHalf;
+                        const uint32_t w = k == KM ? w_last : flipped[k >> 1];
+                        direct(std::integral_constant<int, k & 1>{}, std::integral_constant<int, k + kExtra>{}, w,
+                               std::integral_constant<int, j == 0 ? (KS != 0 ? 1 : 0) : 2>{}, j == 0 ? 1.0 : urc[j], j == 0 ? 0.0 : urs[j], sh2c, sh2s);
+                    });
+                }
             } else if constexpr (KM != 0) {
                 // positions KM and KM + 1 are always events; the others (the taps' m_t, m_t + 1 < KM) are looked for
                 // two samples at a time
@@ -940,45 +1029,10 @@ __device__ __forceinline__ bool correlate_epoch_chip(const void* __restrict__ ri
                 }
             }
             double2 ptot;
-            if constexpr (kFold) {
-                // what the offsets -- 8448 and 8447 per pair, 4224 per single sample -- put into each sum that is read
-                pr -= fshc[3], pi -= fshs[3];
-                capr[1] -= fshc[2], capi[1] -= fshs[2];
-                capr[2] -= fshc[KS != 0 ? 1 : 0], capi[2] -= fshs[KS != 0 ? 1 : 0];
-                if constexpr (KS != 0) capr[0] -= fshc[0], capi[0] -= fshs[0];
-            } else if constexpr (kStatic && SDR_BIASED_CVT) {
-                // what the offset of 4224 per sample put into each sum that is read (its first sample has rotation 1:
-                // the sums start from the biased sample itself, and sum_{k<n} r_k includes that r_0 = 1)
-                constexpr int iFirst = 2 * kHalf - KM;             // (biasc[i]: a sum of KM - kHalf + i samples)
-                pr -= biasc[1], pi -= biass[1];                    // second half, KM + 1 - kHalf samples
-                capr[1] -= biasc[0], capi[1] -= biass[0];          // ... before its last sample
-                capr[2] -= biasc[iFirst], capi[2] -= biass[iFirst];      // first half: kHalf samples
-                if constexpr (KS != 0) capr[0] -= biasc[iFirst - 1], capi[0] -= biass[iFirst - 1];   // P_KS: kHalf - 1 samples
-            }
-            // (straight-line forms) the block's flags, from its fraction and HERE: a flag made when the block was prepared is a
-            // lane mask in a scalar register pair for the length of a block, two blocks in flight, beside the 52 scalar
-            // registers of the rotations -- which then spill through v_readlane.  One add per flag, in the place of the compare.
-            bool dnf = false, dsf[NT];
-#pragma unroll
-            for (int t = 0; t < NT; ++t) dsf[t] = false;
-            if constexpr (kWalk) {
-                if (__builtin_expect(b.slow != 0, 0)) {
-                    dnf = b.dn != 0;
-#pragma unroll
-                    for (int t = 0; t < NT; ++t) dsf[t] = b.ds[t] != 0;
-                    asm volatile("" : "+v"(pr), "+v"(pi));   // (stays a branch: as selects, both sides would be paid in every block)
-                } else {
-                    uint32_t f = b.f;
-                    asm volatile("" : "+v"(f), "+v"(pr), "+v"(pi));   // (... and behind the block's last sample)
-                    bool nr;
-                    chip_walk_flags<NT, KI>(f, T_lo, delta_lo, dnf, dsf, nr);
-                }
-            }
             if constexpr (kStatic) {
-                if constexpr (!kWalk) dnf = b.dn != 0;
-                const double qr = dnf ? pr : capr[1], qi = dnf ? pi : capi[1];   // second half up to M or M + 1 samples
-                ptot.x = __builtin_fma(-qi, urs[kHalf], __builtin_fma(qr, urc[kHalf], capr[2]));
-                ptot.y = __builtin_fma(qi, urc[kHalf], __builtin_fma(qr, urs[kHalf], capi[2]));
+                // (the second half -- pr, pi -- onto the first)
+                ptot.x = __builtin_fma(-pi, urs[kHalf], __builtin_fma(pr, urc[kHalf], hr));
+                ptot.y = __builtin_fma(pi, urc[kHalf], __builtin_fma(pr, urs[kHalf], hi));
             } else {
                 ptot = strip[rank[A] + b.dn];
                 if constexpr (SDR_BIASED_CVT) {             // (P_M or P_(M+1): the offset's share of that many samples out)
@@ -1004,6 +1058,20 @@ __device__ __forceinline__ bool correlate_epoch_chip(const void* __restrict__ ri
                 }
                 return;
             }
+            if constexpr (kTurnOnce) {
+                // E = c(q-1) ps + c(q) (ptot - ps), L = c(q) ps + c(q+1) (ptot - ps): with X = ph ptot, Y = ph ps
+                //     P += c(q) X,    E' += (c(q-1) - c(q)) Y,    L' += (c(q) - c(q+1)) (Y - X),    E = E' + P,  L = L' + P
+                // the block phasor turns two sums once instead of three tap shares (E' and L' are made whole behind the rounds)
+                const double xr = __builtin_fma(-sbk, ptot.y, cbk * ptot.x), xi = __builtin_fma(sbk, ptot.x, cbk * ptot.y);
+                const double yr = __builtin_fma(-sbk, hi, cbk * hr), yi = __builtin_fma(sbk, hr, cbk * hi);
+                const double zr = yr - xr, zi = yi - xi;
+                const double ce = __hiloint2double((int)lq[-1], 0), cp = __hiloint2double((int)lq[0], 0), cl = __hiloint2double((int)lq[1], 0);
+                const double de = ce - cp, dl = cp - cl;
+                accr[A] = __builtin_fma(cp, xr, accr[A]), acci[A] = __builtin_fma(cp, xi, acci[A]);
+                accr[0] = __builtin_fma(de, yr, accr[0]), acci[0] = __builtin_fma(de, yi, acci[0]);
+                accr[2] = __builtin_fma(dl, zr, accr[2]), acci[2] = __builtin_fma(dl, zi, acci[2]);
+                return;
+            }
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
                 double gr, gi;
@@ -1014,7 +1082,7 @@ __device__ __forceinline__ bool correlate_epoch_chip(const void* __restrict__ ri
                 } else {
                     double2 ps;
                     if constexpr (kStatic)
-                        ps = (kWalk ? dsf[NT == 3 ? 0 : t] : b.ds[NT == 3 ? 0 : t] != 0) ? make_double2(capr[2], capi[2]) : make_double2(capr[0], capi[0]);
+                        ps = make_double2(hr, hi);          // (KS: the first half ends where the lane's taps switch)
                     else {
                         ps = strip[rank[t] + b.ds[t]];
                         if constexpr (SDR_BIASED_CVT) {
@@ -1061,7 +1129,9 @@ __device__ __forceinline__ bool correlate_epoch_chip(const void* __restrict__ ri
                 prepare_walk(clampc, to_round, walk, to);
                 if (__builtin_expect((from.slow | to.slow) != 0, 0)) {
                     bool alive = true;
-                    int d = dd ? 1 : 0;                 // to.S - from.S - Dmin
+                    // to.S - from.S - Dmin.  (Read back from the carry's lane mask: `dd ? 1 : 0` is the integer the walk's step adds,
+                    // and the compiler forms it in front of the branch, one instruction in every block)
+                    int d = (int)((__builtin_amdgcn_ballot_w64(dd) >> wlane) & 1u);
                     if constexpr (kClamp) {
                         // (a lane beyond the last whole chip: its block is the last chip's, wherever the walk went)
                         alive = to_round * stride + lane <= last_idx;
@@ -1103,6 +1173,10 @@ __device__ __forceinline__ bool correlate_epoch_chip(const void* __restrict__ ri
             for (int it = 0; it < plain; ++it) round_pair(std::false_type{}, it);
             for (int it = plain; it < rounds / 2; ++it) round_pair(std::true_type{}, it);
             if (rounds & 1) process(blk_a, rounds - 1, sb, cb, std::true_type{});
+            if constexpr (kTurnOnce) {              // E = E' + P, L = L' + P
+                accr[0] += accr[A], acci[0] += acci[A];
+                accr[2] += accr[A], acci[2] += acci[A];
+            }
         } else {
             for (int it = 0; it < rounds / 2; ++it) {
                 const double sb0 = sb, cb0 = cb;
