@@ -39,7 +39,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define SDR_ABI_VERSION 5   /* 5 (still): + sdr_ddc_cfg, sdr_ddc_create / _destroy / _reset / _push / _push_queue / _out_count (additive); 5 (still): + sdr_iq_probe (additive); 5 (still): + sdr_corr_profile, option "corr_profile_per_sample" (additive); 5 (still): + sdr_iq_packing, sdr_iq_packed_bytes, sdr_iq_upload_packed / _begin / _queue (additive); 5 (still): + sdr_acq_refine, sdr_acq_refine_bins (additive); 5: + sdr_bank_tick_mirrored_begin / _end, sdr_iq_upload_queue, sdr_host_alloc / _free, options "tick_server" + sdr_tick_server_stats, "bind_thread_to_device" (additive); 4: + sdr_build_id, sdr_epl_plan_create_dev, sdr_bank_tick_mirrored, sdr_iq_upload_begin, sdr_block_schedule, sdr_bank_step_begin / _end (additive) */
+#define SDR_ABI_VERSION 5   /* 5 (still): + sdr_acq_deep, sdr_acq_deep_shift (additive); 5 (still): + sdr_ddc_cfg, sdr_ddc_create / _destroy / _reset / _push / _push_queue / _out_count (additive); 5 (still): + sdr_iq_probe (additive); 5 (still): + sdr_corr_profile, option "corr_profile_per_sample" (additive); 5 (still): + sdr_iq_packing, sdr_iq_packed_bytes, sdr_iq_upload_packed / _begin / _queue (additive); 5 (still): + sdr_acq_refine, sdr_acq_refine_bins (additive); 5: + sdr_bank_tick_mirrored_begin / _end, sdr_iq_upload_queue, sdr_host_alloc / _free, options "tick_server" + sdr_tick_server_stats, "bind_thread_to_device" (additive); 4: + sdr_build_id, sdr_epl_plan_create_dev, sdr_bank_tick_mirrored, sdr_iq_upload_begin, sdr_block_schedule, sdr_bank_step_begin / _end (additive) */
 
 typedef struct sdr_engine sdr_engine;
 
@@ -315,6 +315,53 @@ int sdr_acq_refine(sdr_engine* e, const sdr_refine_item* items, int n_items, dou
                    double span_hz, double step_hz, sdr_refine_result* results,
                    double* power /* nullable [n_items][n_periods][K] */,
                    double* segment_sums /* nullable [n_items][n_periods][n_segments][2] */);
+
+/* ------------------------------- deep acquisition: folded coherent blocks, code-Doppler shift, bit-edge groups
+ * The search for weak signals (opt-in like sdr_acq_refine; sdr_pcps is unchanged).  N, the Doppler grid d_b = bins[b]
+ * (np.arange(-doppler_range, doppler_range + 1, doppler_step)), the code spectra codeFFT_p = conj(fft(UpsampleCode(code_p)))
+ * and the mixing sign (the carrier removed for bin b is if_hz - d_b: a peak_bin means what sdr_pcps's means) are sdr_pcps's.
+ * With C = coh coherent periods per block (1..20), K = noncoh blocks (>= 1), G = groups bit-edge groups (1 or 2, K >= G) and
+ * carrier_rf_hz, the carrier the code Doppler is scaled by (> 0, or 0 for no compensation), the window is C*K*N ring samples
+ * from start_sample = s0 (it may cross the ring's end where sdr_pcps's may).  For block i < K, bin b, sample n < N:
+ *   phi[k]     = k * 2 * pi / fs, k < C*N              (np.array(range(C*N)) * 2 * np.pi / fs: the carrier restarts with every
+ *                                                       block, as the reference's does)
+ *   F[b][i][n] = sum_{c<C} x[s0 + (i*C + c)*N + n] * exp(-1j * (if_hz - d_b) * phi[c*N + n])
+ *   R[p][b][i] = ifft( fft(F[b][i]) * codeFFT_p )
+ *   q[b][i]    = nearbyint( d_b * float(i*C*N) / carrier_rf_hz )   (fp64 in this order, half-even; 0 when carrier_rf_hz == 0)
+ *   M[p][g][b][n] = sum over i = g (mod G), ascending i, of | R[p][b][i][ (n + q[b][i]) mod N ] |        (Python's modulo)
+ * The C mixed periods of a block are added in front of ONE forward transform (the transform is linear): C times fewer
+ * transforms than sdr_pcps(coh = C).  Blocks that hold a data-bit edge lose energy; with G = 2 and C*N half a bit or less, the
+ * blocks of one of the two groups hold none.  q moves every block's map back by the code's drift at the bin's Doppler, so
+ * the peak of a long window stays on one sample.  With G = 1 and carrier_rf_hz = 0, M is PCPS(coh = C, noncoh = K)'s map up
+ * to the order of additions.
+ * Per PRN: (peak_group, peak_bin, peak_code) = the first maximum of M[p] in row-major (g, b, n) order, peak_value = M[p]
+ * there, peak_ratio = TwoCorrelationPeakComparison on M[p][peak_group] (the second peak from the winning row, with the
+ * reference's exclusion window, as in sdr_pcps), peak_code_end = (peak_code + nearbyint(d_peak * float(K*C*N) /
+ * carrier_rf_hz)) mod N: the code start referred to the window's END, which is what a caller that places currentSample
+ * behind the window needs (postAcquisitionUpdate); equal to peak_code when carrier_rf_hz == 0.
+ * The shifts are made on the host by sdr_acq_deep_shift's expression and uploaded as integers; sums are added in a fixed
+ * order (two identical calls return identical bits); the call is synchronous on the engine's stream.  The maps of all PRNs
+ * stay resident for the call: n_prn * G * bins * N * 8 bytes (32 PRNs, two groups, 201 bins at 25 MHz: 2.6 GB); a call
+ * whose buffers cannot be reserved fails with SDR_ERR_NOMEM like any other.  corr_map (nullable) receives M.
+ * SDR_ERR_INVALID: NULL code_slots / cfg / results, n_prn < 1, coh outside 1..20, noncoh < 1, groups outside 1..2,
+ * noncoh < groups, a bad grid or fs, negative or non-finite carrier_rf_hz, a slot that is not staged; SDR_ERR_RANGE: a
+ * window longer than the ring, a negative start_sample; SDR_ERR_STATE: no ring or no code slots.
+ * sdr_prof_enable scopes: "deep_fold", "deep_fwd_fft", "deep_inv_fft", "deep_shift_acc", "deep_peak", "call_acq_deep" (the
+ * code spectra, made when they are not cached, keep sdr_pcps's "pcps_upsample" / "pcps_code_fft"). */
+typedef struct sdr_deep_cfg {
+    double fs, if_hz, doppler_range, doppler_step, carrier_rf_hz;
+    int32_t coh, noncoh, groups, reserved;
+} sdr_deep_cfg;
+typedef struct sdr_deep_result {
+    int64_t peak_bin, peak_code, peak_code_end;
+    int32_t peak_group, reserved;
+    double peak_ratio, peak_value;
+} sdr_deep_result;
+int sdr_acq_deep(sdr_engine* e, const int32_t* code_slots, int n_prn, int64_t start_sample, const sdr_deep_cfg* cfg,
+                 sdr_deep_result* results, double* corr_map /* nullable [n_prn][groups][bins][N] */);
+/* q[b][i] above for b = bin, i = block (host helper like sdr_pcps_bins; block = noncoh gives the shift of peak_code_end;
+ * 0 for a NULL cfg, a negative bin or block, or carrier_rf_hz == 0). */
+int64_t sdr_acq_deep_shift(const sdr_deep_cfg* cfg, int bin, int64_t block);
 
 /* ------------------------------------------------- closed-loop tracking
  * On-device loop closure: one persistent workgroup per

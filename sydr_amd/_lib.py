@@ -54,6 +54,18 @@ REFINE_RESULT_DTYPE = np.dtype([("fine_hz", np.float64), ("power", np.float64), 
                                 ("fine_idx", np.int32), ("bit_edge", np.int32)], align=True)
 
 
+class DeepCfg(C.Structure):
+    """sdr_deep_cfg (include/sydr_amd.h)."""
+    _fields_ = [("fs", C.c_double), ("if_hz", C.c_double), ("doppler_range", C.c_double), ("doppler_step", C.c_double),
+                ("carrier_rf_hz", C.c_double), ("coh", C.c_int32), ("noncoh", C.c_int32), ("groups", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+DEEP_RESULT_DTYPE = np.dtype([("peak_bin", np.int64), ("peak_code", np.int64), ("peak_code_end", np.int64),
+                              ("peak_group", np.int32), ("reserved", np.int32), ("peak_ratio", np.float64),
+                              ("peak_value", np.float64)], align=True)
+
+
 class IqPacking(C.Structure):
     """sdr_iq_packing (include/sydr_amd.h): bits per component, SDR_PACK_* flags, the table of levels."""
     _fields_ = [("bits", C.c_int32), ("flags", C.c_int32), ("levels", C.c_int8 * 16)]
@@ -211,6 +223,8 @@ _PROTOTYPES = {
                                           C.POINTER(C.c_double)]),
     "sdr_acq_refine_bins": (C.c_int, [C.c_double, C.c_double]),
     "sdr_acq_refine": (C.c_int, [_VP, _VP, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double, _VP, _VP, _VP]),
+    "sdr_acq_deep": (C.c_int, [_VP, _VP, C.c_int, C.c_int64, C.POINTER(DeepCfg), _VP, _VP]),
+    "sdr_acq_deep_shift": (C.c_int64, [C.POINTER(DeepCfg), C.c_int, C.c_int64]),
     "sdr_corr_profile": (C.c_int, [_VP, _VP, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, _VP]),
     "sdr_iq_probe": (C.c_int, [_VP, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_double, C.POINTER(ProbeResultC), _VP, _VP]),
     "sdr_track_cluster": (C.c_int, [_VP, C.c_int]),

@@ -669,7 +669,8 @@ class ChannelManager:
 
     def _acquire(self, acquiring):
         """Channels with enough samples for their search, grouped by search geometry: ONE sdr_pcps call per group
-        (the forward transforms of the Doppler-mixed slab are shared by all PRNs).  Plugins that replace the
+        (the forward transforms of the Doppler-mixed slab are shared by all PRNs) -- ONE sdr_acq_deep call for a group
+        configured for the deep search (`bit_edge_groups` / `code_doppler_compensation`).  Plugins that replace the
         search seam (e.g. the SerialSearch plugin) run their own.  Channels configured for the fine frequency search
         (`fine_frequency_ms`) wait for its window as well, and a group's channels are refined in ONE sdr_acq_refine call
         behind their search."""
@@ -684,19 +685,30 @@ class ChannelManager:
             r = ch.acquisitionRequest()
             fine = (ch.acq_fineFrequencyMs, ch.acq_fineFrequencyStep, ch.FINE_FREQUENCY_SEGMENTS) \
                 if getattr(ch, "fineFrequencySearch", False) else None
-            key = (r["start"], r["fs"], r["if_hz"], r["doppler_range"], r["doppler_step"], r["coh"], r["noncoh"], fine)
+            deep = getattr(ch, "acq_deep", None)       # (bit-edge groups, carrier_rf_hz): the deep search, tracked.py
+            key = (r["start"], r["fs"], r["if_hz"], r["doppler_range"], r["doppler_step"], r["coh"], r["noncoh"], fine, deep)
             groups.setdefault(key, []).append(ch)
-        for (start, fs, if_hz, rng, step, coh, noncoh, fine), chans in groups.items():
-            pb, pc, pr, cmap = self.engine.pcps([c.codeSlot for c in chans], start, fs, if_hz, rng, step, coh, noncoh,
-                                                want_map=self.keepCorrelationMap)
+        for (start, fs, if_hz, rng, step, coh, noncoh, fine, deep), chans in groups.items():
+            rows = None
+            if deep is None:
+                pb, pc, pr, cmap = self.engine.pcps([c.codeSlot for c in chans], start, fs, if_hz, rng, step, coh, noncoh,
+                                                    want_map=self.keepCorrelationMap)
+                code_start = pc
+            else:
+                rows, gmap = self.engine.acq_deep([c.codeSlot for c in chans], start, fs, if_hz, rng, step, coh, noncoh,
+                                                  deep[0], deep[1], want_map=self.keepCorrelationMap)
+                pb, pc, pr, code_start = rows["peak_bin"], rows["peak_code"], rows["peak_ratio"], rows["peak_code_end"]
+                cmap = [gmap[k][int(rows["peak_group"][k])] for k in range(len(chans))] if gmap is not None else None
             refined = None
             if fine is not None:
-                reqs = [ch.fineFrequencyRequest([int(pb[k]), int(pc[k])]) for k, ch in enumerate(chans)]
+                reqs = [ch.fineFrequencyRequest([int(pb[k]), int(code_start[k])]) for k, ch in enumerate(chans)]
                 items = make_refine_items(*([q[name] for q in reqs] for name in ("code_slot", "start_sample", "carrier_hz", "code_hz")))
                 # (the fine grid spans +-one bin of the search: noise may have picked the bin next to the nearest)
                 refined = self.engine.acq_refine(items, fs, n_periods=fine[0], n_segments=fine[2], span_hz=step, step_hz=fine[1])
             for k, ch in enumerate(chans):
                 ch._injectedAcquisition = (cmap[k] if cmap is not None else None, [int(pb[k]), int(pc[k])], float(pr[k]))
+                if rows is not None:
+                    ch._acqDeep = rows[k]
                 if refined is not None:
                     ch._injectedFine = refined[k]
                 packets.append(ch.runAcquisition())

@@ -24,6 +24,8 @@ class GpuCorrelatorSeams:
     codeSlot = None          # staged PRN replica of this channel (set by the manager or lazily)
     _injectedCorrelators = None   # set by a batching manager: this epoch's [IE,QE,IP,QP,IL,QL]
     _injectedAcquisition = None   # set by a batching manager: (map or None, [bin, code], ratio)
+    acq_deep = None               # (bit-edge groups, carrier_rf_hz) of a channel configured for the deep search (tracked.py)
+    _acqDeep = None               # ... its sdr_deep_result row of the search that just ran
 
     # ------------------------------------------------------------------ plumbing
     def _engine(self):
@@ -71,6 +73,15 @@ class GpuCorrelatorSeams:
             return cmap
         eng = self._ensure_code()
         start = self._stage_slice(eng, self.currentSample, self.acq_requiredSamples)
+        if self.acq_deep is not None:
+            res, cmap = eng.acq_deep([self.codeSlot], start, self.rfSignal.samplingFrequency, self.rfSignal.interFrequency,
+                                     self.acq_dopplerRange, self.acq_dopplerSteps, self.acq_coherentIntegration,
+                                     self.acq_nonCoherentIntegration, *self.acq_deep, want_map=True)
+            self._acqDeep = res[0]
+            self._acqMap = cmap[0][int(res[0]["peak_group"])]
+            self._acqPeak = [int(res[0]["peak_bin"]), int(res[0]["peak_code"])]
+            self._acqRatio = float(res[0]["peak_ratio"])
+            return self._acqMap
         pb, pc, pr, cmap = eng.pcps([self.codeSlot], start, self.rfSignal.samplingFrequency,
                                     self.rfSignal.interFrequency, self.acq_dopplerRange, self.acq_dopplerSteps,
                                     self.acq_coherentIntegration, self.acq_nonCoherentIntegration, want_map=True)

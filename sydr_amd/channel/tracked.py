@@ -18,7 +18,7 @@ from __future__ import annotations
 import numpy as np
 
 from ..engine import make_items, make_refine_items
-from ..utils.constants import GPS_L1CA_CODE_FREQ, GPS_L1CA_CODE_MS, GPS_L1CA_CODE_SIZE_BITS, LNAV_MS_PER_BIT
+from ..utils.constants import GPS_L1CA_CARRIER_FREQ, GPS_L1CA_CODE_FREQ, GPS_L1CA_CODE_MS, GPS_L1CA_CODE_SIZE_BITS, LNAV_MS_PER_BIT
 from ..utils.devicering import CircularBuffer as DeviceRing
 from ..utils.enumerations import ChannelMessage, ChannelState, GNSSSignalType, GNSSSystems, TrackingFlags
 from .bank import tracking_packet
@@ -109,6 +109,22 @@ class DeviceTrackedChannel(GpuCorrelatorSeams, Channel, metaclass=_ViewMeta):
             raise ValueError(f"the ring holds {self.rfBuffer.maxSize} samples; the search and the fine frequency window behind it "
                              f"need {self.acq_waitSamples} (a longer ring_ms, or a shorter fine_frequency_ms)")
         self._acqFine = None
+        # optional (no counterpart in the reference): the deep search (sdr_acq_deep) in place of sdr_pcps when either key
+        # is present -- `bit_edge_groups` (1 or 2 interleaved sets of coherent blocks, so that with blocks of half a data
+        # bit one set holds no bit edge) and `code_doppler_compensation` (0 or 1: every block's map moved back by the
+        # code's drift at the bin's Doppler, scaled by the L1 carrier).  coherent_integration / non_coherent_integration
+        # keep their meaning.  Both absent: sdr_pcps, as the reference searches.
+        self.acq_deep = None
+        if 'bit_edge_groups' in configuration or 'code_doppler_compensation' in configuration:
+            groups = int(configuration.get('bit_edge_groups', 1))
+            compensate = int(configuration.get('code_doppler_compensation', 0))
+            if groups not in (1, 2) or compensate not in (0, 1):
+                raise ValueError("bit_edge_groups must be 1 or 2 and code_doppler_compensation 0 or 1")
+            if not 1 <= self.acq_coherentIntegration <= LNAV_MS_PER_BIT or self.acq_nonCoherentIntegration < groups:
+                raise ValueError(f"the deep search takes coherent_integration in 1..{LNAV_MS_PER_BIT} and at least "
+                                 "bit_edge_groups non-coherent blocks")
+            self.acq_deep = (groups, GPS_L1CA_CARRIER_FREQ if compensate else 0.0)
+        self._acqDeep = None
 
     def setTracking(self, configuration):
         """Fill this channel's sdr_loop_cfg row and the state tracking starts from (kaplan:256-338, borre:206-259)."""
@@ -276,8 +292,11 @@ class DeviceTrackedChannel(GpuCorrelatorSeams, Channel, metaclass=_ViewMeta):
             return None
         correlationMap = self.runSignalSearch()
         indices, ratio = self.runPeakFinder(correlationMap)
-        self._acqFine = self.runFineFrequencySearch(indices) if self.fineFrequencySearch else None
-        self.postAcquisitionUpdate(indices)
+        # (the deep search's window is long enough for the code to drift: tracking starts behind the window, so it takes
+        # the code start referred to the window's end -- peak_code_end -- where the packet reports the map's own index)
+        start = indices if self._acqDeep is None else [indices[0], int(self._acqDeep["peak_code_end"])]
+        self._acqFine = self.runFineFrequencySearch(start) if self.fineFrequencySearch else None
+        self.postAcquisitionUpdate(start)
         return self.prepareResultsAcquisition(correlationMap, indices, ratio)
 
     def trackingStart(self, acqIndices):
@@ -335,6 +354,9 @@ class DeviceTrackedChannel(GpuCorrelatorSeams, Channel, metaclass=_ViewMeta):
                       correlation_map=correlationMap, peak_ratio=acqPeakRatio)
         if self._acqFine is not None:
             packet.update(fine_frequency_idx=int(self._acqFine["fine_idx"]), bit_edge=int(self._acqFine["bit_edge"]))
+        if self._acqDeep is not None:                    # (correlation_map is the winning group's)
+            packet.update(bit_edge_group=int(self._acqDeep["peak_group"]))
+            self._acqDeep = None
         return packet
 
     # ------------------------------------------------------------------ tracking = one device step

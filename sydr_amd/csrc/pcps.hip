@@ -17,6 +17,7 @@
 #include <chrono>
 #include "sincos_reduced.h"
 #include "pcps_codelets.h"
+#include "acq_deep.h"
 
 #include <cmath>
 #include <cstring>
@@ -1530,6 +1531,108 @@ int run_map(sdr_engine* e, const PcpsPlan& p, const PcpsCall& c) {
     return SDR_OK;
 }
 
+// ---- the deep search (sdr_acq_deep): coherent blocks folded in front of ONE forward transform per (bin, block), the blocks'
+// magnitudes added into their bit-edge group's map at the code-Doppler shift of (bin, block).  The transforms, the code spectra
+// and the peak kernels are the map route's (run_map with coh = 1: the same instantiations); the fold and the shifted
+// accumulation are acq_deep.hip's.  The shifted accumulation is a kernel of its own behind the inverse sweep's magnitude store
+// (STORE_MAG_ACC into a scratch row per transform), not a store mode of the sweep's last pass: that costs one more read and
+// write of pc * nbins * N doubles per block and sweep -- a sixth of what the sweep itself moves through HBM (its column kernel
+// writes and its row kernel reads 16 N bytes per transform, the operands come on top) -- and leaves every existing kernel,
+// the register-resident ones included, as it is; their stores go out in 64-byte runs of one map row, which a per-row offset
+// would break at the wrap.
+struct DeepCall {
+    int64_t start = 0;
+    double if_hz = 0.0;
+    int coh = 1, noncoh = 1, groups = 1;
+    const int32_t* q = nullptr;      // device: [noncoh][nbins] shifts, each in [0, N)
+    double2* fold = nullptr;         // [nbins][N]
+    double* mag = nullptr;           // [prn_chunk][nbins][N]
+};
+
+__global__ __launch_bounds__(64) void deep_peak_value_kernel(const double* __restrict__ map, long long per_prn, int N, int n_prn,
+                                                             const long long* __restrict__ row, const long long* __restrict__ code,
+                                                             double* __restrict__ value) {
+    const int p = blockIdx.x * 64 + threadIdx.x;
+    if (p < n_prn) value[p] = map[(size_t)p * per_prn + (size_t)row[p] * N + code[p]];
+}
+
+int run_deep(sdr_engine* e, const PcpsPlan& p, const PcpsCall& c, const DeepCall& d) {
+    const int n_prn = p.n_prn, nbins = p.nbins, N = p.N, G = d.groups;
+    double2* A = (double2*)e->pcps_a.ptr;
+    double2* B = (double2*)e->pcps_b.ptr;
+    double* map = (double*)e->pcps_map.ptr;        // [n_prn][G][nbins][N]
+    for (int i = 0; i < d.noncoh; ++i) {
+        if (int rc = sdr_deep_fold(e, d.start + (int64_t)i * d.coh * N, N, d.coh, nbins, p.fs, d.if_hz, p.bin_start, p.bin_delta,
+                                   d.fold))
+            return rc;
+        PassArgs f = {};
+        f.tw = (const double2*)e->pcps_tw.ptr;
+        f.N = N;
+        f.in = d.fold;
+        run_fft<false, LOAD_PLAIN, STORE_PLAIN, SDR_FMT_CF64>(e, p.xf, f, nbins, A, B, (double2*)e->pcps_fwd.ptr, "deep_fwd_fft", c.blu);
+        for (int p0 = 0; p0 < n_prn; p0 += p.prn_chunk) {
+            const int pc = std::min(n_prn - p0, p.prn_chunk);
+            PassArgs g = sweep_args(e, p, p0);
+            g.map = d.mag;
+            g.first_block = 1;
+            run_fft<true, LOAD_MUL_CODE, STORE_MAG_ACC, SDR_FMT_CF64>(e, p.xf, g, pc * nbins, A, B, nullptr, "deep_inv_fft", c.blu);
+            if (int rc = sdr_deep_shift_acc(e, d.mag, map + (size_t)p0 * G * nbins * N, d.q + (size_t)i * nbins, pc, nbins, N, G,
+                                            i % G, i < G ? 1 : 0))
+                return rc;
+        }
+    }
+    {
+        // rows of a PRN: (group, bin), row r = group r / nbins, bin r % nbins; the ratio stays inside the winning row
+        ProfScope ps(e, "deep_peak");
+        Best* parts = (Best*)e->pcps_part.ptr;
+        const long long per_prn = (long long)G * nbins * N;
+        hipLaunchKernelGGL(argmax_part_kernel, dim3(kPeakParts, n_prn), dim3(kThreads), 0, e->stream, map, per_prn, parts);
+        hipLaunchKernelGGL(peak_finish_kernel, dim3(n_prn), dim3(kThreads), 0, e->stream, map, G * nbins, N, p.spc, parts,
+                           c.res_bin, c.res_code, c.res_ratio);
+        hipLaunchKernelGGL(deep_peak_value_kernel, dim3((n_prn + 63) / 64), dim3(64), 0, e->stream, map, per_prn, N, n_prn,
+                           c.res_bin, c.res_code, c.res_ratio + n_prn);
+    }
+    SDR_HIP(hipGetLastError());
+    return SDR_OK;
+}
+
+// The tables a plan's transforms read, made when the code length changes: the twiddles, and for a chirp-z length the chirp,
+// the length-M twiddles and the spectra of both kernels (*blu_out: the chirp-z plan, filled where p.M is set).
+int prepare_tables(sdr_engine* e, const PcpsPlan& p, BluPlan* blu_out) {
+    const int N = p.N;
+    int rc;
+    if (e->pcps_tw_n != N) {
+        if ((rc = sdr_devbuf_reserve(e, &e->pcps_tw, p.tbytes))) return rc;
+        hipLaunchKernelGGL(twiddle_kernel, dim3((N + kThreads - 1) / kThreads), dim3(kThreads), 0, e->stream,
+                           (double2*)e->pcps_tw.ptr, N);
+        SDR_HIP(hipGetLastError());
+        e->pcps_tw_n = N;
+    }
+    if (p.M) {
+        const int M = p.M;
+        for (DevBuf* b : {&e->pcps_blu, &e->pcps_blu_x, &e->pcps_blu_a, &e->pcps_blu_b})
+            if ((rc = sdr_devbuf_reserve(e, b, b == &e->pcps_blu ? p.blu_bytes : p.blu_work_bytes))) return rc;
+        double2* chirp = (double2*)e->pcps_blu.ptr;
+        double2* spec_fwd = chirp + N;
+        double2* twM = spec_fwd + 2 * M;
+        *blu_out = {N, M, chirp, spec_fwd, spec_fwd + M, twM, (double2*)e->pcps_blu_x.ptr, (double2*)e->pcps_blu_a.ptr,
+                    (double2*)e->pcps_blu_b.ptr, &p.xm};
+        if (e->pcps_blu_n != N) {  // plan cached per code length: chirp, length-M twiddles, spectra of both kernels
+            hipLaunchKernelGGL(twiddle_kernel, dim3((M + kThreads - 1) / kThreads), dim3(kThreads), 0, e->stream, twM, M);
+            hipLaunchKernelGGL(blu_chirp_kernel, dim3((M + kThreads - 1) / kThreads), dim3(kThreads), 0, e->stream, chirp,
+                               blu_out->x, blu_out->x + M, N, M);
+            PassArgs a = {};
+            a.N = M;
+            a.tw = twM;
+            a.in = blu_out->x;  // two transforms at once: [kernel_fwd, kernel_inv] -> [spec_fwd, spec_inv] (adjacent)
+            run_fft<false, LOAD_PLAIN, STORE_PLAIN, SDR_FMT_CF64>(e, p.xm, a, 2, blu_out->a, blu_out->b, spec_fwd, "pcps_bluestein_plan");
+            SDR_HIP(hipGetLastError());
+            e->pcps_blu_n = N;
+        }
+    }
+    return SDR_OK;
+}
+
 template <int FMT>
 int pcps_search(sdr_engine* e, const PcpsPlan& p, PcpsCall& c) {
     if (int rc = code_spectra<FMT>(e, p, c)) return rc;
@@ -1621,36 +1724,8 @@ static int pcps_impl(sdr_engine* e, const int32_t* code_slots, const double* cod
     for (const auto& b : bufs)       // (0 bytes: a buffer this search does not use)
         if (b.second && (rc = sdr_devbuf_reserve(e, b.first, b.second))) return rc;
     if (e->pcps_code2.ptr != code2_before) e->pcps_code2_ok = false;
-    if (e->pcps_tw_n != N) {
-        if ((rc = sdr_devbuf_reserve(e, &e->pcps_tw, p.tbytes))) return rc;
-        hipLaunchKernelGGL(twiddle_kernel, dim3((N + kThreads - 1) / kThreads), dim3(kThreads), 0, e->stream,
-                           (double2*)e->pcps_tw.ptr, N);
-        SDR_HIP(hipGetLastError());
-        e->pcps_tw_n = N;
-    }
     BluPlan blu;
-    if (p.M) {
-        const int M = p.M;
-        for (DevBuf* b : {&e->pcps_blu, &e->pcps_blu_x, &e->pcps_blu_a, &e->pcps_blu_b})
-            if ((rc = sdr_devbuf_reserve(e, b, b == &e->pcps_blu ? p.blu_bytes : p.blu_work_bytes))) return rc;
-        double2* chirp = (double2*)e->pcps_blu.ptr;
-        double2* spec_fwd = chirp + N;
-        double2* twM = spec_fwd + 2 * M;
-        blu = {N, M, chirp, spec_fwd, spec_fwd + M, twM, (double2*)e->pcps_blu_x.ptr, (double2*)e->pcps_blu_a.ptr,
-               (double2*)e->pcps_blu_b.ptr, &p.xm};
-        if (e->pcps_blu_n != N) {  // plan cached per code length: chirp, length-M twiddles, spectra of both kernels
-            hipLaunchKernelGGL(twiddle_kernel, dim3((M + kThreads - 1) / kThreads), dim3(kThreads), 0, e->stream, twM, M);
-            hipLaunchKernelGGL(blu_chirp_kernel, dim3((M + kThreads - 1) / kThreads), dim3(kThreads), 0, e->stream, chirp,
-                               blu.x, blu.x + M, N, M);
-            PassArgs a = {};
-            a.N = M;
-            a.tw = twM;
-            a.in = blu.x;  // two transforms at once: [kernel_fwd, kernel_inv] -> [spec_fwd, spec_inv] (adjacent)
-            run_fft<false, LOAD_PLAIN, STORE_PLAIN, SDR_FMT_CF64>(e, p.xm, a, 2, blu.a, blu.b, spec_fwd, "pcps_bluestein_plan");
-            SDR_HIP(hipGetLastError());
-            e->pcps_blu_n = N;
-        }
-    }
+    if ((rc = prepare_tables(e, p, &blu))) return rc;
     // small transfers go through page-locked staging: one copy each way, no hidden synchronisation
     // page-locked: [results: bin, code, ratio per PRN][slot numbers][done words]
     if ((rc = sdr_pinned_reserve(e, &e->ctx0, p.pinned_bytes))) return rc;
@@ -1734,6 +1809,108 @@ int sdr_pcps_spectra(sdr_engine* e, const double* code_spectra, int n_prn, int n
     if (!code_spectra || n_code < 2) return sdr_fail(SDR_ERR_INVALID, "code_spectra is NULL or too short");
     return pcps_impl(e, nullptr, code_spectra, n_code, n_prn, start_sample, fs, if_hz, doppler_range, doppler_step,
                      coh, noncoh, peak_bin, peak_code, peak_ratio, corr_map, n_bins_out);
+}
+
+
+int sdr_acq_deep(sdr_engine* e, const int32_t* code_slots, int n_prn, int64_t start_sample, const sdr_deep_cfg* cfg,
+                 sdr_deep_result* results, double* corr_map) {
+    if (int rc = sdr_set_device(e)) return rc;
+    if (!code_slots || !cfg || !results) return sdr_fail(SDR_ERR_INVALID, "NULL argument");
+    if (n_prn < 1) return sdr_fail(SDR_ERR_INVALID, "no PRN to search");
+    const int C = cfg->coh, K = cfg->noncoh, G = cfg->groups;
+    if (C < 1 || C > 20) return sdr_fail(SDR_ERR_INVALID, "coh = %d outside 1..20", C);
+    if (K < 1) return sdr_fail(SDR_ERR_INVALID, "noncoh = %d < 1", K);
+    if (G < 1 || G > 2 || K < G) return sdr_fail(SDR_ERR_INVALID, "groups = %d outside 1..2 or above noncoh = %d", G, K);
+    if (!(cfg->fs > 0.0) || !std::isfinite(cfg->fs) || !std::isfinite(cfg->if_hz)) return sdr_fail(SDR_ERR_INVALID, "bad fs / if_hz");
+    if (!(cfg->carrier_rf_hz >= 0.0) || !std::isfinite(cfg->carrier_rf_hz))
+        return sdr_fail(SDR_ERR_INVALID, "carrier_rf_hz negative or not finite");
+    const int nbins = sdr_pcps_bins(cfg->doppler_range, cfg->doppler_step);
+    if (nbins <= 0 || !std::isfinite(cfg->doppler_range) || !std::isfinite(cfg->doppler_step))
+        return sdr_fail(SDR_ERR_INVALID, "empty Doppler grid");
+    if (!e->iq) return sdr_fail(SDR_ERR_STATE, "IQ ring not allocated");
+    if (!e->codes) return sdr_fail(SDR_ERR_STATE, "code slots not allocated");
+    for (int i = 0; i < n_prn; ++i)
+        if (code_slots[i] < 0 || code_slots[i] >= e->n_slots || e->code_len_host[code_slots[i]] <= 0)
+            return sdr_fail(SDR_ERR_INVALID, "PRN entry %d: code slot %d is not staged", i, code_slots[i]);
+    const int64_t N64 = (int64_t)std::nearbyint(cfg->fs * 1023.0 / 1.023e6);
+    if (N64 < 2 || N64 > (1 << 24)) return sdr_fail(SDR_ERR_UNSUPPORTED, "samples per code %lld unsupported", (long long)N64);
+    const int N = (int)N64;
+    if (start_sample < 0 || (int64_t)K > e->iq_capacity / ((int64_t)N * C))
+        return sdr_fail(SDR_ERR_RANGE, "deep acquisition needs %d x %d x %d samples from %lld, ring holds %lld", C, K, N,
+                        (long long)start_sample, (long long)e->iq_capacity);
+    if (nbins > 65535 || n_prn > 65535) return sdr_fail(SDR_ERR_UNSUPPORTED, "grid too large");
+    const double bin_start = -cfg->doppler_range;
+    const double bin_delta = (bin_start + cfg->doppler_step) - bin_start;
+    // the map route's plan of coh = 1 (transforms, PRN chunks, work buffers); the deep route's own buffers on top
+    const PcpsPlan p = plan_pcps(e, N, cfg->fs, nbins, bin_start, bin_delta, 1, K, n_prn, true);
+
+    int rc;
+    const size_t row_bytes = (size_t)nbins * N * sizeof(double);
+    const size_t res_bytes = (size_t)n_prn * 4 * sizeof(double);     // row, code, ratio, value per PRN
+    const std::pair<DevBuf*, size_t> bufs[] = {{&e->pcps_fwd, p.fwd_bytes}, {&e->pcps_a, p.work_bytes}, {&e->pcps_b, p.work_bytes},
+                                               {&e->pcps_code, p.code_bytes}, {&e->pcps_map, (size_t)n_prn * G * row_bytes},
+                                               {&e->pcps_part, p.part_bytes}, {&e->pcps_res, res_bytes + n_prn * sizeof(int32_t)},
+                                               {&e->deep_fold, 2 * row_bytes}, {&e->deep_mag, (size_t)p.prn_chunk * row_bytes},
+                                               {&e->deep_q, (size_t)K * nbins * sizeof(int32_t)}};
+    for (const auto& b : bufs)
+        if ((rc = sdr_devbuf_reserve(e, b.first, b.second))) return rc;
+    BluPlan blu;
+    if ((rc = prepare_tables(e, p, &blu))) return rc;
+    if ((rc = sdr_pinned_reserve(e, &e->ctx0, (size_t)n_prn * sizeof(int32_t)))) return rc;
+    memcpy(e->ctx0.pinned, code_slots, (size_t)n_prn * sizeof(int32_t));
+
+    // q[b][i]: made here by sdr_acq_deep_shift's one expression, reduced with Python's modulo; the device rounds nothing
+    std::vector<int32_t> q((size_t)K * nbins);
+    for (int i = 0; i < K; ++i)
+        for (int b = 0; b < nbins; ++b) {
+            const int64_t r = sdr_acq_deep_shift(cfg, b, i) % N;
+            q[(size_t)i * nbins + b] = (int32_t)(r < 0 ? r + N : r);
+        }
+    SDR_HIP(hipMemcpyAsync(e->deep_q.ptr, q.data(), q.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    SDR_HIP(hipStreamSynchronize(e->stream));      // (pageable source: complete before `q` goes)
+
+    PcpsCall c;
+    c.slots = code_slots;
+    c.slots_pinned = (const int32_t*)e->ctx0.pinned;
+    c.d_slots = (int32_t*)((char*)e->pcps_res.ptr + res_bytes);
+    c.res_bin = (long long*)e->pcps_res.ptr;
+    c.res_code = c.res_bin + n_prn;
+    c.res_ratio = (double*)(c.res_code + n_prn);
+    c.blu = p.M ? &blu : nullptr;
+    DeepCall d;
+    d.start = start_sample;
+    d.if_hz = cfg->if_hz;
+    d.coh = C, d.noncoh = K, d.groups = G;
+    d.q = (const int32_t*)e->deep_q.ptr;
+    d.fold = (double2*)e->deep_fold.ptr;
+    d.mag = (double*)e->deep_mag.ptr;
+    {
+        ProfScope whole(e, "call_acq_deep");
+        rc = code_spectra<SDR_FMT_CF64>(e, p, c);
+        if (!rc) rc = run_deep(e, p, c, d);
+    }
+    if (rc) {
+        e->pcps_spec_key.clear();      // (a search that stopped half way: what the code-spectra buffer holds is unknown)
+        return rc;
+    }
+    std::vector<long long> host(4 * (size_t)n_prn);
+    SDR_HIP(hipMemcpyAsync(host.data(), e->pcps_res.ptr, res_bytes, hipMemcpyDeviceToHost, e->stream));
+    if (corr_map)
+        SDR_HIP(hipMemcpyAsync(corr_map, e->pcps_map.ptr, (size_t)n_prn * G * row_bytes, hipMemcpyDeviceToHost, e->stream));
+    SDR_HIP(hipStreamSynchronize(e->stream));
+    for (int i = 0; i < n_prn; ++i) {
+        sdr_deep_result& r = results[i];
+        const long long row = host[(size_t)i];
+        r.peak_group = (int32_t)(row / nbins);
+        r.reserved = 0;
+        r.peak_bin = row % nbins;
+        r.peak_code = host[(size_t)n_prn + i];
+        memcpy(&r.peak_ratio, &host[2 * (size_t)n_prn + i], sizeof(double));
+        memcpy(&r.peak_value, &host[3 * (size_t)n_prn + i], sizeof(double));
+        const int64_t end = (r.peak_code + sdr_acq_deep_shift(cfg, (int)r.peak_bin, K)) % N;
+        r.peak_code_end = end < 0 ? end + N : end;
+    }
+    return SDR_OK;
 }
 
 }  // extern "C"

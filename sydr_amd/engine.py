@@ -634,6 +634,25 @@ class Engine:
                                        ptr(z) if want_tables else None))
         return (res, power, z) if want_tables else res
 
+    def acq_deep(self, code_slots, start_sample, fs, if_hz, doppler_range, doppler_step, coh, noncoh, groups=1,
+                 carrier_rf_hz=0.0, want_map=False):
+        """The deep search (sdr_acq_deep): coherent blocks of `coh` code periods folded in front of one transform, `noncoh`
+        blocks added into `groups` bit-edge groups at the code-Doppler shift `carrier_rf_hz` gives (0: none).
+        -> (results: DEEP_RESULT_DTYPE records -- peak_bin, peak_code, peak_code_end, peak_group, peak_ratio, peak_value --
+        one per slot, map float64[n][groups][bins][N] or None)."""
+        slots = np.ascontiguousarray(code_slots, dtype=np.int32)
+        n = len(slots)
+        cfg = _lib.DeepCfg(float(fs), float(if_hz), float(doppler_range), float(doppler_step), float(carrier_rf_hz),
+                           int(coh), int(noncoh), int(groups), 0)
+        res = np.zeros(n, dtype=_lib.DEEP_RESULT_DTYPE)
+        cmap = None
+        if want_map:
+            nbins = max(0, self._lib.sdr_pcps_bins(float(doppler_range), float(doppler_step)))
+            cmap = np.empty((n, max(0, int(groups)), nbins, int(round(fs * 1023 / 1.023e6))), dtype=np.float64)
+        check(self._lib.sdr_acq_deep(self._h, ptr(slots), n, int(start_sample), C.byref(cfg), ptr(res),
+                                     ptr(cmap) if want_map else None))
+        return res, cmap
+
     def two_peak_compare_ss(self, cmap: np.ndarray):
         cmap = np.ascontiguousarray(cmap, dtype=np.float64)
         pb, pc, pr = C.c_int64(0), C.c_int64(0), C.c_double(0)
