@@ -2,7 +2,7 @@
 """Track an IQ recording with the reference's own configuration files.
 
     python examples/run_file.py receiver.ini [--ms 2000] [--block 80 | --read-ahead 50] [--csv out.csv]
-                                              [--profile N_TAPS] [--probe]
+                                              [--profile N_TAPS] [--probe] [--search-behind PRN,PRN,...]
 
 `receiver.ini` is the reference's receiver configuration (config/receiver.ini: [DEFAULT] nb_channels /
 ms_to_process, [RFSIGNAL], [SATELLITES] include_prn, [CHANNELS] gps_l1ca = <channel ini>).  What the reference's
@@ -15,7 +15,11 @@ manager tracks N ms ahead behind it (`enableReadAhead`).  Subframes the channels
 measurements, database and report stay the reference's business (feed them the packets this script prints / writes).
 `--probe` looks at the front end first: the first second of the recording goes into a ring of its own length and
 `Engine.iq_probe` says what it holds -- levels, rails, DC offset, I/Q imbalance, the histogram's occupied bins, the noise
-floor and the bins that stand out of the spectrum -- before any channel is started."""
+floor and the bins that stand out of the spectrum -- before any channel is started.
+`--search-behind 4,9,30` ends with a search for those PRNs BEHIND the tracked ones: 20 more milliseconds go through
+`ChannelManager.searchBehindTracked`, which tracks them as a block, subtracts every tracked signal's replica from those
+samples into a second engine (`sdr_iq_cancel`) and searches the residue over 10 non-coherent milliseconds -- a PRN 24 dB or
+more under a tracked one shows there and not in a search of the samples as they came."""
 import argparse
 import configparser
 import os
@@ -68,6 +72,8 @@ def main(argv=None):
     ap.add_argument("--csv", default=None, help="write one line per tracking epoch")
     ap.add_argument("--profile", type=int, default=0, metavar="N_TAPS",
                     help="print |correlation function| of every channel's last epoch at the end: N_TAPS taps across +-2 chips")
+    ap.add_argument("--search-behind", default="", metavar="PRNS",
+                    help="at the end: search these PRNs (comma separated) in 20 ms with the tracked signals cancelled")
     ap.add_argument("--probe", action="store_true", help="print what the first second of the recording holds (Engine.iq_probe) before tracking")
     args = ap.parse_args(argv)
 
@@ -125,6 +131,16 @@ def main(argv=None):
             emit(mgr.run(), ms + 1)
             ms += 1
     dt = time.perf_counter() - t0
+    behind = [int(p) for p in args.search_behind.split(",") if p.strip()]
+    if behind and 20 < ring_ms - 2:
+        for _ in range(20):
+            mgr.addNewRFData(rf.getMilliseconds(1))
+        packets, rows = mgr.searchBehindTracked(behind, 20, dict(doppler_range=5000.0, doppler_step=250.0, coh=1, noncoh=10))
+        emit(packets, ms + 20)
+        ms += 20
+        for r in rows:
+            print(f"behind the tracked signals: G{r['satelliteID']:02d} bin {r['peak_bin']} ({r['doppler_hz']:+.0f} Hz) code {r['peak_code']} "
+                  f"ratio {r['peak_ratio']:.2f} from sample {r['start_sample']}")
     for ch in mgr.channels.values():
         if ch.channelState is not ChannelState.IDLE:
             bits = "".join(str(int(b)) for b in getattr(ch, "navBits", [])[:40])

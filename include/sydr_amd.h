@@ -39,7 +39,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define SDR_ABI_VERSION 5   /* 5 (still): + sdr_acq_deep, sdr_acq_deep_shift (additive); 5 (still): + sdr_ddc_cfg, sdr_ddc_create / _destroy / _reset / _push / _push_queue / _out_count (additive); 5 (still): + sdr_iq_probe (additive); 5 (still): + sdr_corr_profile, option "corr_profile_per_sample" (additive); 5 (still): + sdr_iq_packing, sdr_iq_packed_bytes, sdr_iq_upload_packed / _begin / _queue (additive); 5 (still): + sdr_acq_refine, sdr_acq_refine_bins (additive); 5: + sdr_bank_tick_mirrored_begin / _end, sdr_iq_upload_queue, sdr_host_alloc / _free, options "tick_server" + sdr_tick_server_stats, "bind_thread_to_device" (additive); 4: + sdr_build_id, sdr_epl_plan_create_dev, sdr_bank_tick_mirrored, sdr_iq_upload_begin, sdr_block_schedule, sdr_bank_step_begin / _end (additive) */
+#define SDR_ABI_VERSION 5   /* 5 (still): + sdr_iq_cancel, sdr_cancel_stats (additive); 5 (still): + sdr_acq_deep, sdr_acq_deep_shift (additive); 5 (still): + sdr_ddc_cfg, sdr_ddc_create / _destroy / _reset / _push / _push_queue / _out_count (additive); 5 (still): + sdr_iq_probe (additive); 5 (still): + sdr_corr_profile, option "corr_profile_per_sample" (additive); 5 (still): + sdr_iq_packing, sdr_iq_packed_bytes, sdr_iq_upload_packed / _begin / _queue (additive); 5 (still): + sdr_acq_refine, sdr_acq_refine_bins (additive); 5: + sdr_bank_tick_mirrored_begin / _end, sdr_iq_upload_queue, sdr_host_alloc / _free, options "tick_server" + sdr_tick_server_stats, "bind_thread_to_device" (additive); 4: + sdr_build_id, sdr_epl_plan_create_dev, sdr_bank_tick_mirrored, sdr_iq_upload_begin, sdr_block_schedule, sdr_bank_step_begin / _end (additive) */
 
 typedef struct sdr_engine sdr_engine;
 
@@ -274,6 +274,55 @@ int sdr_two_peak_compare_ss(sdr_engine* e, const double* corr_map, int n_rows, i
 #define SDR_CORR_MAX_TAPS 1024
 int sdr_corr_profile(sdr_engine* e, const sdr_epl_item* items, int n_items, double first_chips, double step_chips,
                      int n_taps, double fs, double* out /* [n_items][n_taps][2] = I, Q */);
+
+/* ------------------------------------------- successive interference cancellation on the ring
+ * The Gold codes isolate one C/A signal from another by only ~24 dB: a satellite tracked at 50 dB-Hz leaves cross-correlation
+ * peaks in every other PRN's search map as high as the peak of a signal 24 dB weaker.  The remedy: rebuild each strongly
+ * tracked signal from what its loop already knows -- the NCO inputs of every epoch (an sdr_epl_item) and a complex amplitude
+ * per epoch --, subtract it from the samples and search in the residue (sdr_pcps / sdr_acq_deep).
+ * items[n_ch][n_epochs], amps[n_ch][n_epochs][2] = (a_re, a_im), 1 <= n_ch <= SDR_CANCEL_MAX_CHANNELS; the window is ring
+ * samples window_start .. window_start + W - 1 (W = window_samples; it may cross the ring's end).  For an item with
+ * n = n_samples, L chips c staged in its slot and A = a_re + j*a_im, sample i = 0..n-1 of the item gets the prompt tap of EPL
+ * above (sydr/dsp/tracking.py:92-116: lines 102-104 the replica, 111-112 the chip index), in the reference's operation order:
+ *   t_i     = np.arange(0.0, n) / fs
+ *   theta_i = -(carrier_hz * 2.0 * np.pi * t_i) + rem_carrier
+ *   idx_i   = ceil(linspace(rem_code + 0.0, code_step*n + rem_code + 0.0, n, endpoint=False))
+ *   chip_i  = c[(idx_i - 1) mod L]                                              (Python's modulo, any idx)
+ *   r_re    = chip_i * (a_re*cos(theta_i) + a_im*sin(theta_i))
+ *   r_im    = chip_i * (a_im*cos(theta_i) - a_re*sin(theta_i))                  (A * chip * conj(replica))
+ * every product and sum in fp64 exactly as written (the library is built without contraction).  An item sits at window
+ * offset off = (start_sample - window_start) mod capacity and lies wholly inside the window (off + n <= W); within a channel
+ * the offsets ascend and do not overlap, gaps are allowed, items with n_samples == 0 are padding and are skipped.  A window
+ * sample m with ring value x widened to fp64 becomes
+ *   y = x;  for ch = 0 .. n_ch-1 in this order:  if an item of ch covers m:  y_re -= r_re;  y_im -= r_im
+ * and is stored in the ring's format: cf64 as it is, cf32 rounded to nearest, ci8 / ci16 by sdr_ddc_push's rule (rint,
+ * clipped to +-127 / +-32767).  A sample no item covers is copied as it is.  A NaN or Inf input sample stays non-finite and
+ * affects no other sample.  The least-squares amplitude of an epoch is its prompt over n_samples (it carries the data
+ * bit's sign and the carrier phase): the prompt of the same item on the cancelled samples is then zero to rounding.
+ * dst == NULL, or dst == e with dst_offset == window_start (modulo the capacity): the window is replaced in place.  Any
+ * other dst -- another engine on the same device with a ring of the same format, or a window of e's own ring that shares no
+ * sample with the source window --: the cancelled window goes to dst's ring at dst_offset, wrapping there too, and the
+ * source window stays as it is (a live receiver's trackers keep reading the original ring, its searches run on the second
+ * engine).  The call waits for dst's stream, runs on e's stream and returns when it is done, like sdr_corr_profile.  Every
+ * output sample is written by exactly one thread, which has read its own input first; no atomics touch the samples: two
+ * identical calls return identical bits, in place is safe.
+ * stats (nullable): samples_written = W, samples_changed = samples at least one item covers, clipped_components = components
+ * of an integer ring whose rounded value lay beyond a rail -- exact, equal to the NumPy statement's
+ * (sydr_amd/signal/cancel.py: cancel_statement).
+ * SDR_ERR_INVALID: NULL items / amps, n_ch outside 1..64, n_epochs < 1, window_samples < 1, fs <= 0, non-finite amplitudes
+ * or NCO parameters, code_step <= 0, n_samples < 0, a slot that is not staged, items of a channel that overlap or do not
+ * ascend, dst == e with a different window that overlaps the source window, a dst on another device or with a ring of another
+ * format; SDR_ERR_RANGE: a window longer than either ring, a negative window_start / dst_offset / start_sample, an item not
+ * wholly inside the window; SDR_ERR_UNSUPPORTED: a chip index that would leave +-2^30; SDR_ERR_STATE: no ring (either
+ * engine) or no code slots.  A refused call writes nothing.
+ * sdr_prof_enable scopes: "cancel_items_upload", "cancel_kernel", "call_iq_cancel". */
+#define SDR_CANCEL_MAX_CHANNELS 64
+typedef struct sdr_cancel_stats {
+    int64_t samples_written, samples_changed, clipped_components;
+} sdr_cancel_stats;
+int sdr_iq_cancel(sdr_engine* e, const sdr_epl_item* items /* [n_ch][n_epochs] */, const double* amps /* [n_ch][n_epochs][2] */,
+                  int n_ch, int n_epochs, double fs, int64_t window_start, int64_t window_samples,
+                  sdr_engine* dst /* nullable */, int64_t dst_offset, sdr_cancel_stats* stats /* nullable */);
 
 /* ------------------------------- fine carrier frequency and bit edge behind an acquisition
  * The step between acquisition and tracking of the textbook receiver (code wipe-off over ~10 ms, a fine frequency

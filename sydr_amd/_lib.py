@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("SYDR_AMD_LIB") or os.path.join(_HERE, "libsydr_amd.so
 
 SDR_MAX_TAPS = 8
 SDR_CORR_MAX_TAPS = 1024
+SDR_CANCEL_MAX_CHANNELS = 64
 FMT_CI8, FMT_CI16, FMT_CF32, FMT_CF64 = 0, 1, 2, 3
 _FMT_NP = {FMT_CI8: np.int8, FMT_CI16: np.int16, FMT_CF32: np.float32, FMT_CF64: np.float64}
 
@@ -64,6 +65,11 @@ class DeepCfg(C.Structure):
 DEEP_RESULT_DTYPE = np.dtype([("peak_bin", np.int64), ("peak_code", np.int64), ("peak_code_end", np.int64),
                               ("peak_group", np.int32), ("reserved", np.int32), ("peak_ratio", np.float64),
                               ("peak_value", np.float64)], align=True)
+
+
+class CancelStats(C.Structure):
+    """sdr_cancel_stats (include/sydr_amd.h): what sdr_iq_cancel wrote, changed and clipped."""
+    _fields_ = [("samples_written", C.c_int64), ("samples_changed", C.c_int64), ("clipped_components", C.c_int64)]
 
 
 class IqPacking(C.Structure):
@@ -226,6 +232,8 @@ _PROTOTYPES = {
     "sdr_acq_deep": (C.c_int, [_VP, _VP, C.c_int, C.c_int64, C.POINTER(DeepCfg), _VP, _VP]),
     "sdr_acq_deep_shift": (C.c_int64, [C.POINTER(DeepCfg), C.c_int, C.c_int64]),
     "sdr_corr_profile": (C.c_int, [_VP, _VP, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, _VP]),
+    "sdr_iq_cancel": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_double, C.c_int64, C.c_int64, _VP, C.c_int64,
+                                C.POINTER(CancelStats)]),
     "sdr_iq_probe": (C.c_int, [_VP, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_double, C.POINTER(ProbeResultC), _VP, _VP]),
     "sdr_track_cluster": (C.c_int, [_VP, C.c_int]),
     "sdr_track_closed_loop": (C.c_int, [_VP, C.c_int, _VP, C.POINTER(LoopCfg), C.c_int, _VP]),

@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from .._lib import EPL_ITEM_DTYPE
 from ..engine import FMT_CF64, FMT_CI16, FMT_CI8, Engine, make_items, make_refine_items
 from ..utils.devicering import CircularBuffer
 from ..utils.enumerations import ChannelState
@@ -511,6 +512,9 @@ class ChannelManager:
         if self.bank is not None:
             self.bank.close()
             self.sharedBuffer.channelBank = None
+        if getattr(self, "_searchEngine", None) is not None:      # (searchBehindTracked's second engine)
+            self._searchEngine.close()
+            self._searchEngine = None
 
     # ------------------------------------------------------------------ the tick
     def run(self):
@@ -721,6 +725,10 @@ class ChannelManager:
         Each channel runs as many whole epochs as the ring already holds for it (at most nbEpochs): nothing is
         read that has not been written.  Returns the per-epoch TRACKING_UPDATE packets, channel by channel, epoch
         by epoch, followed by one CHANNEL_UPDATE per tracking channel."""
+        return self._run_block(nbEpochs, None)
+
+    def _run_block(self, nbEpochs: int, ran):
+        """runBlock; `ran` (a list or None) collects (channel, n_taps, its records that ran) for searchBehindTracked."""
         self._flush_pending()
         if (self._readahead is not None and (self._readahead.slabs_left or not self._readahead.empty)) or self._ahead is not None:
             raise RuntimeError("runBlock while a read-ahead block is being replayed or tracked ahead: finish its ticks first")
@@ -742,6 +750,8 @@ class ChannelManager:
             kinds = bank.cfg["loop_kind"][members]
             decoded = {(c, e): pkt for c, e, pkt in bank.take_decoded()}
             flat = []
+            if ran is not None:
+                ran.extend((self.channels[int(c)], int(bank.cfg["n_taps"][c]), rec[r, :done[r]].copy()) for r, c in enumerate(members))
             for r, (c, k) in enumerate(zip(members, kinds)):
                 for e in range(done[r]):
                     flat.append((int(c), int(k), rec[r, e]))
@@ -750,6 +760,74 @@ class ChannelManager:
             out.add(len(flat), lambda i, flat=flat: flat[i] if isinstance(flat[i], dict) else tracking_packet(*flat[i]))
         out.add_ready(ch.prepareChannelUpdate() for ch in chans)
         return out
+
+    # ------------------------------------------------------------------ searching behind the tracked signals
+    def _make_search_engine(self):
+        """The second engine searchBehindTracked searches on -- on this manager's device; a seam: a test injects a fake by
+        replacing this method."""
+        return Engine(getattr(self.engine, "device_id", 0))
+
+    def searchBehindTracked(self, satelliteIDs, nbEpochs: int, search: dict, minCn0=None):
+        """runBlock(nbEpochs) for the tracking channels -- the same preconditions, the same packets -- and then a search for
+        `satelliteIDs` in what is left of those samples once the channels that ran are subtracted from them (successive
+        interference cancellation: sdr_iq_cancel with each epoch's NCO inputs and its prompt over n_samples, into a second
+        engine on the same device; the ring the trackers read stays as it is).  minCn0: only channels whose last epoch
+        reports that C/N0 [dB-Hz] or more are cancelled.  search: doppler_range, doppler_step and optionally coh, noncoh
+        (Engine.pcps), with groups / carrier_rf_hz Engine.acq_deep; it starts at the first sample every cancelled channel
+        covers.  -> (packets, rows): one row per PRN with peak_bin, peak_code, peak_ratio, doppler_hz.  Starts no channel: the
+        caller decides.  ValueError when no channel is cancelled or the span they all cover is shorter than the search needs
+        (the block has run by then; its packets are in the exception's `packets`)."""
+        from ..signal import cancel as _cancel
+        ran = []
+        packets = self._run_block(nbEpochs, ran)
+
+        def refuse(text):
+            err = ValueError(text)
+            err.packets = packets
+            return err
+        ran = [(ch, nt, rec) for ch, nt, rec in ran if len(rec) and (minCn0 is None or float(rec["cn0"][-1]) >= minCn0)]
+        if not ran:
+            raise refuse("no tracking channel ran an epoch" + ("" if minCn0 is None else f" at {minCn0} dB-Hz or more"))
+        fs = self.rfSignal.samplingFrequency
+        n_epochs = max(len(rec) for _, _, rec in ran)
+        items = np.zeros((len(ran), n_epochs), dtype=EPL_ITEM_DTYPE)
+        amps = np.zeros((len(ran), n_epochs, 2))
+        for r, (ch, nt, rec) in enumerate(ran):
+            its, am, _ = _cancel.items_from_records(rec, [ch.codeSlot], n_taps=nt)
+            items[r, :len(rec)], amps[r, :len(rec)] = its[0], am[0]
+            items["code_step"][r, len(rec):] = 1.0
+        w0, W = _cancel.hull(items)
+        first = max(int(rec["start_sample"][0]) for _, _, rec in ran)
+        last = min(int(rec["start_sample"][-1]) + int(rec["n_samples"][-1]) for _, _, rec in ran)
+        deep = "groups" in search or "carrier_rf_hz" in search
+        coh, noncoh = int(search.get("coh", 1)), int(search.get("noncoh", 1))
+        need = coh * noncoh * int(round(fs * 1e-3))
+        if last - first < need:
+            raise refuse(f"the cancelled channels share {max(0, last - first)} samples, the search needs {need}")
+        if getattr(self, "_searchEngine", None) is None:
+            self._searchEngine = self._make_search_engine()
+        eng = self._searchEngine
+        if eng.iq_capacity != self.engine.iq_capacity or eng.iq_fmt != self.engine.iq_fmt:
+            eng.iq_alloc(self.engine.iq_capacity, self.engine.iq_fmt)
+        prns = [int(p) for p in satelliteIDs]
+        if getattr(eng, "n_slots", 0) < len(prns):
+            eng.code_slots(max(32, len(prns)))
+        for s, p in enumerate(prns):
+            eng.load_gps_code(s, p)
+        cap = self.engine.iq_capacity
+        self.lastCancelStats = self.engine.iq_cancel(items, amps, fs, window=(w0, W), dst=eng, dst_offset=w0 % cap)
+        self._pending = False         # (the call waited for the engine's stream: a queued slab is in the ring)
+        R, S = float(search["doppler_range"]), float(search["doppler_step"])
+        if_hz = self.rfSignal.interFrequency
+        if deep:
+            res, _ = eng.acq_deep(np.arange(len(prns)), first % cap, fs, if_hz, R, S, coh, noncoh, int(search.get("groups", 1)),
+                                  float(search.get("carrier_rf_hz", 0.0)))
+            pb, pc, pr = res["peak_bin"], res["peak_code"], res["peak_ratio"]
+        else:
+            pb, pc, pr, _ = eng.pcps(np.arange(len(prns)), first % cap, fs, if_hz, R, S, coh, noncoh)
+        rows = [dict(satelliteID=p, peak_bin=int(pb[k]), peak_code=int(pc[k]), peak_ratio=float(pr[k]),
+                     doppler_hz=-(-R + S * int(pb[k])), start_sample=first) for k, p in enumerate(prns)]
+        return packets, rows
 
 
 def _default_search():

@@ -186,6 +186,9 @@ struct sdr_engine {
 
     // sdr_ddc_push / _queue (ddc.hip)
     DevBuf ddc_stage;             // the raw inputs of a push in HBM, read by the converter's kernels behind their copy command on `stream`
+
+    // sdr_iq_cancel (cancel.hip)
+    DevBuf cancel_ws;             // [items][counts][the two counters]
 };
 
 int sdr_devbuf_reserve(sdr_engine* e, DevBuf* b, size_t bytes);

@@ -560,6 +560,40 @@ class Engine:
                                          ptr(out)))
         return out
 
+    def iq_cancel(self, items, amps=None, fs=None, window=None, dst=None, dst_offset=0) -> dict:
+        """Subtract tracked signals' replicas from a window of the ring (sdr_iq_cancel; the NumPy statement is
+        signal.cancel.cancel_statement).  items[n_ch][n_epochs] (`make_items` records; one row = one channel, epochs
+        ascending, n_samples == 0 = padding), amps[n_ch][n_epochs][2] or complex [n_ch][n_epochs] -- None: each epoch's
+        prompt over its n_samples (`epl_batch` on this ring, signal.cancel.amplitudes_from_prompts).  window = (start,
+        samples) -- None: the hull of the items.  dst None: in place; another Engine on this device (or this one, with a
+        window that shares no sample with the source's): the cancelled window goes to its ring at dst_offset and this ring
+        stays as it is.  -> the counters of sdr_cancel_stats as a dict."""
+        from .signal import cancel as _cancel
+        if fs is None:
+            raise TypeError("iq_cancel needs the sampling frequency fs")
+        items = np.ascontiguousarray(np.atleast_2d(np.asarray(items, dtype=EPL_ITEM_DTYPE)))
+        n_ch, n_epochs = items.shape
+        if amps is None:
+            flat = items.reshape(-1)
+            live = flat["n_samples"] > 0
+            prompts = np.zeros((flat.size, 2), dtype=np.float64)
+            if live.any():
+                prompts[live] = self.epl_batch(flat[live], [0.0], fs)
+            amps = _cancel.amplitudes_from_prompts(prompts, flat["n_samples"])
+        amps = np.asarray(amps)
+        if np.iscomplexobj(amps):
+            amps = np.stack([amps.real, amps.imag], axis=-1)
+        amps = np.ascontiguousarray(amps, dtype=np.float64)
+        if amps.size != 2 * items.size:
+            raise ValueError(f"amps of {amps.shape} for items of {items.shape}")
+        w0, W = _cancel.hull(items) if window is None else (int(window[0]), int(window[1]))
+        in_place = dst is None
+        stats = _lib.CancelStats()
+        check(self._lib.sdr_iq_cancel(self._h, ptr(items), ptr(amps), n_ch, n_epochs, float(fs), w0, W,
+                                      None if in_place else dst._h, w0 if in_place else int(dst_offset), C.byref(stats)))
+        return dict(samples_written=stats.samples_written, samples_changed=stats.samples_changed,
+                    clipped_components=stats.clipped_components)
+
     def epl_plan_dev(self, device_items: int, n_items: int, spacing, fs) -> EplPlan:
         """A plan of n_items items that are already in device memory at address device_items."""
         return EplPlan(self, None, spacing, fs, device_items=device_items, n_items=n_items)
