@@ -275,6 +275,57 @@ int sdr_two_peak_compare_ss(sdr_engine* e, const double* corr_map, int n_rows, i
 int sdr_corr_profile(sdr_engine* e, const sdr_epl_item* items, int n_items, double first_chips, double step_chips,
                      int n_taps, double fs, double* out /* [n_items][n_taps][2] = I, Q */);
 
+/* ------------------------------------------- a delay-Doppler map around a known code phase and carrier
+ * The search of a small neighbourhood of a state the receiver already has -- a few chips and a few hundred hertz around
+ * a code phase and a carrier: reacquisition after a short loss, a warm start from a prediction, the check that a channel
+ * sits on the main peak (not on a cross-correlation peak or a side lobe), and the data product of reflectometry.
+ * An item is an sdr_epl_item read as a PREDICTION: start_sample = s0, n_samples = W (the whole window), carrier_hz = f0,
+ * rem_carrier / rem_code / code_step = the NCO state at s0 -- what sdr_track_state holds for a channel's next epoch, with
+ * a longer n.  With B = n_blocks, S = n_segments, Q = B*S, T = n_taps, K = 2*floor(span_hz/step_hz) + 1:
+ *   Stage 1: segment q < Q covers window samples [a_q, b_q), a_q = (q*W)/Q, b_q = ((q+1)*W)/Q (64-bit integer
+ *   divisions).  z[q][j] = what EPL above returns for the single spacing s_j = first_chips + j*step_chips (fp64, one
+ *   multiply, one add) on ring samples s0+a_q .. s0+b_q-1 (modulo the capacity) with carrier_hz = f0,
+ *   rem_carrier_q = (rem_carrier + (-(f0*2.0*pi*a_q/fs))) mod 2*pi (Python's modulo: in [0, 2*pi)),
+ *   rem_code_q = rem_code + (double)a_q * code_step (the product, then the sum) and the item's code_step; a padded
+ *   index p stands for chip c[(p - 1) mod L] for ANY p, as in sdr_corr_profile.  tau_q = (a_q + b_q - 1) / 2.0 / fs.
+ *   Stage 2: d_k = (k - (K-1)/2) * step_hz.  For block b < B:
+ *   Z[b][k][j] = sum_{s<S} z[b*S+s][j] * exp(-2j*pi*d_k*tau_{b*S+s}) (s ascending),
+ *   map[k][j] = sum_{b<B} |Z[b][k][j]|^2 (b ascending): coherent inside a block, non-coherent across blocks -- choose B so
+ *   that a block is shorter than what a data bit or the frequency error allows.
+ *   Result: (peak_bin, peak_tap) = the first maximum of map in row-major (k, j) order; peak_hz = f0 + d_peak_bin,
+ *   peak_chips = s_peak_tap, peak_value = the map there.  The true code phase at s0 is rem_code + peak_chips, the true
+ *   carrier peak_hz.  second_value = the maximum of the entries whose tap lies a chip or more from the peak's
+ *   (|s_j - s_peak_tap| >= 1.0, any k), noise_mean their mean; both 0.0 when no entry qualifies.
+ * map (nullable) receives [n_items][K][n_taps], segment_sums (nullable) z as [n_items][Q][n_taps][2]; Z and the map are
+ * made on the device, the host link carries only what is asked for.  Sums are added in a fixed order, no atomics: two
+ * identical calls return identical bits.  Synchronous on the engine's stream like sdr_corr_profile; all four ring formats;
+ * a window may cross the ring's end; items of one call may have different W.  A window that holds NaN / Inf samples (a
+ * float ring) gives that item a non-finite map, peak_value = second_value = noise_mean = NaN, peak_bin = (K-1)/2,
+ * peak_tap = 0, peak_hz = f0, peak_chips = first_chips; no other item is affected.
+ * At 8 samples per chip or more a tap is summed as one term per chip run over prefix sums of the wiped samples, below
+ * that -- or with sdr_set_option(e, "ddm_per_sample", 1) -- as a term per sample: same definition, equal to rounding.
+ * sdr_ddm_bins: K of the grid (host helper like sdr_acq_refine_bins; 0 for a bad grid).
+ * SDR_ERR_INVALID: NULL items / cfg / results, n_items outside 1..65535, n_taps outside 1..SDR_CORR_MAX_TAPS, non-finite first_chips /
+ * step_chips, a bad fs, step_hz <= 0, span_hz < 0 or either non-finite, n_blocks < 1, n_segments outside 1..64,
+ * n_segments == 1 with K > 1 (one segment per block carries no frequency information: every row of the map would be
+ * equal to rounding), a slot that is not staged, n_samples < 1, code_step <= 0 or non-finite NCO parameters;
+ * SDR_ERR_UNSUPPORTED: K > 4096, Q > 4096, Q > W for some item (an empty segment), a chip index that would leave +-2^30,
+ * a code too long for the LDS; SDR_ERR_RANGE: a window longer than the ring, a negative start_sample; SDR_ERR_STATE: no
+ * ring or no code slots.  A refused call writes nothing.
+ * sdr_prof_enable scopes: "ddm_items_upload", "ddm_segments_kernel", "ddm_map_kernel", "ddm_peak_kernel", "call_ddm". */
+typedef struct sdr_ddm_cfg {
+    double fs, first_chips, step_chips, span_hz, step_hz;
+    int32_t n_taps, n_blocks, n_segments, reserved;
+} sdr_ddm_cfg;
+typedef struct sdr_ddm_result {
+    int32_t peak_bin, peak_tap;
+    double peak_hz, peak_chips, peak_value, second_value, noise_mean;
+} sdr_ddm_result;
+int sdr_ddm_bins(double span_hz, double step_hz);
+int sdr_ddm(sdr_engine* e, const sdr_epl_item* items, int n_items, const sdr_ddm_cfg* cfg, sdr_ddm_result* results,
+            double* map /* nullable [n_items][K][n_taps] */,
+            double* segment_sums /* nullable [n_items][n_blocks*n_segments][n_taps][2] */);
+
 /* ------------------------------------------- successive interference cancellation on the ring
  * The Gold codes isolate one C/A signal from another by only ~24 dB: a satellite tracked at 50 dB-Hz leaves cross-correlation
  * peaks in every other PRN's search map as high as the peak of a signal 24 dB weaker.  The remedy: rebuild each strongly

@@ -55,6 +55,27 @@ REFINE_RESULT_DTYPE = np.dtype([("fine_hz", np.float64), ("power", np.float64), 
                                 ("fine_idx", np.int32), ("bit_edge", np.int32)], align=True)
 
 
+class DdmCfg(C.Structure):
+    """sdr_ddm_cfg (include/sydr_amd.h): the tap grid, the frequency grid and the blocks / segments of a delay-Doppler map."""
+    _fields_ = [("fs", C.c_double), ("first_chips", C.c_double), ("step_chips", C.c_double), ("span_hz", C.c_double),
+                ("step_hz", C.c_double), ("n_taps", C.c_int32), ("n_blocks", C.c_int32), ("n_segments", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class DdmResult(C.Structure):
+    """sdr_ddm_result (include/sydr_amd.h): the map's first maximum and what lies a chip or more from it."""
+    _fields_ = [("peak_bin", C.c_int32), ("peak_tap", C.c_int32), ("peak_hz", C.c_double), ("peak_chips", C.c_double),
+                ("peak_value", C.c_double), ("second_value", C.c_double), ("noise_mean", C.c_double)]
+
+
+DDM_CFG_DTYPE = np.dtype([("fs", np.float64), ("first_chips", np.float64), ("step_chips", np.float64),
+                          ("span_hz", np.float64), ("step_hz", np.float64), ("n_taps", np.int32), ("n_blocks", np.int32),
+                          ("n_segments", np.int32), ("reserved", np.int32)], align=True)
+DDM_RESULT_DTYPE = np.dtype([("peak_bin", np.int32), ("peak_tap", np.int32), ("peak_hz", np.float64),
+                             ("peak_chips", np.float64), ("peak_value", np.float64), ("second_value", np.float64),
+                             ("noise_mean", np.float64)], align=True)
+
+
 class DeepCfg(C.Structure):
     """sdr_deep_cfg (include/sydr_amd.h)."""
     _fields_ = [("fs", C.c_double), ("if_hz", C.c_double), ("doppler_range", C.c_double), ("doppler_step", C.c_double),
@@ -232,6 +253,8 @@ _PROTOTYPES = {
     "sdr_acq_deep": (C.c_int, [_VP, _VP, C.c_int, C.c_int64, C.POINTER(DeepCfg), _VP, _VP]),
     "sdr_acq_deep_shift": (C.c_int64, [C.POINTER(DeepCfg), C.c_int, C.c_int64]),
     "sdr_corr_profile": (C.c_int, [_VP, _VP, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, _VP]),
+    "sdr_ddm_bins": (C.c_int, [C.c_double, C.c_double]),
+    "sdr_ddm": (C.c_int, [_VP, _VP, C.c_int, C.POINTER(DdmCfg), _VP, _VP, _VP]),
     "sdr_iq_cancel": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_double, C.c_int64, C.c_int64, _VP, C.c_int64,
                                 C.POINTER(CancelStats)]),
     "sdr_iq_probe": (C.c_int, [_VP, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_double, C.POINTER(ProbeResultC), _VP, _VP]),

@@ -150,6 +150,28 @@ class ChannelManager:
                 return channel
         raise Warning(f"Could not find an IDLE channel for tracking satellite [G{satelliteID}].")
 
+    def requestTrackingWarm(self, satelliteID: int, carrierFrequency: float, codePhaseChips: float, atSample: int, **hint):
+        """`requestTracking` with a prediction (from another channel, an earlier track, an almanac): at ring sample
+        `atSample` the satellite's code phase is `codePhaseChips` and its carrier `carrierFrequency` (IF included).  The
+        channel searches that neighbourhood (sdr_ddm) instead of the whole code period and every Doppler bin; **hint:
+        codeStep, chips, chipStep, spanHz, stepHz of `DeviceTrackedChannel.setWarmHint`."""
+        channel = self.requestTracking(satelliteID)
+        channel.setWarmHint(atSample, codePhaseChips, carrierFrequency, **hint)
+        return channel
+
+    def reacquire(self, channelID, **hint):
+        """Send a TRACKING channel (lost or not) back through a warm acquisition around its own NCO state
+        (`DeviceTrackedChannel.reacquire`): a few chips and a few hundred hertz, not a cold search.  When to call it is
+        the caller's decision -- nothing here watches the lock indicators.  Not under read-ahead (the mirror is then a
+        block ahead of what the packets have reported)."""
+        ch = self.getChannel(channelID)
+        if self._readahead is not None and not self._readahead.empty:
+            raise ValueError("reacquire while a read-ahead block is being replayed")
+        self._flush_pending()
+        ch.reacquire(**hint)
+        self._lists = None
+        return ch
+
     def enableReadAhead(self, nbMilliseconds: int = 50):
         """Serve the per-millisecond loop from blocks computed ahead (readahead.py): whenever every active channel is
         tracking and `rfSignal` is this package's file reader, the next `nbMilliseconds` of the recording are uploaded
@@ -481,6 +503,34 @@ class ChannelManager:
         self._pending = False         # (the call waited for the engine's stream: a queued slab is in the ring)
         return {cid: out[k] for k, cid in enumerate(cids)}
 
+    def delayDopplerMaps(self, nbMilliseconds: float, nbBlocks=None, nbSegments: int = 4, chips: float = 2.0,
+                         chipStep: float = 0.25, spanHz: float = 250.0, stepHz: float = 25.0):
+        """{channelID: (sdr_ddm_result row, map[K][T])}: the delay-Doppler map of every channel that is tracking and not
+        lost over its last `nbMilliseconds`, ending with its latest epoch, around its own code phase and carrier -- ONE
+        library call for all of them (sdr_ddm).  A channel on its main peak has peak_chips ~ 0 and peak_hz ~ its carrier; one
+        on a side lobe or a cross-correlation peak shows the larger peak beside it.  nbBlocks None: one block per
+        millisecond (a block then holds no data-bit edge: the window ends where an epoch ends); taps +-chips at chipStep,
+        frequencies +-spanHz at stepHz.  A channel that has run no epoch yet, or whose window the ring does not hold, has
+        no entry (as in `correlationProfiles`)."""
+        cids, rows = [], []
+        for cid, ch in self.channels.items():
+            if ch.channelState is not ChannelState.TRACKING or not hasattr(ch, "delayDopplerItem") or ch.lostLock:
+                continue
+            try:
+                rows.append(ch.delayDopplerItem(nbMilliseconds))
+            except ValueError:
+                continue
+            cids.append(cid)
+        if not cids:
+            return {}
+        blocks = max(1, int(round(nbMilliseconds))) if nbBlocks is None else int(nbBlocks)
+        half = int(np.floor(chips / chipStep))
+        items = make_items(*(np.array(col) for col in zip(*rows)))
+        res, maps, _ = self.engine.ddm(items, self.rfSignal.samplingFrequency, blocks, nbSegments, -half * chipStep, chipStep,
+                                       2 * half + 1, spanHz, stepHz)
+        self._pending = False         # (the call waited for the engine's stream: a queued slab is in the ring)
+        return {cid: (res[k], maps[k]) for k, cid in enumerate(cids)}
+
     def probeRFData(self, nbMilliseconds: int, nfft: int = 1024):
         """What the newest `nbMilliseconds` of the ring hold (CircularBuffer.probe -> signal.probe.ProbeResult): levels, rails,
         histogram, and the Welch spectrum at the recording's sampling frequency (nfft = 0: none) -- the front end looked at
@@ -678,9 +728,14 @@ class ChannelManager:
         search seam (e.g. the SerialSearch plugin) run their own.  Channels configured for the fine frequency search
         (`fine_frequency_ms`) wait for its window as well, and a group's channels are refined in ONE sdr_acq_refine call
         behind their search."""
-        packets, groups = [], {}
+        packets, groups, warm = [], {}, {}
         for ch in acquiring:
             if self.sharedBuffer.getNbUnreadSamples(ch.currentSample) < getattr(ch, "acq_waitSamples", ch.acq_requiredSamples):
+                continue
+            if getattr(ch, "_warmHint", None) is not None:      # a warm search: all of a tick's go into one sdr_ddm call
+                ch._ensure_code()
+                r = ch.warmRequest()
+                warm.setdefault(tuple(r[name] for name in _WARM_KEY), []).append((ch, r["item"]))
                 continue
             if getattr(type(ch), "runSignalSearch", None) is not _default_search():
                 packets.extend(ch._processHandler())
@@ -715,6 +770,12 @@ class ChannelManager:
                     ch._acqDeep = rows[k]
                 if refined is not None:
                     ch._injectedFine = refined[k]
+                packets.append(ch.runAcquisition())
+        for key, members in warm.items():
+            items = make_items(*(np.array(col) for col in zip(*(item for _, item in members))))
+            res, maps, _ = self.engine.ddm(items, **dict(zip(_WARM_KEY, key)), want_map=self.keepCorrelationMap)
+            for k, (ch, _) in enumerate(members):
+                ch._injectedWarm = (res[k], maps[k] if maps is not None else None)
                 packets.append(ch.runAcquisition())
         return [p for p in packets if p is not None]
 
@@ -828,6 +889,10 @@ class ChannelManager:
         rows = [dict(satelliteID=p, peak_bin=int(pb[k]), peak_code=int(pc[k]), peak_ratio=float(pr[k]),
                      doppler_hz=-(-R + S * int(pb[k])), start_sample=first) for k, p in enumerate(prns)]
         return packets, rows
+
+
+# what a tick's warm searches must share to go into one sdr_ddm call: `Engine.ddm`'s arguments, by name (tracked.py warmRequest)
+_WARM_KEY = ("fs", "n_blocks", "n_segments", "first_chips", "step_chips", "n_taps", "span_hz", "step_hz")
 
 
 def _default_search():

@@ -100,6 +100,18 @@ class MultiDeviceChannelManager:
                     return channel
         raise Warning(f"Could not find an IDLE channel for tracking satellite [G{satelliteID}].")
 
+    def requestTrackingWarm(self, satelliteID: int, carrierFrequency: float, codePhaseChips: float, atSample: int, **hint):
+        """ChannelManager.requestTrackingWarm on the least busy device (every device's ring holds the same stream)."""
+        channel = self.requestTracking(satelliteID)
+        channel.setWarmHint(atSample, codePhaseChips, carrierFrequency, **hint)
+        return channel
+
+    def reacquire(self, channelID, **hint):
+        """ChannelManager.reacquire on the device that tracks the channel."""
+        self.getChannel(channelID)
+        self._merge_cache = None
+        return self.parts[self._part_of[channelID]].reacquire(channelID, **hint)
+
     def addNewRFData(self, data):
         for part in self.parts:                              # the same slab into every device's ring; none is waited for
             part.addNewRFData(data)
@@ -124,6 +136,14 @@ class MultiDeviceChannelManager:
         for part in self.parts:
             if part.nbChannels:
                 out.update(part.correlationProfiles(first, step, n_taps))
+        return dict(sorted(out.items()))
+
+    def delayDopplerMaps(self, nbMilliseconds: float, **grid):
+        """{channelID: (result, map)} over all devices: one library call per device (ChannelManager.delayDopplerMaps)."""
+        out = {}
+        for part in self.parts:
+            if part.nbChannels:
+                out.update(part.delayDopplerMaps(nbMilliseconds, **grid))
         return dict(sorted(out.items()))
 
     def probeRFData(self, nbMilliseconds: int, nfft: int = 1024):

@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from ..dsp.ddm import segments_for
 from ..engine import make_items, make_refine_items
 from ..utils.constants import GPS_L1CA_CARRIER_FREQ, GPS_L1CA_CODE_FREQ, GPS_L1CA_CODE_MS, GPS_L1CA_CODE_SIZE_BITS, LNAV_MS_PER_BIT
 from ..utils.devicering import CircularBuffer as DeviceRing
@@ -283,13 +284,15 @@ class DeviceTrackedChannel(GpuCorrelatorSeams, Channel, metaclass=_ViewMeta):
         """Unread samples acquisition waits for: the searched slab, and with the fine search on the window behind it --
         it starts at the sample tracking starts at, which `enterTracking` puts between one code period before and one
         sample past the slab's end, so it ends inside (fine_frequency_ms + 1) more milliseconds."""
-        if not self.fineFrequencySearch:
+        if self._warmHint is not None or not self.fineFrequencySearch:     # (a warm search has no fine stage behind it)
             return self.acq_requiredSamples
         return self.acq_requiredSamples + (self.acq_fineFrequencyMs + 1) * int(self.rfSignal.samplingFrequency * 1e-3)
 
     def runAcquisition(self):
         if self.rfBuffer.getNbUnreadSamples(self.currentSample) < self.acq_waitSamples:
             return None
+        if self._warmHint is not None:
+            return self.runWarmAcquisition()
         correlationMap = self.runSignalSearch()
         indices, ratio = self.runPeakFinder(correlationMap)
         # (the deep search's window is long enough for the code to drift: tracking starts behind the window, so it takes
@@ -298,6 +301,90 @@ class DeviceTrackedChannel(GpuCorrelatorSeams, Channel, metaclass=_ViewMeta):
         self._acqFine = self.runFineFrequencySearch(start) if self.fineFrequencySearch else None
         self.postAcquisitionUpdate(start)
         return self.prepareResultsAcquisition(correlationMap, indices, ratio)
+
+    # ------------------------------------------------------------------ warm acquisition (sdr_ddm around a hint)
+    _warmHint = None                # a prediction for this channel's next acquisition: see setWarmHint
+    _injectedWarm = None            # set by a batching manager: (this channel's sdr_ddm_result row, its map or None)
+    WARM_SEGMENT_FRACTION = 0.25    # a segment of the warm search is this part of a code period or shorter
+
+    def setWarmHint(self, atSample, codePhaseChips, carrierFrequency, codeStep=None, chips=4.0, chipStep=0.25, spanHz=500.0,
+                    stepHz=25.0):
+        """A prediction for the next acquisition of this channel: at ring sample `atSample` the code phase is
+        `codePhaseChips` (the rem_code of an sdr_epl_item that starts there) and the carrier `carrierFrequency` (IF
+        included), the code advances by `codeStep` chips per sample (None: the nominal rate); the truth is expected within
+        +-`chips` (searched at `chipStep`) and +-`spanHz` (at `stepHz`).  While the hint stands, `runAcquisition` searches
+        that neighbourhood with one sdr_ddm item over its usual slab instead of the whole code period and every bin."""
+        if not (chips > 0.0 and chipStep > 0.0 and spanHz >= 0.0 and stepHz > 0.0):
+            raise ValueError("the uncertainties of a warm hint must be positive")
+        step = GPS_L1CA_CODE_FREQ / self.rfSignal.samplingFrequency if codeStep is None else float(codeStep)
+        self._warmHint = dict(sample=int(atSample), phase=float(codePhaseChips), carrier=float(carrierFrequency), code_step=step,
+                              chips=float(chips), chip_step=float(chipStep), span_hz=float(spanHz), step_hz=float(stepHz))
+
+    def warmRequest(self):
+        """This channel's warm search: the sdr_epl_item fields of its slab (the hint's phase carried forward to the slab's
+        first sample) and the sdr_ddm_cfg values -- a batching manager puts a tick's warm channels into one call."""
+        h = self._warmHint
+        fs, W = self.rfSignal.samplingFrequency, int(self.acq_requiredSamples)
+        ahead = (self.currentSample - h["sample"]) % self.rfBuffer.maxSize
+        phase = (h["phase"] + ahead * h["code_step"]) % GPS_L1CA_CODE_SIZE_BITS
+        B = max(1, int(self.acq_nonCoherentIntegration))
+        S = segments_for(W, B, GPS_L1CA_CODE_SIZE_BITS / h["code_step"], self.WARM_SEGMENT_FRACTION)
+        half = int(np.floor(h["chips"] / h["chip_step"]))
+        return dict(item=(self.codeSlot, W, self.currentSample, h["carrier"], 0.0, phase, h["code_step"]), fs=fs, n_blocks=B,
+                    n_segments=S, first_chips=-half * h["chip_step"], step_chips=h["chip_step"], n_taps=2 * half + 1,
+                    span_hz=h["span_hz"], step_hz=h["step_hz"])
+
+    def runWarmAcquisition(self):
+        """The warm search and, from its peak, the step a PCPS result takes: `enterTracking` with a fresh loop state at
+        peak_hz, at the sample where the code period begins according to rem_code + peak_chips."""
+        r = self.warmRequest()
+        if self._injectedWarm is not None:
+            (res, cmap), self._injectedWarm = self._injectedWarm, None
+        else:
+            out, maps, _ = self._ensure_code().ddm(make_items(*r["item"]), r["fs"], r["n_blocks"], r["n_segments"], r["first_chips"],
+                                                   r["step_chips"], r["n_taps"], r["span_hz"], r["step_hz"])
+            res, cmap = out[0], maps[0]
+        self._warmHint = None
+        step = r["item"][6]
+        phase = r["item"][5] + float(res["peak_chips"])                   # the code phase at the slab's first sample
+        # rem_code = 0 at sample t means the period's first chip begins right behind t (idx = ceil(i * step)): t is where
+        # the phase comes round to a whole period -- the code sample a PCPS peak reports, which _firstEpochSample turns
+        # into the first epoch's sample (SURVEY T10)
+        per_code = int(np.round(GPS_L1CA_CODE_SIZE_BITS / step))
+        code_idx = int(np.round(((-phase) % GPS_L1CA_CODE_SIZE_BITS) / step)) % per_code
+        second = float(res["second_value"])
+        ratio = float(res["peak_value"]) / second if second > 0.0 else float("inf")
+        self._acqFine = self._acqDeep = None
+        self.enterTracking(float(res["peak_hz"]), code_idx)
+        packet = self.prepareResultsAcquisition(cmap, [int(res["peak_bin"]), code_idx], ratio)
+        packet["warm_start"] = True
+        return packet
+
+    def reacquire(self, chips=4.0, chipStep=0.25, spanHz=500.0, stepHz=25.0):
+        """From TRACKING (lost or not) back to ACQUIRING with this channel's own NCO state as the warm hint: the next
+        epoch's first sample, its rem_code, the carrier and the code step.  The loop state, the flags, the bit and
+        subframe synchronisation start afresh, as after a cold acquisition.  The searched slab starts at that sample: call
+        while the ring still holds it.  Nothing guards the ring for a channel the device has parked (`lostLock`) -- one
+        parked more than a ring's length ago would search newer samples with a stale phase -- so reacquire promptly, or
+        start such a channel anew with `requestTrackingWarm` from a prediction carried forward."""
+        if self.channelState is not ChannelState.TRACKING:
+            raise ValueError(f"channel {self.channelID} is not tracking: there is no state to reacquire from")
+        bank, row = self._bank, self._row
+        st = bank.state[row]
+        slot, at = int(st["code_slot"]), int(st["current_sample"])
+        hint = (at, float(st["rem_code"]), float(st["carrier_hz"]), float(st["code_step"]))
+        bank.state[row] = np.zeros((), dtype=bank.state.dtype)
+        bank.state["code_slot"][row], bank.state["current_sample"][row] = slot, at
+        bank.lost[row] = False
+        bank.code_since_tow[row], bank.tow[row], bank.tow_decoded[row], bank.host_flags[row] = 0, 0.0, False, 0
+        bank.last["n_samples"][row] = 0
+        del bank.nav_bits[row][:]
+        if bank.decoders[row] is not None:
+            bank.decoders[row].reset()
+        self.trackFlags = TrackingFlags.UNKNOWN
+        self.setTracking(self.configuration['TRACKING'])
+        self.setWarmHint(*hint, chips=chips, chipStep=chipStep, spanHz=spanHz, stepHz=stepHz)
+        self.channelState = ChannelState.ACQUIRING
 
     def trackingStart(self, acqIndices):
         """(coarse carrier, ring index of the sample tracking starts at) for a PCPS peak [bin, code sample]: what
@@ -396,6 +483,22 @@ class DeviceTrackedChannel(GpuCorrelatorSeams, Channel, metaclass=_ViewMeta):
         (-0.5, 0.5, 3) gives the epoch's E, P, L again.  ValueError: see `correlationProfileItem`."""
         items = make_items(*self.correlationProfileItem())
         return self._bank.engine.corr_profile(items, first, step, n_taps, self.rfSignal.samplingFrequency)[0]
+
+    def delayDopplerItem(self, nbMilliseconds: float):
+        """The last `nbMilliseconds` of this channel, ending with its latest epoch, as sdr_epl_item fields for sdr_ddm: the
+        item of `correlationProfileItem` carried BACK by the extra samples -- the code phase by back * code_step (the chips
+        are indexed modulo the code length, so a negative rem_code is served), the carrier phase likewise.  ValueError as
+        for `correlationProfileItem`, and when the ring does not hold the whole window (any more, or yet)."""
+        slot, n, start, carrier, rem_carrier, rem_code, code_step = self.correlationProfileItem()
+        fs, ring = self.rfSignal.samplingFrequency, self.rfBuffer
+        W = max(n, int(round(fs * 1e-3 * nbMilliseconds)))
+        back = W - n
+        unread = ring.getNbUnreadSamples((start + n) % ring.maxSize)
+        if unread + W > ring.size:
+            raise ValueError(f"the ring does not hold the last {W} samples of channel {self.channelID} "
+                             f"({unread} written behind them, {ring.size} held)")
+        rem_carrier = (rem_carrier + carrier * 2.0 * np.pi * back / fs) % (2.0 * np.pi)
+        return (slot, W, (start - back) % ring.maxSize, carrier, float(rem_carrier), rem_code - back * code_step, code_step)
 
     def runTracking(self):
         if self.lostLock or self.rfBuffer.getNbUnreadSamples(self.currentSample) < self.track_requiredSamples:

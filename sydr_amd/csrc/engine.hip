@@ -275,6 +275,7 @@ int sdr_set_option(sdr_engine* e, const char* name, int value) {
     else if (!strcmp(name, "epl_no_half_chip_view")) e->epl_no_double = value != 0;
     else if (!strcmp(name, "epl_no_two_chip_variant")) e->epl_no_chip2 = value != 0;
     else if (!strcmp(name, "corr_profile_per_sample")) e->corr_per_sample = value != 0;
+    else if (!strcmp(name, "ddm_per_sample")) e->ddm_per_sample = value != 0;
     else return sdr_fail(SDR_ERR_INVALID, "unknown option '%s'", name);
     return SDR_OK;
 }
@@ -385,7 +386,7 @@ void sdr_engine_destroy(sdr_engine* e) {
     DevBuf* bufs[] = {&e->ws_items,  &e->ws_out,   &e->ws_spacing, &e->ws_setups, &e->ws_stats, &e->pcps_fwd,   &e->pcps_a,
                       &e->pcps_b,    &e->pcps_code, &e->pcps_code2, &e->pcps_tickets, &e->pcps_spec_off, &e->pcps_tw,   &e->pcps_map,   &e->pcps_csum,
                       &e->pcps_part, &e->pcps_res,  &e->track_state, &e->track_cfg,
-                      &e->pcps_blu,  &e->pcps_blu_x, &e->pcps_blu_a, &e->pcps_blu_b, &e->pcps_work, &e->pcps_theta, &e->refine_ws, &e->deep_fold, &e->deep_mag, &e->deep_q, &e->corr_ws, &e->unpack_stage, &e->probe_ws, &e->probe_tab, &e->ddc_stage, &e->cancel_ws};
+                      &e->pcps_blu,  &e->pcps_blu_x, &e->pcps_blu_a, &e->pcps_blu_b, &e->pcps_work, &e->pcps_theta, &e->refine_ws, &e->deep_fold, &e->deep_mag, &e->deep_q, &e->corr_ws, &e->unpack_stage, &e->probe_ws, &e->probe_tab, &e->ddc_stage, &e->cancel_ws, &e->ddm_ws};
     for (DevBuf* b : bufs)
         if (b->ptr) (void)hipFree(b->ptr);
     for (DevBuf& b : e->plan_pool)

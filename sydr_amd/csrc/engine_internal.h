@@ -177,6 +177,12 @@ struct sdr_engine {
     size_t corr_lds_allowed[8] = {0};   // dynamic LDS its kernels were last allowed, per (format, form)
     bool corr_per_sample = false; // "corr_profile_per_sample": the per-sample form at any rate (tests, A/B timing)
 
+    // sdr_ddm (ddm.hip)
+    DevBuf ddm_ws;                // [items][segment sums][map][results]
+    std::vector<char> ddm_host;   // the host image of its item list (the source of the upload)
+    size_t ddm_lds_allowed[8] = {0};   // dynamic LDS its segments kernels were last allowed, per (format, form)
+    bool ddm_per_sample = false;  // "ddm_per_sample": the per-sample form at any rate (tests, A/B timing)
+
     // sdr_iq_probe (probe.hip)
     DevBuf probe_ws;              // [result block][histogram][moment rows][spectrum rows][spectrum]
     DevBuf probe_tab;             // the transform's twiddles and the Hann window of probe_tab_nfft, sum of its squares

@@ -560,6 +560,33 @@ class Engine:
                                          ptr(out)))
         return out
 
+    def ddm_bins(self, span_hz: float, step_hz: float) -> int:
+        return int(self._lib.sdr_ddm_bins(float(span_hz), float(step_hz)))
+
+    def ddm(self, items, fs, n_blocks, n_segments, first_chips, step_chips, n_taps, span_hz, step_hz, want_map=True,
+            want_segments=False):
+        """A delay-Doppler map around a known code phase and carrier (sdr_ddm; the NumPy statement is
+        dsp.ddm.ddm_statement).  `items` as for `epl_batch` (`make_items`), read as predictions: start_sample, the whole
+        window n_samples, the carrier, the NCO state at the start.  n_blocks non-coherent blocks of n_segments segments,
+        taps first_chips + step_chips * arange(n_taps), frequencies carrier + (k - (K-1)/2) * step_hz within +-span_hz.
+        -> (results (DDM_RESULT_DTYPE: peak_bin, peak_tap, peak_hz, peak_chips, peak_value, second_value, noise_mean),
+        map[n][K][n_taps] or None, z[n][n_blocks*n_segments][n_taps] complex or None)."""
+        items = np.ascontiguousarray(items, dtype=EPL_ITEM_DTYPE).reshape(-1)
+        n = len(items)
+        cfg = _lib.DdmCfg(float(fs), float(first_chips), float(step_chips), float(span_hz), float(step_hz), int(n_taps),
+                          int(n_blocks), int(n_segments), 0)
+        res = np.zeros(n, dtype=_lib.DDM_RESULT_DTYPE)
+        taps = max(0, min(int(n_taps), _lib.SDR_CORR_MAX_TAPS))
+        cmap = z = None
+        if want_map:
+            cmap = np.empty((n, max(0, self.ddm_bins(span_hz, step_hz)), taps), dtype=np.float64)
+        if want_segments:
+            q = max(0, int(n_blocks)) * max(0, int(n_segments))
+            z = np.empty((n, q if q <= 4096 else 0, taps), dtype=np.complex128)
+        check(self._lib.sdr_ddm(self._h, ptr(items), n, C.byref(cfg), ptr(res), ptr(cmap) if want_map else None,
+                                ptr(z) if want_segments else None))
+        return res, cmap, z
+
     def iq_cancel(self, items, amps=None, fs=None, window=None, dst=None, dst_offset=0) -> dict:
         """Subtract tracked signals' replicas from a window of the ring (sdr_iq_cancel; the NumPy statement is
         signal.cancel.cancel_statement).  items[n_ch][n_epochs] (`make_items` records; one row = one channel, epochs
