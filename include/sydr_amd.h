@@ -806,6 +806,53 @@ int64_t sdr_ddc_out_count(const sdr_ddc* d, int64_t n_in);
  * ceil(T / L) - 1 inputs), "call_ddc_push". */
 int sdr_ddc_create_rational(sdr_engine* e, const sdr_ddc_cfg* cfg, int interpolation, sdr_ddc** out);
 
+/* ------------------------------------------------- input layouts: packed, float32 and interleaved recordings through the converter
+ * sdr_ddc_create_layout makes a converter whose inputs are described by an INPUT LAYOUT in place of an sdr_ddc_input: how the
+ * recording's bytes hold the samples.  The kernels decode the layout where they load their inputs; the push stages the bytes as
+ * they are (one copy command of sdr_ddc_layout_bytes bytes: a packed recording stays packed over the link and in HBM).  The NumPy
+ * form is sydr_amd/signal/downconvert.py `decode`.
+ * Fields.  A recording is a sequence of fields f = 0, 1, ..., one component each, of one kind: INT8, INT16 (native byte order),
+ * FLOAT32 (native) or PACKED, a code of `bits` bits, bits one of 1, 2, 4.  With F = 8 / bits, field f of a packed recording lies
+ * in byte f div F at position p = f mod F: its code is the `bits` bits from bit bits * p up (least significant field first) or,
+ * with MSB_FIRST, from bit bits * (F - 1 - p) up; the component is levels[code], an int8 (sdr_iq_packing's rule, field for
+ * field).  Every component is widened to fp64, which is exact for all four kinds.
+ * Frames.  A frame is `stride` consecutive fields; input j of the stream is frame j:
+ *   real:                 x_j = field(j * stride + lane) + 0i
+ *   COMPLEX:              a = field(j * stride + lane), b = field(j * stride + lane + 1), x_j = a + ib
+ *   COMPLEX | SWAP_IQ:    x_j = b + ia
+ * From x_j on everything is the converter's statement above (p_j, t_j, z_j, v_m, the resampler's form, the mitigator, the
+ * ring's formats).  Frames of a packed layout need not be whole bytes: a 1-bit real stream with stride 3 is valid.
+ * Limits (SDR_ERR_INVALID otherwise): stride in 1..64; lane >= 0 and lane + (COMPLEX ? 2 : 1) <= stride; bits 1, 2 or 4 exactly
+ * when the kind is PACKED and 0 otherwise; SWAP_IQ only with COMPLEX; MSB_FIRST only with PACKED; no other flag bit, reserved 0.
+ * Pushes.  n_in counts frames and `in` points at the first byte of the push's first frame.  A push reads
+ * B = n_in * stride * (bytes per field) bytes, of a packed layout B = n_in * stride * bits / 8, which must be a whole number:
+ * otherwise the push is refused with SDR_ERR_INVALID and neither the ring nor the converter changes -- every push begins on a
+ * byte boundary.  sdr_ddc_out_count, the kept inputs (the last Tp - 1, held DECODED: this stream's components alone, int8, int16 or
+ * float32, one or two per input, zeros after creation or reset) and the promise that the ring does not depend on the cut, bit
+ * for bit, are the converter's as before.
+ * Float inputs are the caller's to keep finite: a NaN or Inf input may change only the outputs whose filter window contains it
+ * (with a mitigator: the outputs of the segments that contain it), to unspecified values; every other output is what it would
+ * be with that input replaced by 0.
+ * Bit for bit, in every ring format: the layouts {INT8 real, stride 1, lane 0}, {INT16 real, 1, 0}, {INT8 COMPLEX, 2, 0} and
+ * {INT16 COMPLEX, 2, 0} give the ring of SDR_DDC_IN_R8, _R16, _CI8 and _CI16; a packed layout gives the ring the matching INT8
+ * layout gives on the unpacked bytes; a float32 recording that holds integers within int16 gives the ring of the INT16 layout.
+ * cfg is as for sdr_ddc_create_rational (cfg->in_fmt is not read), interpolation == 1 the integer converter.  Every other
+ * sdr_ddc_* call takes the handle as it takes any converter's.  Scopes: those of the converter ("ddc_kernel" / "resample_kernel",
+ * "ddc_history_kernel", "call_ddc_push").  A converter of sdr_ddc_create / _rational makes the launches it always made. */
+enum sdr_ddc_field { SDR_DDC_FIELD_INT8 = 0, SDR_DDC_FIELD_INT16 = 1, SDR_DDC_FIELD_FLOAT32 = 2, SDR_DDC_FIELD_PACKED = 3 };
+#define SDR_DDC_LAYOUT_COMPLEX   1
+#define SDR_DDC_LAYOUT_SWAP_IQ   2
+#define SDR_DDC_LAYOUT_MSB_FIRST 4
+typedef struct sdr_ddc_layout {
+    int32_t field, bits, stride, lane, flags, reserved;
+    int8_t  levels[16];          /* PACKED: the first 1 << bits are read */
+} sdr_ddc_layout;
+/* cfg as for sdr_ddc_create_rational (cfg->in_fmt is not read); interpolation == 1: the integer converter */
+int sdr_ddc_create_layout(sdr_engine* e, const sdr_ddc_cfg* cfg, int interpolation, const sdr_ddc_layout* layout, sdr_ddc** out);
+/* bytes a push of n_in frames reads (host arithmetic, like sdr_iq_packed_bytes); SDR_ERR_INVALID for a bad layout, n_in < 0 or a
+ * packed push that is not whole bytes */
+int64_t sdr_ddc_layout_bytes(const sdr_ddc_layout* layout, int64_t n_in);
+
 /* ------------------------------------------------- pulse blanking and narrow-band excision in front of the ring
  * An opt-in stage of a converter, between the filter's fp64 output v and the ring's format: a threshold blanker against pulsed
  * interference (DME, radar, a switching supply) and a frequency-domain excisor with windowed overlap-add against carrier-wave

@@ -117,6 +117,16 @@ class DdcCfg(C.Structure):
 DDC_IN_R8, DDC_IN_R16, DDC_IN_CI8, DDC_IN_CI16 = 0, 1, 2, 3
 
 
+class DdcLayout(C.Structure):
+    """sdr_ddc_layout (include/sydr_amd.h): how a recording's bytes hold the converter's inputs."""
+    _fields_ = [("field", C.c_int32), ("bits", C.c_int32), ("stride", C.c_int32), ("lane", C.c_int32), ("flags", C.c_int32),
+                ("reserved", C.c_int32), ("levels", C.c_int8 * 16)]
+
+
+DDC_FIELD_INT8, DDC_FIELD_INT16, DDC_FIELD_FLOAT32, DDC_FIELD_PACKED = 0, 1, 2, 3
+DDC_LAYOUT_COMPLEX, DDC_LAYOUT_SWAP_IQ, DDC_LAYOUT_MSB_FIRST = 1, 2, 4
+
+
 class MitCfg(C.Structure):
     """sdr_mit_cfg (include/sydr_amd.h): the blanker's level, lead and hold, the excisor's transform length and limits."""
     _fields_ = [("nfft", C.c_int32), ("blank_lead", C.c_int32), ("blank_hold", C.c_int32), ("flags", C.c_int32),
@@ -281,6 +291,8 @@ _PROTOTYPES = {
     "sdr_iq_upload_packed_queue": (C.c_int, [_VP, C.POINTER(IqPacking), _VP, C.c_int64, C.c_int64]),
     "sdr_ddc_create": (C.c_int, [_VP, C.POINTER(DdcCfg), C.POINTER(_VP)]),
     "sdr_ddc_create_rational": (C.c_int, [_VP, C.POINTER(DdcCfg), C.c_int, C.POINTER(_VP)]),
+    "sdr_ddc_create_layout": (C.c_int, [_VP, C.POINTER(DdcCfg), C.c_int, C.POINTER(DdcLayout), C.POINTER(_VP)]),
+    "sdr_ddc_layout_bytes": (C.c_int64, [C.POINTER(DdcLayout), C.c_int64]),
     "sdr_ddc_destroy": (None, [_VP, _VP]),
     "sdr_ddc_reset": (C.c_int, [_VP, _VP]),
     "sdr_ddc_push": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),

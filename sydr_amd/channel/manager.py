@@ -416,6 +416,9 @@ class ChannelManager:
     def _raw_input(self, data):
         """A slab of raw input as the converter takes it: contiguous, the recording's integer type, whole samples."""
         cfg = self._frontEnd.config
+        if getattr(cfg, "layout", None) is not None:    # an input layout: the recording's bytes as they are, whole frames
+            data = data if type(data) is np.ndarray and data.ndim == 1 else np.ascontiguousarray(data).reshape(-1)
+            return data, cfg.layout.frames_in(cfg.layout.input_array(data).nbytes)
         from ..signal.downconvert import input_dtype, input_is_complex
         data = np.ascontiguousarray(data, dtype=input_dtype(cfg.in_fmt)).reshape(-1) if not (
             type(data) is np.ndarray and data.ndim == 1 and data.flags.c_contiguous and data.dtype == input_dtype(cfg.in_fmt)) else data

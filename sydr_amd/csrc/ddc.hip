@@ -23,19 +23,20 @@ using namespace sdr;
 // One workgroup per tile of outputs (ddc_tiles.h).  Phase 1: the tile's inputs, each mixed once, into LDS as fp64 complex.
 // Phase 2: a lane per output, the taps by wave-uniform (scalar) loads, k ascending, product then sum (no contraction: the
 // NumPy statement's own operations); the store in the ring's format, a ci8 ring's bytes sign-flipped.
-__global__ __launch_bounds__(kDdcThreads) void ddc_kernel(const void* __restrict__ in, const void* __restrict__ hist,
-                                                          const double* __restrict__ taps, void* __restrict__ ring, DdcPush push, int tile,
-                                                          int in_fmt, int out_fmt, uint64_t fcw, double gain, int64_t ring_offset,
-                                                          int64_t capacity) {
-    extern __shared__ __attribute__((aligned(16))) char ddc_smem[];
-    double2* z = (double2*)ddc_smem;
+// `load` reads an input of the push's block or of the history: one of the four formats (ddc_kernel), or a layout's frames,
+// decoded here and nowhere else (ddc_layout_kernel).
+template <class Load>
+__device__ __forceinline__ void ddc_kernel_body(double2* z, const void* __restrict__ in, const void* __restrict__ hist,
+                                                const double* __restrict__ taps, void* __restrict__ ring, const DdcPush& push, int tile,
+                                                const Load& load, int out_fmt, uint64_t fcw, double gain, int64_t ring_offset,
+                                                int64_t capacity) {
     const DdcTile t = ddc_tile(push, tile, blockIdx.x);
     for (int i = threadIdx.x; i < t.span; i += kDdcThreads) {
         const int64_t j = t.j0 + i;
         const int64_t src = ddc_source(push, j);
         double xr = 0.0, xi = 0.0;
-        if (src < 0) ddc_load(hist, ~src, in_fmt, &xr, &xi);
-        else if (src < push.n_in) ddc_load(in, src, in_fmt, &xr, &xi);
+        if (src < 0) load.history(hist, ~src, &xr, &xi);
+        else if (src < push.n_in) load.block(in, src, &xr, &xi);
         const uint64_t p = (uint64_t)j * fcw;                       // (j < 0: x = 0 whatever the phasor)
         const double turn = (double)(p >> 11) * 0x1p-53;
         double s, c;
@@ -72,6 +73,24 @@ __global__ __launch_bounds__(kDdcThreads) void ddc_kernel(const void* __restrict
     }
 }
 
+__global__ __launch_bounds__(kDdcThreads) void ddc_kernel(const void* __restrict__ in, const void* __restrict__ hist,
+                                                          const double* __restrict__ taps, void* __restrict__ ring, DdcPush push, int tile,
+                                                          int in_fmt, int out_fmt, uint64_t fcw, double gain, int64_t ring_offset,
+                                                          int64_t capacity) {
+    extern __shared__ __attribute__((aligned(16))) char ddc_smem[];
+    ddc_kernel_body((double2*)ddc_smem, in, hist, taps, ring, push, tile, DdcFormatLoad{in_fmt}, out_fmt, fcw, gain, ring_offset, capacity);
+}
+
+// The same kernel over a converter with an input layout (sdr_ddc_create_layout): `in` is the recording's bytes as they are.
+__global__ __launch_bounds__(kDdcThreads) void ddc_layout_kernel(const void* __restrict__ in, const void* __restrict__ hist,
+                                                                 const double* __restrict__ taps, void* __restrict__ ring, DdcPush push,
+                                                                 int tile, DdcLayout lay, int out_fmt, uint64_t fcw, double gain,
+                                                                 int64_t ring_offset, int64_t capacity) {
+    extern __shared__ __attribute__((aligned(16))) char ddc_smem[];
+    ddc_kernel_body((double2*)ddc_smem, in, hist, taps, ring, push, tile, DdcLayoutLoad{lay, ddc_layout_history(lay)}, out_fmt, fcw, gain,
+                    ring_offset, capacity);
+}
+
 // The history after a push: one workgroup, every lane reads its element (out of the block, or -- a push shorter than T-1 --
 // further up the old history) before any lane writes.  `unit` = bytes per raw input.
 __global__ __launch_bounds__(kDdcMaxTaps) void ddc_history_kernel(const void* __restrict__ in, void* hist, int64_t n_in, int T, int unit) {
@@ -91,10 +110,43 @@ __global__ __launch_bounds__(kDdcMaxTaps) void ddc_history_kernel(const void* __
     }
 }
 
+// The same for a converter with an input layout: an element out of the block is decoded, one out of the old history is read as
+// the history holds it; both are stored decoded.
+__global__ __launch_bounds__(kDdcMaxTaps) void ddc_layout_history_kernel(const void* __restrict__ in, void* hist, int64_t n_in, int T, DdcLayout lay) {
+    const int i = threadIdx.x;
+    const DdcLayout h = ddc_layout_history(lay);
+    double re = 0.0, im = 0.0;
+    if (i < T - 1) {
+        const int64_t src = ddc_hist_source(n_in, T, i);
+        if (src >= 0) ddc_layout_load(in, src, lay, &re, &im);
+        else ddc_layout_load((const void*)hist, ~src, h, &re, &im);
+    }
+    __syncthreads();
+    if (i < T - 1) ddc_layout_history_store(hist, i, h, re, im);
+}
+
 void sdr::ddc_history_launch(sdr_engine* e, sdr_ddc* d, int64_t n_in) {
     ProfScope ps(e, "ddc_history_kernel");
+    if (d->has_layout) {
+        hipLaunchKernelGGL(ddc_layout_history_kernel, dim3(1), dim3(kDdcMaxTaps), 0, e->stream, (const void*)e->ddc_stage.ptr, d->hist, n_in,
+                           d->Tp, d->layout);
+        return;
+    }
     hipLaunchKernelGGL(ddc_history_kernel, dim3(1), dim3(kDdcMaxTaps), 0, e->stream, (const void*)e->ddc_stage.ptr, d->hist, n_in, d->Tp,
                        (int)ddc_in_bytes(d->in_fmt));
+}
+
+int sdr::ddc_push_bytes(const sdr_ddc* d, int64_t n_in, size_t* bytes) {
+    if (!d->has_layout) {
+        *bytes = (size_t)n_in * ddc_in_bytes(d->in_fmt);
+        return SDR_OK;
+    }
+    if (n_in > kDdcLayoutMaxFrames) return sdr_fail(SDR_ERR_RANGE, "%lld frames in one push", (long long)n_in);
+    const int64_t b = ddc_layout_push_bytes(d->layout, n_in);
+    if (b < 0)
+        return sdr_fail(SDR_ERR_INVALID, "%lld frames of %d fields of %d bit(s) are not whole bytes", (long long)n_in, d->layout.stride, d->layout.bits);
+    *bytes = (size_t)b;
+    return SDR_OK;
 }
 
 static int ddc_push_impl(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in, int64_t off, int64_t* n_out, bool wait) {
@@ -110,10 +162,11 @@ static int ddc_push_impl(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in
     const DdcPush push = ddc_push(d->n_seen, n_in, d->D, d->T);
     if (push.n_out > cap)
         return sdr_fail(SDR_ERR_RANGE, "%lld outputs exceed the ring capacity %lld", (long long)push.n_out, (long long)cap);
+    size_t bytes = 0;
+    if (int rc = ddc_push_bytes(d, n_in, &bytes)) return rc;
     if (n_out) *n_out = push.n_out;
     if (n_in == 0) return SDR_OK;
     ProfScope whole(e, "call_ddc_push");
-    const size_t unit = ddc_in_bytes(d->in_fmt), bytes = (size_t)n_in * unit;
     // one copy command brings the raw inputs into the engine's staging buffer in HBM (no kernel reads host memory), the
     // kernels follow it on the same stream -- whose order is all the guard the buffer and the history need
     if (int rc = sdr_devbuf_reserve(e, &e->ddc_stage, bytes)) return rc;
@@ -132,16 +185,16 @@ static int ddc_push_impl(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in
         const int64_t tiles = ddc_tiles(push, tile);
         const size_t lds = (size_t)((tile - 1) * d->D + d->T) * sizeof(double2);
         ProfScope ps(e, "ddc_kernel");
-        hipLaunchKernelGGL(ddc_kernel, dim3((unsigned)tiles), dim3(kDdcThreads), lds, e->stream, (const void*)e->ddc_stage.ptr,
-                           (const void*)d->hist, (const double*)d->taps, dst, push, tile, d->in_fmt, dst_fmt, d->fcw, d->gain, dst_off, dst_cap);
+        if (d->has_layout)
+            hipLaunchKernelGGL(ddc_layout_kernel, dim3((unsigned)tiles), dim3(kDdcThreads), lds, e->stream, (const void*)e->ddc_stage.ptr,
+                               (const void*)d->hist, (const double*)d->taps, dst, push, tile, d->layout, dst_fmt, d->fcw, d->gain, dst_off, dst_cap);
+        else
+            hipLaunchKernelGGL(ddc_kernel, dim3((unsigned)tiles), dim3(kDdcThreads), lds, e->stream, (const void*)e->ddc_stage.ptr,
+                               (const void*)d->hist, (const double*)d->taps, dst, push, tile, d->in_fmt, dst_fmt, d->fcw, d->gain, dst_off, dst_cap);
     }
     if (d->mit && push.n_out > 0)
         if (int rc = mit_push_finish(e, d->mit, push.m_first, push.n_out, off)) return rc;
-    if (d->T > 1) {
-        ProfScope ps(e, "ddc_history_kernel");
-        hipLaunchKernelGGL(ddc_history_kernel, dim3(1), dim3(kDdcMaxTaps), 0, e->stream, (const void*)e->ddc_stage.ptr, d->hist, n_in, d->T,
-                           (int)unit);
-    }
+    if (d->T > 1) ddc_history_launch(e, d, n_in);
     SDR_HIP(hipGetLastError());
     d->n_seen += n_in;
     if (wait) SDR_HIP(hipStreamSynchronize(e->stream));
@@ -183,6 +236,51 @@ int sdr_ddc_create(sdr_engine* e, const sdr_ddc_cfg* cfg, sdr_ddc** out) {
     return SDR_OK;
 }
 
+static bool layout_of(const sdr_ddc_layout* in, DdcLayout* out) {
+    if (!in || !ddc_layout_valid(in->field, in->bits, in->stride, in->lane, in->flags, in->reserved)) return false;
+    *out = ddc_layout_make(in->field, in->bits, in->stride, in->lane, in->flags, in->levels);
+    return true;
+}
+
+int64_t sdr_ddc_layout_bytes(const sdr_ddc_layout* layout, int64_t n_in) {
+    DdcLayout lay;
+    if (!layout_of(layout, &lay)) return sdr_fail(SDR_ERR_INVALID, "the input layout is NULL or outside its limits");
+    if (n_in < 0) return sdr_fail(SDR_ERR_INVALID, "negative input count");
+    if (n_in > kDdcLayoutMaxFrames) return sdr_fail(SDR_ERR_RANGE, "%lld frames in one push", (long long)n_in);
+    const int64_t b = ddc_layout_push_bytes(lay, n_in);
+    if (b < 0) return sdr_fail(SDR_ERR_INVALID, "%lld frames of %d fields of %d bit(s) are not whole bytes", (long long)n_in, lay.stride, lay.bits);
+    return b;
+}
+
+int sdr_ddc_create_layout(sdr_engine* e, const sdr_ddc_cfg* cfg, int interpolation, const sdr_ddc_layout* layout, sdr_ddc** out) {
+    if (int rc = sdr_set_device(e)) return rc;
+    if (!cfg || !out) return sdr_fail(SDR_ERR_INVALID, "NULL configuration or result pointer");
+    *out = nullptr;
+    DdcLayout lay;
+    if (!layout_of(layout, &lay)) return sdr_fail(SDR_ERR_INVALID, "the input layout is NULL or outside its limits");
+    // the converter itself is sdr_ddc_create_rational's, every check of cfg included (cfg->in_fmt is not read: the layout says
+    // what an input is); its history then takes the layout's form
+    sdr_ddc_cfg c = *cfg;
+    c.in_fmt = SDR_DDC_IN_R8;
+    sdr_ddc* d = nullptr;
+    if (int rc = sdr_ddc_create_rational(e, &c, interpolation, &d)) return rc;
+    d->has_layout = true, d->layout = lay;
+    const size_t hist_bytes = (size_t)(d->Tp > 1 ? d->Tp - 1 : 1) * ddc_hist_unit(d);
+    void* hist = nullptr;
+    hipError_t err = hipMalloc(&hist, hist_bytes);
+    if (err == hipSuccess) err = hipMemsetAsync(hist, 0, hist_bytes, e->stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+    if (err != hipSuccess) {
+        if (hist) (void)hipFree(hist);
+        sdr_ddc_destroy(e, d);
+        return sdr_fail(SDR_ERR_HIP, "sdr_ddc_create_layout: %s", hipGetErrorString(err));
+    }
+    (void)hipFree(d->hist);
+    d->hist = hist;
+    *out = d;
+    return SDR_OK;
+}
+
 void sdr_ddc_destroy(sdr_engine* e, sdr_ddc* d) {
     if (!d) return;
     if (e && sdr_set_device(e) == SDR_OK) (void)hipStreamSynchronize(e->stream);     // (a queued push may still read them)
@@ -195,7 +293,7 @@ void sdr_ddc_destroy(sdr_engine* e, sdr_ddc* d) {
 int sdr_ddc_reset(sdr_engine* e, sdr_ddc* d) {
     if (int rc = sdr_set_device(e)) return rc;
     if (int rc = ddc_check(e, d)) return rc;
-    const size_t hist_bytes = (size_t)(d->Tp > 1 ? d->Tp - 1 : 1) * ddc_in_bytes(d->in_fmt);
+    const size_t hist_bytes = (size_t)(d->Tp > 1 ? d->Tp - 1 : 1) * ddc_hist_unit(d);
     SDR_HIP(hipMemsetAsync(d->hist, 0, hist_bytes, e->stream));
     if (d->mit)
         if (int rc = mit_reset(e, d->mit)) return rc;

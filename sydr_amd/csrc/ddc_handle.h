@@ -3,6 +3,7 @@
 #pragma once
 
 #include "engine_internal.h"
+#include "ddc_layout.h"
 #include "mitigate.h"
 
 struct sdr_ddc {
@@ -18,6 +19,10 @@ struct sdr_ddc {
     // table [Tp][L'] of resample_tiles.h and `hist` the last Tp - 1 raw inputs
     int L = 1;
     int Tp = 1;                  // ceil(T / L): the history holds Tp - 1 inputs (L = 1: T)
+    // a converter made by sdr_ddc_create_layout: in_fmt is not read, the staged bytes are decoded by `layout` where the kernels
+    // load them and `hist` holds the last Tp - 1 inputs DECODED (ddc_layout.h)
+    bool has_layout = false;
+    sdr::DdcLayout layout = {};
 };
 
 inline size_t ddc_in_bytes(int in_fmt) {
@@ -29,6 +34,9 @@ inline size_t ddc_in_bytes(int in_fmt) {
     }
     return 0;
 }
+
+// Bytes one input takes in the history.
+inline size_t ddc_hist_unit(const sdr_ddc* d) { return d->has_layout ? (size_t)sdr::ddc_layout_history_unit(d->layout) : ddc_in_bytes(d->in_fmt); }
 
 __device__ __forceinline__ void ddc_load(const void* __restrict__ p, int64_t i, int in_fmt, double* re, double* im) {
     switch (in_fmt) {
@@ -47,6 +55,19 @@ __device__ __forceinline__ void ddc_load(const void* __restrict__ p, int64_t i, 
     }
 }
 
+// How phase 1 of ddc_kernel / resample_kernel reads input `i` of the push's block or of the history: one of the four formats ...
+struct DdcFormatLoad {
+    int in_fmt;
+    __device__ __forceinline__ void block(const void* __restrict__ p, int64_t i, double* re, double* im) const { ddc_load(p, i, in_fmt, re, im); }
+    __device__ __forceinline__ void history(const void* __restrict__ p, int64_t i, double* re, double* im) const { ddc_load(p, i, in_fmt, re, im); }
+};
+// ... or a layout's frames, the history holding decoded components.
+struct DdcLayoutLoad {
+    sdr::DdcLayout lay, hist;
+    __device__ __forceinline__ void block(const void* __restrict__ p, int64_t i, double* re, double* im) const { sdr::ddc_layout_load(p, i, lay, re, im); }
+    __device__ __forceinline__ void history(const void* __restrict__ p, int64_t i, double* re, double* im) const { sdr::ddc_layout_load(p, i, hist, re, im); }
+};
+
 __device__ __forceinline__ double ddc_clip_rint(double v, double lim) { return fmin(fmax(rint(v), -lim), lim); }
 
 inline int ddc_check(sdr_engine* e, const sdr_ddc* d) {
@@ -61,6 +82,9 @@ namespace sdr {
 // ddc.hip: the history launch behind a push's kernel -- the last d->Tp - 1 of the raw inputs in the staging buffer and the old
 // history, under the scope "ddc_history_kernel".
 void ddc_history_launch(sdr_engine* e, sdr_ddc* d, int64_t n_in);
+// ddc.hip: the bytes a push of n_in >= 0 inputs copies to the staging buffer; of a converter with a layout SDR_ERR_INVALID when
+// they are not whole (nothing has changed then).
+int ddc_push_bytes(const sdr_ddc* d, int64_t n_in, size_t* bytes);
 int rs_push_impl(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in, int64_t off, int64_t* n_out, bool wait);
 
 }  // namespace sdr

@@ -22,19 +22,20 @@ using namespace sdr;
 // history) and mixed once, into LDS as fp64 complex.  Phase 2: a lane per output, its K_p taps down its column of the table,
 // k ascending, product then sum (no contraction: the NumPy statement's own operations); then gain and the store in the ring's
 // format, a ci8 ring's bytes sign-flipped.
-__global__ __launch_bounds__(kRsThreads) void resample_kernel(const void* __restrict__ in, const void* __restrict__ hist,
-                                                              const double* __restrict__ table, void* __restrict__ ring, RsPush push, int tile,
-                                                              int in_fmt, int out_fmt, uint64_t fcw, double gain, int64_t ring_offset,
-                                                              int64_t capacity) {
-    extern __shared__ __attribute__((aligned(16))) char rs_smem[];
-    double2* z = (double2*)rs_smem;
+// `load` reads an input as ddc.hip's kernels do: one of the four formats (resample_kernel) or a layout's frames
+// (resample_layout_kernel).
+template <class Load>
+__device__ __forceinline__ void resample_kernel_body(double2* z, const void* __restrict__ in, const void* __restrict__ hist,
+                                                     const double* __restrict__ table, void* __restrict__ ring, const RsPush& push, int tile,
+                                                     const Load& load, int out_fmt, uint64_t fcw, double gain, int64_t ring_offset,
+                                                     int64_t capacity) {
     const RsTile t = rs_tile(push, tile, blockIdx.x);
     for (int i = threadIdx.x; i < t.span; i += kRsThreads) {
         const int64_t j = t.j0 + i;
         const int64_t src = rs_source(push, j);
         double xr = 0.0, xi = 0.0;
-        if (src < 0) ddc_load(hist, ~src, in_fmt, &xr, &xi);
-        else if (src < push.n_in) ddc_load(in, src, in_fmt, &xr, &xi);
+        if (src < 0) load.history(hist, ~src, &xr, &xi);
+        else if (src < push.n_in) load.block(in, src, &xr, &xi);
         const uint64_t p = (uint64_t)j * fcw;                       // (j < 0: x = 0 whatever the phasor)
         const double turn = (double)(p >> 11) * 0x1p-53;
         double s, c;
@@ -73,6 +74,23 @@ __global__ __launch_bounds__(kRsThreads) void resample_kernel(const void* __rest
     }
 }
 
+__global__ __launch_bounds__(kRsThreads) void resample_kernel(const void* __restrict__ in, const void* __restrict__ hist,
+                                                              const double* __restrict__ table, void* __restrict__ ring, RsPush push, int tile,
+                                                              int in_fmt, int out_fmt, uint64_t fcw, double gain, int64_t ring_offset,
+                                                              int64_t capacity) {
+    extern __shared__ __attribute__((aligned(16))) char rs_smem[];
+    resample_kernel_body((double2*)rs_smem, in, hist, table, ring, push, tile, DdcFormatLoad{in_fmt}, out_fmt, fcw, gain, ring_offset, capacity);
+}
+
+__global__ __launch_bounds__(kRsThreads) void resample_layout_kernel(const void* __restrict__ in, const void* __restrict__ hist,
+                                                                     const double* __restrict__ table, void* __restrict__ ring, RsPush push,
+                                                                     int tile, DdcLayout lay, int out_fmt, uint64_t fcw, double gain,
+                                                                     int64_t ring_offset, int64_t capacity) {
+    extern __shared__ __attribute__((aligned(16))) char rs_smem[];
+    resample_kernel_body((double2*)rs_smem, in, hist, table, ring, push, tile, DdcLayoutLoad{lay, ddc_layout_history(lay)}, out_fmt, fcw, gain,
+                         ring_offset, capacity);
+}
+
 namespace sdr {
 
 // sdr_ddc_push / _queue of a converter with L > 1: ddc.hip's push with the resampler's counts and kernels.
@@ -87,10 +105,11 @@ int rs_push_impl(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in, int64_
     const RsPush push = rs_push(d->n_seen, n_in, d->L, d->D, d->T);
     if (push.n_out > cap)
         return sdr_fail(SDR_ERR_RANGE, "%lld outputs exceed the ring capacity %lld", (long long)push.n_out, (long long)cap);
+    size_t bytes = 0;
+    if (int rc = ddc_push_bytes(d, n_in, &bytes)) return rc;
     if (n_out) *n_out = push.n_out;
     if (n_in == 0) return SDR_OK;
     ProfScope whole(e, "call_ddc_push");
-    const size_t unit = ddc_in_bytes(d->in_fmt), bytes = (size_t)n_in * unit;
     if (int rc = sdr_devbuf_reserve(e, &e->ddc_stage, bytes)) return rc;
     // with a mitigator the kernel's destination is its linear cf64 work buffer, the first output behind the kept state
     void* dst = e->iq;
@@ -107,8 +126,12 @@ int rs_push_impl(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in, int64_
         const int64_t tiles = rs_tiles(push, tile);
         const size_t lds = (size_t)rs_tile_span_max(d->L, d->D, d->T, tile) * sizeof(double2);
         ProfScope ps(e, "resample_kernel");
-        hipLaunchKernelGGL(resample_kernel, dim3((unsigned)tiles), dim3(kRsThreads), lds, e->stream, (const void*)e->ddc_stage.ptr,
-                           (const void*)d->hist, (const double*)d->taps, dst, push, tile, d->in_fmt, dst_fmt, d->fcw, d->gain, dst_off, dst_cap);
+        if (d->has_layout)
+            hipLaunchKernelGGL(resample_layout_kernel, dim3((unsigned)tiles), dim3(kRsThreads), lds, e->stream, (const void*)e->ddc_stage.ptr,
+                               (const void*)d->hist, (const double*)d->taps, dst, push, tile, d->layout, dst_fmt, d->fcw, d->gain, dst_off, dst_cap);
+        else
+            hipLaunchKernelGGL(resample_kernel, dim3((unsigned)tiles), dim3(kRsThreads), lds, e->stream, (const void*)e->ddc_stage.ptr,
+                               (const void*)d->hist, (const double*)d->taps, dst, push, tile, d->in_fmt, dst_fmt, d->fcw, d->gain, dst_off, dst_cap);
     }
     if (d->mit && push.n_out > 0)
         if (int rc = mit_push_finish(e, d->mit, push.m_first, push.n_out, off)) return rc;

@@ -244,12 +244,21 @@ class Bank:
             pass
 
 
+def layout_struct(layout) -> "_lib.DdcLayout":
+    """sdr_ddc_layout of a signal.downconvert.InputLayout."""
+    c = _lib.DdcLayout(int(layout.field), int(layout.bits), int(layout.stride), int(layout.lane), int(layout.flags), 0)
+    for i, v in enumerate(layout.levels.tolist()):
+        c.levels[i] = v
+    return c
+
+
 class _Ddc:
     """Handle of a device-resident down-converter (Engine.ddc_create)."""
-    __slots__ = ("handle", "in_fmt", "nfft")
+    __slots__ = ("handle", "in_fmt", "nfft", "layout")
 
-    def __init__(self, handle, in_fmt):
+    def __init__(self, handle, in_fmt, layout=None):
         self.handle, self.in_fmt = handle, in_fmt
+        self.layout = layout          # signal.downconvert.InputLayout of a converter made by sdr_ddc_create_layout, else None
         self.nfft = 0                 # of the attached mitigator's excisor (Engine.ddc_mitigate)
 
 
@@ -388,13 +397,17 @@ class Engine:
 
     # ------------------------------------------------------------------ down-conversion into the ring (signal/downconvert.py)
     def ddc_create(self, cfg):
-        """A device-resident down-converter (sdr_ddc_create; with cfg.interpolation != 1 sdr_ddc_create_rational) of a
-        signal.downconvert.DownConverterConfig -> its handle."""
+        """A device-resident down-converter (sdr_ddc_create; with cfg.interpolation != 1 sdr_ddc_create_rational; with
+        cfg.layout sdr_ddc_create_layout) of a signal.downconvert.DownConverterConfig -> its handle."""
         taps = np.ascontiguousarray(cfg.taps, dtype=np.float64)
         c = _lib.DdcCfg(int(cfg.in_fmt), int(cfg.decimation), int(taps.size), 0, int(cfg.fcw), float(cfg.gain),
                         taps.ctypes.data_as(C.POINTER(C.c_double)))
         h = C.c_void_p()
         interpolation = int(cfg.interpolation)
+        layout = getattr(cfg, "layout", None)
+        if layout is not None:            # an input layout: packed, float32 or interleaved recordings (in_fmt is not read)
+            check(self._lib.sdr_ddc_create_layout(self._h, C.byref(c), interpolation, C.byref(layout_struct(layout)), C.byref(h)))
+            return _Ddc(h, int(cfg.in_fmt), layout)
         if interpolation != 1:            # a rational resampler by L / M (sdr_ddc_create_rational): decimation is M
             check(self._lib.sdr_ddc_create_rational(self._h, C.byref(c), interpolation, C.byref(h)))
         else:
@@ -403,6 +416,12 @@ class Engine:
 
     def _ddc_push(self, call, ddc, raw, ring_offset):
         from .signal.downconvert import input_dtype, input_is_complex
+        if ddc.layout is not None:        # the recording's bytes as they are: whole frames (ValueError otherwise)
+            n_in, n_out = ddc.layout.frames_in(ddc.layout.input_array(raw).nbytes), C.c_int64(0)
+            status = call(self._h, ddc.handle, raw.ctypes.data, n_in, int(ring_offset), C.byref(n_out))
+            if status:
+                check(status)
+            return n_out.value
         if not (isinstance(raw, np.ndarray) and raw.ndim == 1 and raw.flags.c_contiguous and raw.dtype == input_dtype(ddc.in_fmt)):
             raise ValueError("a push takes a contiguous 1-D array of raw inputs in the converter's input type")
         n_in = raw.size
@@ -417,7 +436,8 @@ class Engine:
         return n_out.value
 
     def ddc_push(self, ddc, raw: np.ndarray, ring_offset: int = 0) -> int:
-        """Raw inputs (real: one integer each; complex: interleaved I,Q) through the converter into the ring at ring_offset
+        """Raw inputs (real: one integer each; complex: interleaved I,Q; a converter with a layout: the recording's bytes, whole
+        frames, uint8 for packed fields and the field's type otherwise) through the converter into the ring at ring_offset
         (sdr_ddc_push, synchronous) -> the outputs written."""
         return self._ddc_push(self._lib.sdr_ddc_push, ddc, raw, ring_offset)
 

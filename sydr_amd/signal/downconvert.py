@@ -24,6 +24,27 @@ and a push yields exactly the outputs m with N L <= m M < (N + n_in) L, that is 
 ceil(T / L) - 1 raw inputs.  Limits: L in 1..1024, M in 1..1024 with M <= 64 L, T in 1..32768 with ceil(T / L) <= 512; L = 1 is
 the converter above, operation for operation.  The device form of L > 1 is sydr_amd/csrc/resample.hip.
 
+With an INPUT LAYOUT (`InputLayout`, `decode`; sdr_ddc_layout in include/sydr_amd.h) the recording's bytes are described
+field by field instead of by one of the four input formats:
+
+  Fields.  A recording is a sequence of fields f = 0, 1, ..., one component each, of one kind: INT8, INT16 (native byte order),
+  FLOAT32 (native) or PACKED, a code of `bits` bits (1, 2 or 4).  With F = 8 / bits, packed field f lies in byte f div F at
+  position p = f mod F; its code is the `bits` bits from bit bits * p up (least significant field first) or, with msb_first,
+  from bit bits * (F - 1 - p) up; the component is levels[code], an int8 -- `packing.unpack`, field for field.  Every
+  component is widened to fp64, which is exact for all four kinds.
+  Frames.  A frame is `stride` consecutive fields; input j of the stream is frame j: real x_j = field(j stride + lane) + 0i;
+  complex a = field(j stride + lane), b = field(j stride + lane + 1), x_j = a + ib, with swap_iq x_j = b + ia.  Frames of a
+  packed layout need not be whole bytes (1-bit real, stride 3 is valid).
+  Limits.  stride in 1..64; lane >= 0 and lane + (2 if complex else 1) <= stride; bits 1, 2 or 4 exactly when the kind is
+  PACKED, else 0; swap_iq only with complex; msb_first only with PACKED.
+  Pushes.  n_in counts frames; a push reads n_in * stride * (bytes per field) bytes, packed n_in * stride * bits / 8, which
+  must be a whole number (`bytes_for` raises otherwise): every push begins on a byte boundary.
+
+From x_j on everything is the statement above; the history is the last Tp - 1 inputs decoded.  Float inputs are the caller's to
+keep finite: a NaN or Inf may change only the outputs whose filter window contains it.  The layouts {INT8 real, 1, 0},
+{INT16 real, 1, 0}, {INT8 complex, 2, 0}, {INT16 complex, 2, 0} are IN_R8, IN_R16, IN_CI8, IN_CI16; a packed layout is the INT8
+layout on the unpacked bytes; float32 that holds integers within int16 is the INT16 layout on those integers -- bit for bit.
+
 Float rings store v
 (cf32: rounded to nearest float), integer rings clip(rint(v)), ties to even, clip +-127 (ci8) / +-32767 (ci16).
 Every operation below is one IEEE fp64 operation on real arrays in a fixed order (k ascending, product then sum), and the
@@ -42,6 +63,10 @@ FMT_CI8, FMT_CI16, FMT_CF32, FMT_CF64 = 0, 1, 2, 3     # sdr_iq_format (the ring
 MAX_TAPS, MAX_DECIMATION = 512, 64                     # of a converter without interpolation, and of a phase (ceil(T / L))
 MAX_INTERPOLATION, MAX_RATIONAL_DECIMATION, MAX_PROTOTYPE_TAPS = 1024, 1024, 32768
 _IN_DTYPE = {IN_R8: np.int8, IN_R16: np.int16, IN_CI8: np.int8, IN_CI16: np.int16}
+FIELD_INT8, FIELD_INT16, FIELD_FLOAT32, FIELD_PACKED = 0, 1, 2, 3    # sdr_ddc_field
+LAYOUT_COMPLEX, LAYOUT_SWAP_IQ, LAYOUT_MSB_FIRST = 1, 2, 4           # SDR_DDC_LAYOUT_*
+MAX_STRIDE = 64
+_FIELD_DTYPE = {FIELD_INT8: np.int8, FIELD_INT16: np.int16, FIELD_FLOAT32: np.float32, FIELD_PACKED: np.uint8}
 _TWO_PI = 6.283185307179586
 
 
@@ -96,6 +121,121 @@ def design_resampler(L: int, M: int, n_taps=None, cutoff=None, beta: float = 8.0
     return h * (L / h.sum())
 
 
+class InputLayout:
+    """How a recording's bytes hold the converter's inputs (the definition at the top; sdr_ddc_layout)."""
+
+    def __init__(self, field: int, bits: int = 0, stride=None, lane: int = 0, complex: bool = False, swap_iq: bool = False,
+                 msb_first: bool = False, levels=None):
+        from .packing import DEFAULT_LEVELS
+        self.field, self.bits, self.lane = int(field), int(bits), int(lane)
+        self.complex, self.swap_iq, self.msb_first = bool(complex), bool(swap_iq), bool(msb_first)
+        self.stride = (2 if self.complex else 1) if stride is None else int(stride)
+        if self.field not in _FIELD_DTYPE:
+            raise ValueError(f"unknown field kind {field}")
+        if self.field == FIELD_PACKED:
+            if self.bits not in (1, 2, 4):
+                raise ValueError(f"packed fields have 1, 2 or 4 bits, not {bits}")
+        elif self.bits != 0:
+            raise ValueError("bits is 0 unless the fields are packed")
+        if not 1 <= self.stride <= MAX_STRIDE:
+            raise ValueError(f"stride {self.stride} outside 1..{MAX_STRIDE}")
+        if self.lane < 0 or self.lane + (2 if self.complex else 1) > self.stride:
+            raise ValueError(f"lane {self.lane} of a {'complex' if self.complex else 'real'} stream does not fit a frame of {self.stride} fields")
+        if self.swap_iq and not self.complex:
+            raise ValueError("swap_iq needs a complex stream")
+        if self.msb_first and self.field != FIELD_PACKED:
+            raise ValueError("msb_first needs packed fields")
+        if self.field == FIELD_PACKED:
+            levels = DEFAULT_LEVELS[self.bits] if levels is None else tuple(int(v) for v in levels)
+            if len(levels) != 1 << self.bits:
+                raise ValueError(f"{self.bits}-bit fields need {1 << self.bits} levels, {len(levels)} given")
+            if any(not -128 <= v <= 127 for v in levels):
+                raise ValueError("levels are int8")
+        elif levels is not None:
+            raise ValueError("levels need packed fields")
+        self.levels = np.array(levels if levels is not None else (), dtype=np.int8)
+        self.levels.setflags(write=False)
+
+    @property
+    def flags(self) -> int:
+        return (LAYOUT_COMPLEX if self.complex else 0) | (LAYOUT_SWAP_IQ if self.swap_iq else 0) | (LAYOUT_MSB_FIRST if self.msb_first else 0)
+
+    @property
+    def dtype(self):
+        """Of the arrays a push takes: uint8 for packed fields, else the field's own."""
+        return _FIELD_DTYPE[self.field]
+
+    @property
+    def field_bits(self) -> int:
+        return self.bits if self.field == FIELD_PACKED else 8 * np.dtype(self.dtype).itemsize
+
+    @property
+    def frame_bits(self) -> int:
+        return self.stride * self.field_bits
+
+    @property
+    def frame_group(self) -> int:
+        """The fewest frames that are whole bytes: 8 / gcd(8, stride * bits) of a packed layout, else 1."""
+        return 8 // math.gcd(8, self.frame_bits)
+
+    def bytes_for(self, n_in: int) -> int:
+        """Bytes a push of n_in frames reads; ValueError when n_in < 0 or they are not whole."""
+        n_in = int(n_in)
+        if n_in < 0:
+            raise ValueError("negative input count")
+        total = n_in * self.frame_bits
+        if total % 8:
+            raise ValueError(f"{n_in} frames of {self.stride} fields of {self.field_bits} bit(s) are not whole bytes")
+        return total // 8
+
+    def frames_in(self, n_bytes: int) -> int:
+        """The frames n_bytes hold, which must be whole frames (the inverse of bytes_for)."""
+        total = 8 * int(n_bytes)
+        if total % self.frame_bits:
+            raise ValueError(f"{n_bytes} bytes are not whole frames of {self.stride} fields of {self.field_bits} bit(s)")
+        return total // self.frame_bits
+
+    def input_array(self, raw) -> np.ndarray:
+        """`raw` as a push takes it: contiguous, 1-D, of `dtype`, whole frames; ValueError otherwise."""
+        if not (isinstance(raw, np.ndarray) and raw.ndim == 1 and raw.flags.c_contiguous and raw.dtype == self.dtype):
+            raise ValueError(f"a push takes a contiguous 1-D {np.dtype(self.dtype).name} array of the recording's bytes")
+        self.frames_in(raw.nbytes)
+        return raw
+
+    def __eq__(self, other):
+        return (isinstance(other, InputLayout) and (self.field, self.bits, self.stride, self.lane, self.flags) ==
+                (other.field, other.bits, other.stride, other.lane, other.flags) and np.array_equal(self.levels, other.levels))
+
+    def __hash__(self):
+        return hash((self.field, self.bits, self.stride, self.lane, self.flags, self.levels.tobytes()))
+
+    def __repr__(self):
+        return (f"InputLayout(field={self.field}, bits={self.bits}, stride={self.stride}, lane={self.lane}, complex={self.complex}, "
+                f"swap_iq={self.swap_iq}, msb_first={self.msb_first}, levels={tuple(int(v) for v in self.levels)})")
+
+
+def fields(raw, layout: InputLayout) -> np.ndarray:
+    """Every field the bytes of `raw` hold, in order, in the component's own type (packed: int8, `packing.unpack` itself)."""
+    raw = np.ascontiguousarray(raw).reshape(-1)
+    if layout.field != FIELD_PACKED:
+        return raw.view(np.uint8).view(layout.dtype) if raw.dtype != layout.dtype else raw
+    from .packing import Packing, unpack
+    return unpack(raw.view(np.uint8), Packing(layout.bits, layout.levels, layout.msb_first))
+
+
+def decode(raw, layout: InputLayout):
+    """The inputs x_j = xr_j + i xi_j (float64 each) of the frames in `raw`, the recording's bytes of one push."""
+    raw = np.ascontiguousarray(raw).reshape(-1)
+    n_in = layout.frames_in(raw.nbytes)
+    f = fields(raw, layout)
+    at = np.arange(n_in, dtype=np.int64) * layout.stride + layout.lane
+    a = f[at].astype(np.float64)
+    if not layout.complex:
+        return a, np.zeros(n_in)
+    b = f[at + 1].astype(np.float64)
+    return (b, a) if layout.swap_iq else (a, b)
+
+
 @dataclass
 class DownConverterConfig:
     in_fmt: int
@@ -104,12 +244,16 @@ class DownConverterConfig:
     fcw: int = 0
     gain: float = 1.0
     interpolation: int = 1
+    layout: InputLayout | None = None      # an input layout: in_fmt is then not consulted
 
     def __post_init__(self):
         self.taps = np.ascontiguousarray(self.taps, dtype=np.float64).reshape(-1)
         self.decimation, self.fcw, self.gain = int(self.decimation), int(self.fcw), float(self.gain)
         self.interpolation = int(self.interpolation)
-        if self.in_fmt not in _IN_DTYPE:
+        if self.layout is not None:
+            if not isinstance(self.layout, InputLayout):
+                raise ValueError("layout is an InputLayout")
+        elif self.in_fmt not in _IN_DTYPE:
             raise ValueError(f"unknown input format {self.in_fmt}")
         L = self.interpolation
         if not 1 <= L <= MAX_INTERPOLATION:
@@ -171,13 +315,15 @@ class Statement:
         return out_count(self.n_seen, int(n_in), self.cfg.decimation, self.cfg.interpolation)
 
     def push(self, raw) -> np.ndarray:
-        """`raw`: the inputs as the recording holds them (real: one integer each; complex: interleaved I, Q).  Returns the
-        outputs v of this push as complex128."""
+        """`raw`: the inputs as the recording holds them (real: one integer each; complex: interleaved I, Q; with a layout:
+        the bytes of whole frames, `decode`d).  Returns the outputs v of this push as complex128."""
         cfg = self.cfg
         T, M, L, N = cfg.n_taps, cfg.decimation, cfg.interpolation, self.n_seen
         Tp = cfg.phase_taps
         raw = np.asarray(raw).reshape(-1)
-        if input_is_complex(cfg.in_fmt):
+        if cfg.layout is not None:
+            xr, xi = decode(raw, cfg.layout)
+        elif input_is_complex(cfg.in_fmt):
             xr, xi = raw[0::2].astype(np.float64), raw[1::2].astype(np.float64)
         else:
             xr = raw.astype(np.float64)

@@ -14,6 +14,13 @@ empty) -- goes through the device's down-converter (downconvert.py) when the key
 `frontEnd` says how the one becomes the other.  The optional key `interpolation` (L; only beside `decimation`, which is then
 M) makes the converter a rational resampler: the ring's rate is `sampling_frequency * L / M` (16.368 MHz -> 12 MHz with 250 / 341),
 the default filter comes from `design_resampler` and `filter_cutoff` is a fraction of the UP-SAMPLED rate.
+Beside `decimation` the key `sample_format` describes recordings the four integer formats do not cover, as an input layout
+(downconvert.py `InputLayout`) the converter's kernels decode where they load: `packed` (`data_size` 1, 2 or 4, with
+`sample_levels` and `bit_order` as for packed recordings -- real or complex, at any intermediate frequency), `float` (`data_size`
+32: float32 as GNU Radio writes it) or `int` (`data_size` 8 or 16); with it `frame_fields` (the fields of a frame: 2 if
+`is_complex`, else 1, by default), `frame_lane` (the stream's first field in its frame, default 0) and `swap_iq` (1: pairs are
+stored Q before I) pick one stream out of a file that interleaves several.  Such a recording's slabs are whole-byte views of
+its bytes, counted in frames.
 Such a recording may also ask for interference mitigation between the converter and the ring (mitigate.py; keys
 `blanking_factor` with `blanking_lead`, `blanking_hold`, and `excision_nfft` with `excision_margin_db`; `calibration_ms`):
 the blanker's level and the excisor's limits are measured once, on the host, over the converter's output of the recording's
@@ -33,6 +40,7 @@ import numpy as np
 from .packing import Packing, unpack
 
 
+LAYOUT_KEYS = ("sample_format", "frame_fields", "frame_lane", "swap_iq")
 MITIGATION_KEYS = ("blanking_factor", "blanking_lead", "blanking_hold", "excision_nfft", "excision_margin_db", "calibration_ms")
 
 
@@ -73,8 +81,10 @@ class RFSignal:
         # rfsignal.py:35: bool(<ini string>) -- ANY non-empty string is True there ("false" included); mirrored as is
         self.isComplex = bool(configuration["is_complex"])
         bits = int(configuration["data_size"])
-        if bits not in (1, 2, 4, 8, 16):
+        sample_format = str(configuration["sample_format"]).strip().lower() if "sample_format" in configuration else None
+        if bits not in (1, 2, 4, 8, 16) and not (sample_format == "float" and bits == 32):
             raise ValueError(f"Data type of {bits} bit(s) is not valid.")
+        self.layout = None                              # recordings with `sample_format`: downconvert.InputLayout
         self.packing = None                             # packed recordings: how the bytes hold the samples (packing.py)
         if bits < 8:
             levels = None
@@ -84,14 +94,14 @@ class RFSignal:
             if order not in ("lsb", "msb"):
                 raise ValueError(f"bit_order is 'lsb' or 'msb', not {order!r}")
             self.packing = Packing(bits, levels, msb_first=order == "msb")
-        self.fileDataType = np.uint8 if bits < 8 else np.int8 if bits == 8 else np.int16
+        self.fileDataType = np.uint8 if bits < 8 else np.int8 if bits == 8 else np.int16 if bits == 16 else np.float32
         self.frontEnd = None                            # recordings that go through the down-converter: FrontEnd
         if "decimation" in configuration:
             self._front_end(configuration, bits)
         else:
             if "interpolation" in configuration:
                 raise ValueError("`interpolation` needs `decimation` beside it: the ring's rate is sampling_frequency * L / M")
-            for key in MITIGATION_KEYS:
+            for key in LAYOUT_KEYS + MITIGATION_KEYS:
                 if key in configuration:
                     raise ValueError(f"`{key}` needs a front end: set `decimation` (1 with `filter_taps = 1` converts nothing)")
         if not self.isComplex and self.frontEnd is None:
@@ -107,8 +117,15 @@ class RFSignal:
     def _front_end(self, configuration, bits: int):
         """The opt-in keys of a recording that is down-converted and decimated on its way into the ring."""
         from . import downconvert as dc
-        if self.packing is not None:
-            raise ValueError("packed recordings cannot be down-converted: `decimation` needs data_size 8 or 16")
+        sample_format = str(configuration["sample_format"]).strip().lower() if "sample_format" in configuration else None
+        if sample_format is None:
+            for key in LAYOUT_KEYS:
+                if key in configuration:
+                    raise ValueError(f"`{key}` needs `sample_format` beside it")
+            if self.packing is not None:
+                raise ValueError("packed recordings cannot be down-converted: `decimation` needs data_size 8 or 16")
+        else:
+            self.layout = self._layout_keys(configuration, sample_format, bits)
         D = int(configuration["decimation"])
         L = int(configuration["interpolation"]) if "interpolation" in configuration else 1
         if not 1 <= L <= dc.MAX_INTERPOLATION:
@@ -127,17 +144,51 @@ class RFSignal:
         n_taps = int(configuration["filter_taps"]) if "filter_taps" in configuration else 16 * D + 1 if L == 1 else None
         cutoff = float(configuration["filter_cutoff"]) if "filter_cutoff" in configuration else 0.45 / D if L == 1 else None
         gain = float(configuration["output_gain"]) if "output_gain" in configuration else 1.0
-        out_bits = int(configuration["output_bits"]) if "output_bits" in configuration else bits
+        # (the ring's default width: the recording's own where that is one; 8 for packed samples, 16 for float32)
+        out_bits = int(configuration["output_bits"]) if "output_bits" in configuration else bits if bits in (8, 16) else 8 if bits < 8 else 16
         if out_bits not in (8, 16):
             raise ValueError(f"output_bits is 8 or 16, not {out_bits}")
-        in_fmt = {(False, 8): dc.IN_R8, (False, 16): dc.IN_R16, (True, 8): dc.IN_CI8, (True, 16): dc.IN_CI16}[(self.isComplex, bits)]
+        in_fmt = {(False, 8): dc.IN_R8, (False, 16): dc.IN_R16, (True, 8): dc.IN_CI8, (True, 16): dc.IN_CI16}.get((self.isComplex, bits), dc.IN_R8)
         taps = dc.design_lowpass(n_taps, cutoff) if L == 1 else dc.design_resampler(L, D, n_taps, cutoff)
-        config = dc.DownConverterConfig(in_fmt, D, taps, dc.frequency_word(shift, fs_in), gain, L)
+        config = dc.DownConverterConfig(in_fmt, D, taps, dc.frequency_word(shift, fs_in), gain, L, self.layout)
         self.frontEnd = FrontEnd(config, out_bits, shift, self._mitigation_keys(configuration, config))
         # what the channels read is the ring's: its rate, and the carrier's residual offset there
         self.samplingFrequency = fs_in * L / D
         self.interFrequency = if_in - shift
         self._per_sample = 2 if self.isComplex else 1   # elements of the file per input sample
+
+    def _layout_keys(self, configuration, sample_format: str, bits: int):
+        """The opt-in keys `sample_format`, `frame_fields`, `frame_lane`, `swap_iq` -> the recording's input layout."""
+        from . import downconvert as dc
+        sizes = {"packed": (1, 2, 4), "float": (32,), "int": (8, 16)}
+        if sample_format not in sizes:
+            raise ValueError(f"sample_format is 'packed', 'float' or 'int', not {sample_format!r}")
+        if bits not in sizes[sample_format]:
+            raise ValueError(f"sample_format {sample_format!r} needs data_size {' or '.join(str(v) for v in sizes[sample_format])}, not {bits}")
+        stride = int(configuration["frame_fields"]) if "frame_fields" in configuration else 2 if self.isComplex else 1
+        lane = int(configuration["frame_lane"]) if "frame_lane" in configuration else 0
+        swap = int(configuration["swap_iq"]) if "swap_iq" in configuration else 0
+        if swap not in (0, 1):
+            raise ValueError(f"swap_iq is 0 or 1, not {swap}")
+        if sample_format == "packed":
+            layout = dc.InputLayout(dc.FIELD_PACKED, bits, stride, lane, self.isComplex, bool(swap), self.packing.msb_first, self.packing.levels)
+            self.packing = None                         # (not sdr_iq_upload_packed's route: the converter decodes the bytes)
+        else:
+            field = dc.FIELD_FLOAT32 if sample_format == "float" else dc.FIELD_INT8 if bits == 8 else dc.FIELD_INT16
+            layout = dc.InputLayout(field, 0, stride, lane, self.isComplex, bool(swap))
+        per_ms = int(self.samplingFrequency * 1e-3)
+        if per_ms * layout.frame_bits % 8:
+            raise ValueError(f"a millisecond of {per_ms} frames of {stride} fields of {bits} bit(s) is not a whole number of bytes")
+        return layout
+
+    def _layout_span(self, first: int, n_samples: int):
+        """Frames [first, first + n_samples) of a recording with a layout as elements of the mapped file: whole bytes."""
+        lay = self.layout
+        lo, hi = first * lay.frame_bits, (first + n_samples) * lay.frame_bits
+        if lo % 8 or hi % 8:
+            raise ValueError(f"frames [{first}, {first + n_samples}) of {lay.stride} fields of {lay.field_bits} bit(s) are not whole bytes")
+        size = 8 * np.dtype(self.fileDataType).itemsize
+        return lo // size, hi // size
 
     def _mitigation_keys(self, configuration, config):
         """The opt-in mitigation keys -> the calibration to run when the front end's `mitigation` is first asked for (None
@@ -164,6 +215,8 @@ class RFSignal:
         def calibrate():
             from . import downconvert as dc
             n_in = min(ms * self.inputSamplesPerMs, self.totalSamples)
+            if self.layout is not None:
+                n_in -= n_in % self.layout.frame_group      # (whole bytes)
             v = dc.statement(config, [self.samples(0, n_in)])
             level = mt.blanking_level(v, factor) if factor is not None else 0.0
             limit = mt.excision_limits(v, nfft, margin) if nfft else None
@@ -183,6 +236,8 @@ class RFSignal:
     @property
     def totalSamples(self) -> int:
         rec = self._recording()
+        if self.layout is not None:                     # (frames)
+            return 8 * rec.nbytes // self.layout.frame_bits
         if self.frontEnd is not None:                   # (INPUT samples: what `samples` and `getMilliseconds` hand out)
             return rec.size // self._per_sample
         return rec.size * self.packing.samples_per_byte if self.packing is not None else rec.size // 2
@@ -192,6 +247,9 @@ class RFSignal:
         the packed bytes (which then have to be whole: both numbers multiples of the samples per byte)."""
         rec = self._recording()
         first, n_samples = int(first), int(n_samples)
+        if self.layout is not None:                     # the recording's bytes, counted in frames: whole bytes
+            lo, hi = self._layout_span(first, n_samples)
+            return rec[lo:hi]
         if self.frontEnd is not None:                   # raw input: real recordings hold one element per sample
             return rec[self._per_sample * first:self._per_sample * (first + n_samples)]
         if self.packing is None:
@@ -204,6 +262,20 @@ class RFSignal:
     def _complex(self, first: int, n_samples: int) -> np.ndarray:
         """Samples [first, first + n_samples) as complex128, the reference's sample type -- any two numbers: of a packed
         recording the bytes that cover them are unpacked and the samples cut out."""
+        if self.layout is not None:                     # `decode` over the whole bytes that cover the frames
+            from . import downconvert as dc
+            lay = self.layout
+            lead = first % lay.frame_group
+            cover = min(-(-(lead + n_samples) // lay.frame_group) * lay.frame_group, (self.totalSamples - (first - lead)) // lay.frame_group * lay.frame_group)
+            if cover < lead + n_samples:                # (a file that ends inside a group of frames: its last bytes field by field)
+                f = dc.fields(self._recording().view(np.uint8)[(first - lead) * lay.frame_bits // 8:], lay).astype(np.float64)
+                at = (lead + np.arange(n_samples)) * lay.stride + lay.lane
+                xr, xi = (f[at], f[at + 1] if lay.complex else np.zeros(n_samples))
+                xr, xi = (xi, xr) if lay.swap_iq else (xr, xi)
+            else:
+                xr, xi = dc.decode(self.samples(first - lead, cover), lay)
+                xr, xi = xr[lead:lead + n_samples], xi[lead:lead + n_samples]
+            return xr + 1j * xi
         if self.frontEnd is not None and not self.isComplex:
             return self.samples(first, n_samples).astype(np.float64) + 0j
         if self.packing is None:
