@@ -92,6 +92,11 @@ def main(argv=None):
     if args.probe:
         print_probe(rf)
     mgr = ChannelManager(rf, keepCorrelationMap=False)
+    plan = getattr(rf.frontEnd, "array", None) if rf.frontEnd is not None else None
+    if plan is not None:              # a multi-antenna recording ([RFSIGNAL] array_lanes): the weights its elements are combined with
+        w = getattr(mgr, "arrayWeights", rf.frontEnd.config.array.weights)
+        print(f"array of {len(w)} elements, {plan.mode}" + (f" over the first {plan.train_ms} ms" if plan.adaptive else "") + ": weights "
+              + ", ".join(f"{v.real:+.4f}{v.imag:+.4f}j" for v in w))
     mgr.addChannel(plugin, ccfg, max(len(prns), int(rcfg["DEFAULT"].get("nb_channels", len(prns)))))
     for p in prns:
         mgr.requestTracking(p)

@@ -853,6 +853,58 @@ int sdr_ddc_create_layout(sdr_engine* e, const sdr_ddc_cfg* cfg, int interpolati
  * packed push that is not whole bytes */
 int64_t sdr_ddc_layout_bytes(const sdr_ddc_layout* layout, int64_t n_in);
 
+/* ------------------------------------------------- antenna arrays: the elements of a multi-element recording combined in the converter
+ * sdr_ddc_create_array makes a converter over a recording that interleaves the K elements of an antenna array, K in 2..8: the
+ * kernels decode the K elements of a frame where they load it and hand the mixer ONE input, x = w^H s -- with weights that put a
+ * null on a broadband jammer (power inversion, MVDR) the defence the blanker and the excisor cannot give.  Nothing downstream of
+ * the ring changes and the recording crosses the link and lies in HBM as it is, packed if it is packed.  The NumPy form of what
+ * follows is sydr_amd/signal/array.py `statement`; it is the only yardstick.
+ * An array is an input layout (above) plus K elements, element a at lane lanes[a] of the frame: distinct lanes, each with
+ * lanes[a] >= 0 and lanes[a] + (COMPLEX ? 2 : 1) <= stride, in any order, adjacent or not; layout->lane is not read.  Element a
+ * of frame j is decoded exactly as the layout decodes a stream at that lane: s_a = sr_a + i si_a (si = 0 of a real layout,
+ * SWAP_IQ honoured).  With weights w_a = wr_a + i wi_a = weights[a][0] + i weights[a][1], finite doubles, the converter's input
+ * j is x_j = sum_a conj(w_a) s_a, formed in fp64 in this order and no other, every product and every sum rounded, no contraction:
+ *   re = 0; im = 0
+ *   for a = 0 .. K-1:   re = re + wr_a sr_a;  re = re + wi_a si_a;  im = im + wr_a si_a;  im = im - wi_a sr_a
+ * From x_j on everything is the converter's statement above (p_j, t_j, z_j, v_m, the resampler's form, the mitigator, the
+ * ring's formats).  Weights belong to input indices: sdr_ddc_array_weights takes effect with the first input of the next push
+ * (it is ordered on the engine's stream behind the pushes queued so far), earlier inputs keep the x_j they had -- the history
+ * holds the last Tp - 1 COMBINED inputs as cf64 -- so with the weight changes at the same input indices the ring does not depend
+ * on how the stream was cut into pushes, bit for bit.  Bit for bit too, in every ring format: the weights e_a (1 at a, 0
+ * elsewhere) give the ring of sdr_ddc_create_layout with lane = lanes[a]; a packed array gives the ring of the INT8 array on the
+ * unpacked bytes.  The C-ABI takes weights and does not solve for them (sydr_amd/signal/array.py has the two usual rules).
+ * Covariance (flags = SDR_DDC_ARRAY_MEASURE; one more pass over the staged bytes of every push).  Over the inputs j pushed
+ * since creation, reset or the last clearing read:
+ *   R[a][b] = sum_j s_a conj(s_b):   re = sum (sr_a sr_b + si_a si_b),   im = sum (si_a sr_b - sr_a si_b),   n = their number
+ * For INT8, INT16 and PACKED fields the sums are exact 64-bit integers, each converted to double once at the read: the same
+ * numbers on every run and those of the statement, equal, not close.  For FLOAT32 fields the device adds in fp64 in a fixed
+ * order of its own (the same pushes give the same bits); a component differs from the statement's by at most
+ * 2 n 2^-52 sum_j (|sr_a sr_b| + |si_a si_b|) and correspondingly for the imaginary part.  sdr_ddc_array_covariance waits for
+ * the engine's stream and writes R as [K][K][2] doubles (row a, column b, re then im; the lower triangle the conjugate of the
+ * upper) and *n; clear != 0 zeroes both behind the read.
+ * sdr_ddc_reset zeroes the history and the covariance and keeps the weights.  Every other sdr_ddc_* call takes the handle as it
+ * takes any converter's: reset, push, push_queue, out_count, destroy, mitigate, delay, mitigation_stats, and
+ * sdr_ddc_layout_bytes (of the layout) says the bytes of a push.
+ * SDR_ERR_INVALID: NULL arguments, n_elements outside 2..8, a repeated or out-of-frame lane, a non-finite weight, an unknown
+ * flag, a layout outside its limits, every cause of sdr_ddc_create_layout's cfg, and a converter without an array passed to
+ * sdr_ddc_array_weights or sdr_ddc_array_covariance; SDR_ERR_STATE: sdr_ddc_array_covariance on a converter made without
+ * SDR_DDC_ARRAY_MEASURE.  A refused call changes nothing.  Scopes: those of the converter ("ddc_kernel" / "resample_kernel",
+ * "ddc_history_kernel", "call_ddc_push") and "ddc_array_cov_kernel" for the covariance pass.  A converter of sdr_ddc_create,
+ * sdr_ddc_create_rational or sdr_ddc_create_layout makes exactly the launches, and writes exactly the bytes, it always made. */
+#define SDR_DDC_ARRAY_MEASURE 1
+typedef struct sdr_ddc_array {
+    int32_t n_elements, flags;   /* K in 2..8; flags: 0 or SDR_DDC_ARRAY_MEASURE */
+    int32_t lanes[8];            /* the first K are read */
+    double weights[8][2];        /* w_a = weights[a][0] + i weights[a][1]; the first K are read */
+} sdr_ddc_array;
+/* cfg, interpolation and layout as for sdr_ddc_create_layout (layout->lane is not read) */
+int sdr_ddc_create_array(sdr_engine* e, const sdr_ddc_cfg* cfg, int interpolation, const sdr_ddc_layout* layout, const sdr_ddc_array* array,
+                         sdr_ddc** out);
+/* w = [K][2]; from the next push on; ordered on the stream */
+int sdr_ddc_array_weights(sdr_engine* e, sdr_ddc* d, const double* w);
+/* R = [K][K][2]; waits for the stream */
+int sdr_ddc_array_covariance(sdr_engine* e, sdr_ddc* d, double* R, int64_t* n, int clear);
+
 /* ------------------------------------------------- pulse blanking and narrow-band excision in front of the ring
  * An opt-in stage of a converter, between the filter's fp64 output v and the ring's format: a threshold blanker against pulsed
  * interference (DME, radar, a switching supply) and a frequency-domain excisor with windowed overlap-add against carrier-wave

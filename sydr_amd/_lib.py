@@ -127,6 +127,14 @@ DDC_FIELD_INT8, DDC_FIELD_INT16, DDC_FIELD_FLOAT32, DDC_FIELD_PACKED = 0, 1, 2, 
 DDC_LAYOUT_COMPLEX, DDC_LAYOUT_SWAP_IQ, DDC_LAYOUT_MSB_FIRST = 1, 2, 4
 
 
+class DdcArray(C.Structure):
+    """sdr_ddc_array (include/sydr_amd.h): the lanes and weights of the K elements a converter combines."""
+    _fields_ = [("n_elements", C.c_int32), ("flags", C.c_int32), ("lanes", C.c_int32 * 8), ("weights", (C.c_double * 2) * 8)]
+
+
+DDC_ARRAY_MEASURE = 1
+
+
 class MitCfg(C.Structure):
     """sdr_mit_cfg (include/sydr_amd.h): the blanker's level, lead and hold, the excisor's transform length and limits."""
     _fields_ = [("nfft", C.c_int32), ("blank_lead", C.c_int32), ("blank_hold", C.c_int32), ("flags", C.c_int32),
@@ -293,6 +301,9 @@ _PROTOTYPES = {
     "sdr_ddc_create_rational": (C.c_int, [_VP, C.POINTER(DdcCfg), C.c_int, C.POINTER(_VP)]),
     "sdr_ddc_create_layout": (C.c_int, [_VP, C.POINTER(DdcCfg), C.c_int, C.POINTER(DdcLayout), C.POINTER(_VP)]),
     "sdr_ddc_layout_bytes": (C.c_int64, [C.POINTER(DdcLayout), C.c_int64]),
+    "sdr_ddc_create_array": (C.c_int, [_VP, C.POINTER(DdcCfg), C.c_int, C.POINTER(DdcLayout), C.POINTER(DdcArray), C.POINTER(_VP)]),
+    "sdr_ddc_array_weights": (C.c_int, [_VP, _VP, C.POINTER(C.c_double)]),
+    "sdr_ddc_array_covariance": (C.c_int, [_VP, _VP, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),
     "sdr_ddc_destroy": (None, [_VP, _VP]),
     "sdr_ddc_reset": (C.c_int, [_VP, _VP]),
     "sdr_ddc_push": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),

@@ -83,6 +83,8 @@ class ChannelManager:
             self._upload_block = self._upload_block_converted
         self.sharedBuffer = CircularBuffer(buffersize, rfSignal.dtype, engine=engine, fmt=fmt)
         self._ddc = engine.ddc_create(self._frontEnd.config) if self._frontEnd is not None else None
+        if self._ddc is not None and getattr(self._frontEnd, "array", None) is not None and self._frontEnd.array.adaptive:
+            self._train_array()                                         # (power inversion / MVDR: signal/array.py)
         if self._ddc is not None and self._frontEnd.mitigation is not None:
             engine.ddc_mitigate(self._ddc, self._frontEnd.mitigation)   # (pulse blanker / excisor: signal/mitigate.py)
         self.resultQueue = None
@@ -426,6 +428,32 @@ class ChannelManager:
         if data.size % per:
             raise ValueError("interleaved I,Q data needs an even number of elements")
         return data, data.size // per
+
+    def _train_array(self):
+        """The adaptive weights of a multi-antenna recording: its first `array_train_ms` milliseconds pushed with unit weight on
+        the reference element (into the ring's start, which the recording proper overwrites), the covariance read, the weights
+        solved for and set, the converter reset -- the recording then begins again at its first sample (this reads it by
+        position and leaves its cursor alone) and the whole ring is made with one weight vector."""
+        plan, sig = self._frontEnd.array, self.rfSignal
+        per_ms = sig.inputSamplesPerMs
+        n_ms = min(plan.train_ms, sig.totalSamples // per_ms)
+        if n_ms < 1:
+            raise ValueError("the recording is shorter than a millisecond: nothing to train the array's weights on")
+        for ms in range(n_ms):
+            block, _ = self._raw_input(sig.samples(ms * per_ms, per_ms))
+            self.engine.ddc_push(self._ddc, block, 0)
+        R, n = self.engine.ddc_array_covariance(self._ddc, True)
+        self.arrayWeights = plan.solve(R, n)
+        self.engine.ddc_array_weights(self._ddc, self.arrayWeights)
+        self.engine.ddc_reset(self._ddc)
+
+    def arrayCovariance(self, clear: bool = False):
+        """(R [K][K] complex128, n) of the live converter of a multi-antenna recording made with an adaptive `array_mode`: the
+        covariance of the elements over the inputs pushed since the weights were trained (or the last clearing read); None
+        without such a converter."""
+        if self._ddc is None or getattr(self._frontEnd, "array", None) is None or not self._frontEnd.config.array.measure:
+            return None
+        return self.engine.ddc_array_covariance(self._ddc, clear)
 
     def _addNewRFData_converted(self, data):
         """addNewRFData of a recording with a front end: `data` is raw INPUT (rfSignal.getMilliseconds), which the device's

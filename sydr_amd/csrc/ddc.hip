@@ -8,6 +8,7 @@
 // ddc_kernel write its outputs as cf64 into the mitigator's work buffer in place of the ring; without one a push makes the
 // launches it always made.
 // A converter made by sdr_ddc_create_rational with interpolation L > 1 keeps its handle here and its kernels in resample.hip.
+// A converter made by sdr_ddc_create_array (ddc_array.hip) runs the same kernels with a third loader, DdcArrayLoad.
 #include "engine_internal.h"
 #include "ddc_handle.h"
 #include "ddc_tiles.h"
@@ -91,6 +92,15 @@ __global__ __launch_bounds__(kDdcThreads) void ddc_layout_kernel(const void* __r
                     ring_offset, capacity);
 }
 
+// The same kernel over a converter with an array (sdr_ddc_create_array): the K elements of every frame combined where it is loaded.
+__global__ __launch_bounds__(kDdcThreads) void ddc_array_kernel(const void* __restrict__ in, const void* __restrict__ hist,
+                                                                const double* __restrict__ taps, void* __restrict__ ring, DdcPush push,
+                                                                int tile, DdcLayout lay, DdcArray arr, int out_fmt, uint64_t fcw, double gain,
+                                                                int64_t ring_offset, int64_t capacity) {
+    extern __shared__ __attribute__((aligned(16))) char ddc_smem[];
+    ddc_kernel_body((double2*)ddc_smem, in, hist, taps, ring, push, tile, DdcArrayLoad{lay, arr}, out_fmt, fcw, gain, ring_offset, capacity);
+}
+
 // The history after a push: one workgroup, every lane reads its element (out of the block, or -- a push shorter than T-1 --
 // further up the old history) before any lane writes.  `unit` = bytes per raw input.
 __global__ __launch_bounds__(kDdcMaxTaps) void ddc_history_kernel(const void* __restrict__ in, void* hist, int64_t n_in, int T, int unit) {
@@ -125,8 +135,28 @@ __global__ __launch_bounds__(kDdcMaxTaps) void ddc_layout_history_kernel(const v
     if (i < T - 1) ddc_layout_history_store(hist, i, h, re, im);
 }
 
+// The same for a converter with an array: an element out of the block is combined with the push's weights, one out of the old
+// history keeps the value it was combined to; both are stored as cf64.
+__global__ __launch_bounds__(kDdcMaxTaps) void ddc_array_history_kernel(const void* __restrict__ in, void* hist, int64_t n_in, int T, DdcLayout lay,
+                                                                        DdcArray arr) {
+    const int i = threadIdx.x;
+    double re = 0.0, im = 0.0;
+    if (i < T - 1) {
+        const int64_t src = ddc_hist_source(n_in, T, i);
+        if (src >= 0) ddc_array_load(in, src, lay, arr, &re, &im);
+        else ddc_array_history_load((const void*)hist, ~src, &re, &im);
+    }
+    __syncthreads();
+    if (i < T - 1) ddc_array_history_store(hist, i, re, im);
+}
+
 void sdr::ddc_history_launch(sdr_engine* e, sdr_ddc* d, int64_t n_in) {
     ProfScope ps(e, "ddc_history_kernel");
+    if (d->has_array) {
+        hipLaunchKernelGGL(ddc_array_history_kernel, dim3(1), dim3(kDdcMaxTaps), 0, e->stream, (const void*)e->ddc_stage.ptr, d->hist, n_in,
+                           d->Tp, d->layout, d->array);
+        return;
+    }
     if (d->has_layout) {
         hipLaunchKernelGGL(ddc_layout_history_kernel, dim3(1), dim3(kDdcMaxTaps), 0, e->stream, (const void*)e->ddc_stage.ptr, d->hist, n_in,
                            d->Tp, d->layout);
@@ -170,6 +200,8 @@ static int ddc_push_impl(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in
     // one copy command brings the raw inputs into the engine's staging buffer in HBM (no kernel reads host memory), the
     // kernels follow it on the same stream -- whose order is all the guard the buffer and the history need
     if (int rc = sdr_devbuf_reserve(e, &e->ddc_stage, bytes)) return rc;
+    if (d->has_array)
+        if (int rc = ddc_array_cov_reserve(e, d, n_in)) return rc;
     // with a mitigator the kernel's destination is its linear cf64 work buffer, the first output behind the kept state
     void* dst = e->iq;
     int dst_fmt = e->iq_fmt;
@@ -185,7 +217,11 @@ static int ddc_push_impl(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in
         const int64_t tiles = ddc_tiles(push, tile);
         const size_t lds = (size_t)((tile - 1) * d->D + d->T) * sizeof(double2);
         ProfScope ps(e, "ddc_kernel");
-        if (d->has_layout)
+        if (d->has_array)
+            hipLaunchKernelGGL(ddc_array_kernel, dim3((unsigned)tiles), dim3(kDdcThreads), lds, e->stream, (const void*)e->ddc_stage.ptr,
+                               (const void*)d->hist, (const double*)d->taps, dst, push, tile, d->layout, d->array, dst_fmt, d->fcw, d->gain, dst_off,
+                               dst_cap);
+        else if (d->has_layout)
             hipLaunchKernelGGL(ddc_layout_kernel, dim3((unsigned)tiles), dim3(kDdcThreads), lds, e->stream, (const void*)e->ddc_stage.ptr,
                                (const void*)d->hist, (const double*)d->taps, dst, push, tile, d->layout, dst_fmt, d->fcw, d->gain, dst_off, dst_cap);
         else
@@ -194,6 +230,7 @@ static int ddc_push_impl(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in
     }
     if (d->mit && push.n_out > 0)
         if (int rc = mit_push_finish(e, d->mit, push.m_first, push.n_out, off)) return rc;
+    if (d->has_array) ddc_array_cov_launch(e, d, n_in);
     if (d->T > 1) ddc_history_launch(e, d, n_in);
     SDR_HIP(hipGetLastError());
     d->n_seen += n_in;
@@ -286,6 +323,8 @@ void sdr_ddc_destroy(sdr_engine* e, sdr_ddc* d) {
     if (e && sdr_set_device(e) == SDR_OK) (void)hipStreamSynchronize(e->stream);     // (a queued push may still read them)
     if (d->taps) (void)hipFree(d->taps);
     if (d->hist) (void)hipFree(d->hist);
+    if (d->cov) (void)hipFree(d->cov);
+    if (d->cov_slab.ptr) (void)hipFree(d->cov_slab.ptr);
     mit_destroy(nullptr, d->mit);
     delete d;
 }
@@ -295,6 +334,8 @@ int sdr_ddc_reset(sdr_engine* e, sdr_ddc* d) {
     if (int rc = ddc_check(e, d)) return rc;
     const size_t hist_bytes = (size_t)(d->Tp > 1 ? d->Tp - 1 : 1) * ddc_hist_unit(d);
     SDR_HIP(hipMemsetAsync(d->hist, 0, hist_bytes, e->stream));
+    if (d->cov) SDR_HIP(hipMemsetAsync(d->cov, 0, kDdcArrayCovSlots * sizeof(int64_t), e->stream));     // (the weights stay)
+    d->cov_n = 0;
     if (d->mit)
         if (int rc = mit_reset(e, d->mit)) return rc;
     d->n_seen = 0;

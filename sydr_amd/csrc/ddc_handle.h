@@ -4,6 +4,7 @@
 
 #include "engine_internal.h"
 #include "ddc_layout.h"
+#include "ddc_array.h"
 #include "mitigate.h"
 
 struct sdr_ddc {
@@ -23,6 +24,14 @@ struct sdr_ddc {
     // load them and `hist` holds the last Tp - 1 inputs DECODED (ddc_layout.h)
     bool has_layout = false;
     sdr::DdcLayout layout = {};
+    // a converter made by sdr_ddc_create_array (has_layout too): the kernels combine the K elements of a frame where they load
+    // it and `hist` holds the last Tp - 1 COMBINED inputs as cf64 (ddc_array.h).  With SDR_DDC_ARRAY_MEASURE `cov` is the device's
+    // 64 covariance slots (int64, or fp64 of a float32 layout), cov_n the inputs they hold, cov_slab the float pass's rows
+    bool has_array = false;
+    sdr::DdcArray array = {};
+    void* cov = nullptr;
+    int64_t cov_n = 0;
+    DevBuf cov_slab;
 };
 
 inline size_t ddc_in_bytes(int in_fmt) {
@@ -36,7 +45,10 @@ inline size_t ddc_in_bytes(int in_fmt) {
 }
 
 // Bytes one input takes in the history.
-inline size_t ddc_hist_unit(const sdr_ddc* d) { return d->has_layout ? (size_t)sdr::ddc_layout_history_unit(d->layout) : ddc_in_bytes(d->in_fmt); }
+inline size_t ddc_hist_unit(const sdr_ddc* d) {
+    if (d->has_array) return (size_t)sdr::kDdcArrayHistoryUnit;
+    return d->has_layout ? (size_t)sdr::ddc_layout_history_unit(d->layout) : ddc_in_bytes(d->in_fmt);
+}
 
 __device__ __forceinline__ void ddc_load(const void* __restrict__ p, int64_t i, int in_fmt, double* re, double* im) {
     switch (in_fmt) {
@@ -67,6 +79,13 @@ struct DdcLayoutLoad {
     __device__ __forceinline__ void block(const void* __restrict__ p, int64_t i, double* re, double* im) const { sdr::ddc_layout_load(p, i, lay, re, im); }
     __device__ __forceinline__ void history(const void* __restrict__ p, int64_t i, double* re, double* im) const { sdr::ddc_layout_load(p, i, hist, re, im); }
 };
+// ... or an array's: the K elements of a frame combined with the weights, the history holding combined inputs as cf64.
+struct DdcArrayLoad {
+    sdr::DdcLayout lay;
+    sdr::DdcArray arr;
+    __device__ __forceinline__ void block(const void* __restrict__ p, int64_t i, double* re, double* im) const { sdr::ddc_array_load(p, i, lay, arr, re, im); }
+    __device__ __forceinline__ void history(const void* __restrict__ p, int64_t i, double* re, double* im) const { sdr::ddc_array_history_load(p, i, re, im); }
+};
 
 __device__ __forceinline__ double ddc_clip_rint(double v, double lim) { return fmin(fmax(rint(v), -lim), lim); }
 
@@ -86,5 +105,10 @@ void ddc_history_launch(sdr_engine* e, sdr_ddc* d, int64_t n_in);
 // they are not whole (nothing has changed then).
 int ddc_push_bytes(const sdr_ddc* d, int64_t n_in, size_t* bytes);
 int rs_push_impl(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in, int64_t off, int64_t* n_out, bool wait);
+// ddc_array.hip: the covariance pass of a converter with SDR_DDC_ARRAY_MEASURE over the n_in frames in the staging buffer, behind
+// the converter's kernel on the engine's stream, under the scope "ddc_array_cov_kernel"; no-op for every other converter.
+// ddc_array_cov_reserve, before the push has changed anything, makes room for the float pass's rows (SDR_ERR_NOMEM otherwise).
+int ddc_array_cov_reserve(sdr_engine* e, sdr_ddc* d, int64_t n_in);
+void ddc_array_cov_launch(sdr_engine* e, sdr_ddc* d, int64_t n_in);
 
 }  // namespace sdr

@@ -252,12 +252,22 @@ def layout_struct(layout) -> "_lib.DdcLayout":
     return c
 
 
+def array_struct(array) -> "_lib.DdcArray":
+    """sdr_ddc_array of a signal.array.ArrayGeometry."""
+    c = _lib.DdcArray(int(array.n_elements), int(array.flags))
+    for a, lane in enumerate(array.lanes):
+        c.lanes[a] = lane
+        c.weights[a][0], c.weights[a][1] = float(array.weights[a].real), float(array.weights[a].imag)
+    return c
+
+
 class _Ddc:
     """Handle of a device-resident down-converter (Engine.ddc_create)."""
-    __slots__ = ("handle", "in_fmt", "nfft", "layout")
+    __slots__ = ("handle", "in_fmt", "nfft", "layout", "n_elements")
 
-    def __init__(self, handle, in_fmt, layout=None):
+    def __init__(self, handle, in_fmt, layout=None, n_elements=0):
         self.handle, self.in_fmt = handle, in_fmt
+        self.n_elements = n_elements  # K of a converter made by sdr_ddc_create_array, else 0
         self.layout = layout          # signal.downconvert.InputLayout of a converter made by sdr_ddc_create_layout, else None
         self.nfft = 0                 # of the attached mitigator's excisor (Engine.ddc_mitigate)
 
@@ -405,6 +415,11 @@ class Engine:
         h = C.c_void_p()
         interpolation = int(cfg.interpolation)
         layout = getattr(cfg, "layout", None)
+        array = getattr(cfg, "array", None)
+        if array is not None:             # an antenna array: the K elements of the layout's frames combined (signal/array.py)
+            check(self._lib.sdr_ddc_create_array(self._h, C.byref(c), interpolation, C.byref(layout_struct(layout)), C.byref(array_struct(array)),
+                                                 C.byref(h)))
+            return _Ddc(h, int(cfg.in_fmt), layout, array.n_elements)
         if layout is not None:            # an input layout: packed, float32 or interleaved recordings (in_fmt is not read)
             check(self._lib.sdr_ddc_create_layout(self._h, C.byref(c), interpolation, C.byref(layout_struct(layout)), C.byref(h)))
             return _Ddc(h, int(cfg.in_fmt), layout)
@@ -434,6 +449,20 @@ class Engine:
         if status:
             check(status)
         return n_out.value
+
+    def ddc_array_weights(self, ddc, weights):
+        """The weights of an array converter from its next push on (sdr_ddc_array_weights; ordered on the stream)."""
+        from .signal.array import as_weights
+        w = as_weights(weights, ddc.n_elements or 1)
+        flat = np.ascontiguousarray(np.stack([w.real, w.imag], axis=1))
+        check(self._lib.sdr_ddc_array_weights(self._h, ddc.handle, flat.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def ddc_array_covariance(self, ddc, clear: bool = False):
+        """(R [K][K] complex128, n) of an array converter made with `measure` (sdr_ddc_array_covariance; waits for the stream)."""
+        K = max(ddc.n_elements, 1)
+        R, n = np.zeros((K, K, 2)), C.c_int64(0)
+        check(self._lib.sdr_ddc_array_covariance(self._h, ddc.handle, R.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n), int(bool(clear))))
+        return R[..., 0] + 1j * R[..., 1], n.value
 
     def ddc_push(self, ddc, raw: np.ndarray, ring_offset: int = 0) -> int:
         """Raw inputs (real: one integer each; complex: interleaved I,Q; a converter with a layout: the recording's bytes, whole

@@ -45,6 +45,9 @@ keep finite: a NaN or Inf may change only the outputs whose filter window contai
 {INT16 real, 1, 0}, {INT8 complex, 2, 0}, {INT16 complex, 2, 0} are IN_R8, IN_R16, IN_CI8, IN_CI16; a packed layout is the INT8
 layout on the unpacked bytes; float32 that holds integers within int16 is the INT16 layout on those integers -- bit for bit.
 
+With an ARRAY (`DownConverterConfig.array`, signal/array.py) the K elements of a frame are combined, x_j = w^H s_j, where the frame
+is decoded; that file states the combine, the covariance and the weight rules, and from x_j on everything is this statement.
+
 Float rings store v
 (cf32: rounded to nearest float), integer rings clip(rint(v)), ties to even, clip +-127 (ci8) / +-32767 (ci16).
 Every operation below is one IEEE fp64 operation on real arrays in a fixed order (k ascending, product then sum), and the
@@ -245,6 +248,7 @@ class DownConverterConfig:
     gain: float = 1.0
     interpolation: int = 1
     layout: InputLayout | None = None      # an input layout: in_fmt is then not consulted
+    array: object | None = None            # signal.array.ArrayGeometry: the K elements of a frame combined (needs a layout)
 
     def __post_init__(self):
         self.taps = np.ascontiguousarray(self.taps, dtype=np.float64).reshape(-1)
@@ -255,6 +259,13 @@ class DownConverterConfig:
                 raise ValueError("layout is an InputLayout")
         elif self.in_fmt not in _IN_DTYPE:
             raise ValueError(f"unknown input format {self.in_fmt}")
+        if self.array is not None:
+            from .array import ArrayGeometry
+            if not isinstance(self.array, ArrayGeometry):
+                raise ValueError("array is an ArrayGeometry")
+            if self.layout is None:
+                raise ValueError("an array needs an input layout")
+            self.array.check(self.layout)
         L = self.interpolation
         if not 1 <= L <= MAX_INTERPOLATION:
             raise ValueError(f"interpolation {L} outside 1..{MAX_INTERPOLATION}")

@@ -21,6 +21,14 @@ Beside `decimation` the key `sample_format` describes recordings the four intege
 `is_complex`, else 1, by default), `frame_lane` (the stream's first field in its frame, default 0) and `swap_iq` (1: pairs are
 stored Q before I) pick one stream out of a file that interleaves several.  Such a recording's slabs are whole-byte views of
 its bytes, counted in frames.
+Beside `sample_format` the key `array_lanes` (a comma list of K = 2..8 lanes: each element's first field in the frame; `frame_lane`
+is then not read) makes the recording a multi-antenna one whose elements the converter combines, x = w^H s, where it decodes the
+frame (array.py): `array_mode` is `fixed` (the default; `array_weights`, K re,im pairs, default 1 on `array_reference`),
+`power_inversion` or `mvdr` (`array_steering`, K re,im pairs); `array_reference` (default 0), `array_loading` (default 1e-3)
+and `array_train_ms` (default 2) belong to the two adaptive modes, in which the receiver first pushes the recording's first
+`array_train_ms` milliseconds with unit weight on the reference element, reads the covariance, solves for the weights, sets
+them, resets the converter and begins the recording again from its first sample: the whole ring is made with one weight
+vector.  Mitigation keys beside array keys are refused.
 Such a recording may also ask for interference mitigation between the converter and the ring (mitigate.py; keys
 `blanking_factor` with `blanking_lead`, `blanking_hold`, and `excision_nfft` with `excision_margin_db`; `calibration_ms`):
 the blanker's level and the excisor's limits are measured once, on the host, over the converter's output of the recording's
@@ -41,6 +49,7 @@ from .packing import Packing, unpack
 
 
 LAYOUT_KEYS = ("sample_format", "frame_fields", "frame_lane", "swap_iq")
+ARRAY_KEYS = ("array_lanes", "array_mode", "array_weights", "array_steering", "array_reference", "array_loading", "array_train_ms")
 MITIGATION_KEYS = ("blanking_factor", "blanking_lead", "blanking_hold", "excision_nfft", "excision_margin_db", "calibration_ms")
 
 
@@ -48,8 +57,9 @@ class FrontEnd:
     """How a recording's raw input becomes the ring's samples: the down-converter's settings (downconvert.py), its group delay in
     INPUT samples -- common to all channels; reported, not compensated --, the ring's sample width and the shift in Hz."""
 
-    def __init__(self, config, output_bits: int, shift_hz: float, calibrate=None):
+    def __init__(self, config, output_bits: int, shift_hz: float, calibrate=None, array=None):
         self.config = config
+        self.array = array                              # ArrayPlan of a multi-antenna recording (`array_lanes`), else None
         self.decimation = config.decimation
         self.interpolation = config.interpolation
         self.groupDelay = config.group_delay
@@ -71,6 +81,27 @@ class FrontEnd:
         """The mitigator's delay in RING samples -- common to all channels; reported, not compensated."""
         m = self.mitigation
         return m.delay if m is not None else 0
+
+
+class ArrayPlan:
+    """How the weights of a multi-antenna recording come about: `fixed` (those of the configuration) or, measured on the
+    recording's first `train_ms` milliseconds, `power_inversion` / `mvdr` (array.py)."""
+
+    def __init__(self, mode: str, reference: int, loading: float, train_ms: int, steering=None):
+        self.mode, self.reference, self.loading, self.train_ms, self.steering = mode, reference, loading, train_ms, steering
+
+    @property
+    def adaptive(self) -> bool:
+        return self.mode != "fixed"
+
+    def solve(self, R, n):
+        """The weights for the covariance R of n inputs."""
+        from . import array as ar
+        if self.mode == "power_inversion":
+            return ar.power_inversion(R, n, self.reference, self.loading)
+        if self.mode == "mvdr":
+            return ar.mvdr(R, n, self.steering, self.loading)
+        raise ValueError("fixed weights are not solved for")
 
 
 class RFSignal:
@@ -101,7 +132,7 @@ class RFSignal:
         else:
             if "interpolation" in configuration:
                 raise ValueError("`interpolation` needs `decimation` beside it: the ring's rate is sampling_frequency * L / M")
-            for key in LAYOUT_KEYS + MITIGATION_KEYS:
+            for key in LAYOUT_KEYS + ARRAY_KEYS + MITIGATION_KEYS:
                 if key in configuration:
                     raise ValueError(f"`{key}` needs a front end: set `decimation` (1 with `filter_taps = 1` converts nothing)")
         if not self.isComplex and self.frontEnd is None:
@@ -119,7 +150,7 @@ class RFSignal:
         from . import downconvert as dc
         sample_format = str(configuration["sample_format"]).strip().lower() if "sample_format" in configuration else None
         if sample_format is None:
-            for key in LAYOUT_KEYS:
+            for key in LAYOUT_KEYS + ARRAY_KEYS:
                 if key in configuration:
                     raise ValueError(f"`{key}` needs `sample_format` beside it")
             if self.packing is not None:
@@ -150,8 +181,9 @@ class RFSignal:
             raise ValueError(f"output_bits is 8 or 16, not {out_bits}")
         in_fmt = {(False, 8): dc.IN_R8, (False, 16): dc.IN_R16, (True, 8): dc.IN_CI8, (True, 16): dc.IN_CI16}.get((self.isComplex, bits), dc.IN_R8)
         taps = dc.design_lowpass(n_taps, cutoff) if L == 1 else dc.design_resampler(L, D, n_taps, cutoff)
-        config = dc.DownConverterConfig(in_fmt, D, taps, dc.frequency_word(shift, fs_in), gain, L, self.layout)
-        self.frontEnd = FrontEnd(config, out_bits, shift, self._mitigation_keys(configuration, config))
+        geometry, plan = self._array_keys(configuration)
+        config = dc.DownConverterConfig(in_fmt, D, taps, dc.frequency_word(shift, fs_in), gain, L, self.layout, geometry)
+        self.frontEnd = FrontEnd(config, out_bits, shift, self._mitigation_keys(configuration, config), plan)
         # what the channels read is the ring's: its rate, and the carrier's residual offset there
         self.samplingFrequency = fs_in * L / D
         self.interFrequency = if_in - shift
@@ -180,6 +212,52 @@ class RFSignal:
         if per_ms * layout.frame_bits % 8:
             raise ValueError(f"a millisecond of {per_ms} frames of {stride} fields of {bits} bit(s) is not a whole number of bytes")
         return layout
+
+    def _array_keys(self, configuration):
+        """The opt-in keys `array_lanes`, `array_mode`, `array_weights`, `array_steering`, `array_reference`, `array_loading`,
+        `array_train_ms` -> (array.ArrayGeometry, ArrayPlan), or (None, None) without `array_lanes`."""
+        from . import array as ar
+        if "array_lanes" not in configuration:
+            for key in ARRAY_KEYS:
+                if key in configuration:
+                    raise ValueError(f"`{key}` needs `array_lanes` beside it")
+            return None, None
+        for key in MITIGATION_KEYS:
+            if key in configuration:
+                raise ValueError(f"`{key}` beside `array_lanes`: the calibration of a mitigator behind an array is not offered")
+
+        def pairs(key, K):
+            v = [float.fromhex(t.strip()) if "0x" in t.lower() else float(t) for t in str(configuration[key]).split(",")]
+            if len(v) != 2 * K:
+                raise ValueError(f"`{key}` is {K} re,im pairs, {len(v)} numbers given")
+            return ar.as_weights(np.array(v).reshape(K, 2), K)
+        lanes = [int(v) for v in str(configuration["array_lanes"]).split(",")]
+        K = len(lanes)
+        mode = str(configuration["array_mode"]).strip().lower() if "array_mode" in configuration else "fixed"
+        if mode not in ("fixed", "power_inversion", "mvdr"):
+            raise ValueError(f"array_mode is 'fixed', 'power_inversion' or 'mvdr', not {mode!r}")
+        reference = int(configuration["array_reference"]) if "array_reference" in configuration else 0
+        if not 0 <= reference < K:
+            raise ValueError(f"array_reference {reference} outside 0..{K - 1}")
+        loading = float(configuration["array_loading"]) if "array_loading" in configuration else ar.DEFAULT_LOADING
+        if not loading >= 0.0:
+            raise ValueError("array_loading is not negative")
+        train_ms = int(configuration["array_train_ms"]) if "array_train_ms" in configuration else 2
+        if train_ms < 1:
+            raise ValueError("array_train_ms is at least 1")
+        allowed = {"fixed": ("array_weights", "array_reference"), "power_inversion": ("array_reference", "array_loading", "array_train_ms"),
+                   "mvdr": ("array_steering", "array_reference", "array_loading", "array_train_ms")}[mode]
+        for key in ARRAY_KEYS[2:]:
+            if key in configuration and key not in allowed:
+                raise ValueError(f"`{key}` does not belong to array_mode {mode!r}")
+        if mode == "mvdr" and "array_steering" not in configuration:
+            raise ValueError("array_mode 'mvdr' needs `array_steering`")
+        # (an adaptive mode trains with unit weight on the reference element and measures the covariance)
+        weights = pairs("array_weights", K) if "array_weights" in configuration else ar.unit_weights(K, reference)
+        steering = pairs("array_steering", K) if mode == "mvdr" else None
+        geometry = ar.ArrayGeometry(lanes, weights, measure=mode != "fixed")
+        geometry.check(self.layout)
+        return geometry, ArrayPlan(mode, reference, loading, train_ms, steering)
 
     def _layout_span(self, first: int, n_samples: int):
         """Frames [first, first + n_samples) of a recording with a layout as elements of the mapped file: whole bytes."""
