@@ -304,6 +304,10 @@ _PROTOTYPES = {
     "sdr_ddc_create_array": (C.c_int, [_VP, C.POINTER(DdcCfg), C.c_int, C.POINTER(DdcLayout), C.POINTER(DdcArray), C.POINTER(_VP)]),
     "sdr_ddc_array_weights": (C.c_int, [_VP, _VP, C.POINTER(C.c_double)]),
     "sdr_ddc_array_covariance": (C.c_int, [_VP, _VP, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),
+    "sdr_ddc_create_stap": (C.c_int, [_VP, C.POINTER(DdcCfg), C.c_int, C.POINTER(DdcLayout), C.POINTER(DdcArray), C.c_int, C.POINTER(C.c_double),
+                                      C.POINTER(_VP)]),
+    "sdr_ddc_stap_weights": (C.c_int, [_VP, _VP, C.POINTER(C.c_double)]),
+    "sdr_ddc_stap_covariance": (C.c_int, [_VP, _VP, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),
     "sdr_ddc_destroy": (None, [_VP, _VP]),
     "sdr_ddc_reset": (C.c_int, [_VP, _VP]),
     "sdr_ddc_push": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),

@@ -442,10 +442,22 @@ class ChannelManager:
         for ms in range(n_ms):
             block, _ = self._raw_input(sig.samples(ms * per_ms, per_ms))
             self.engine.ddc_push(self._ddc, block, 0)
-        R, n = self.engine.ddc_array_covariance(self._ddc, True)
-        self.arrayWeights = plan.solve(R, n)
-        self.engine.ddc_array_weights(self._ddc, self.arrayWeights)
+        if plan.taps > 1:                 # space-time weights [T][K] from the lag covariance (signal/stap.py)
+            C, n = self.engine.ddc_stap_covariance(self._ddc, True)
+            self.arrayWeights = plan.solve(C, n)
+            self.engine.ddc_stap_weights(self._ddc, self.arrayWeights)
+        else:
+            R, n = self.engine.ddc_array_covariance(self._ddc, True)
+            self.arrayWeights = plan.solve(R, n)
+            self.engine.ddc_array_weights(self._ddc, self.arrayWeights)
         self.engine.ddc_reset(self._ddc)
+
+    @property
+    def arrayDelay(self) -> int:
+        """The delay of a space-time array's reference tap in INPUT samples (`array_reference_tap`; 0 without `array_taps`):
+        common to all channels, reported beside the converter's own delays and not compensated."""
+        plan = getattr(self._frontEnd, "array", None)
+        return plan.delay if plan is not None else 0
 
     def arrayCovariance(self, clear: bool = False):
         """(R [K][K] complex128, n) of the live converter of a multi-antenna recording made with an adaptive `array_mode`: the
@@ -453,6 +465,8 @@ class ChannelManager:
         without such a converter."""
         if self._ddc is None or getattr(self._frontEnd, "array", None) is None or not self._frontEnd.config.array.measure:
             return None
+        if self._frontEnd.array.taps > 1:     # (the lag covariance C [T][K][K] of a space-time array)
+            return self.engine.ddc_stap_covariance(self._ddc, clear)
         return self.engine.ddc_array_covariance(self._ddc, clear)
 
     def _addNewRFData_converted(self, data):

@@ -8,7 +8,8 @@
 // ddc_kernel write its outputs as cf64 into the mitigator's work buffer in place of the ring; without one a push makes the
 // launches it always made.
 // A converter made by sdr_ddc_create_rational with interpolation L > 1 keeps its handle here and its kernels in resample.hip.
-// A converter made by sdr_ddc_create_array (ddc_array.hip) runs the same kernels with a third loader, DdcArrayLoad.
+// A converter made by sdr_ddc_create_array (ddc_array.hip) runs the same kernels with a third loader, DdcArrayLoad, one made by
+// sdr_ddc_create_stap (ddc_stap.hip) with a fourth, DdcStapLoad.
 #include "engine_internal.h"
 #include "ddc_handle.h"
 #include "ddc_tiles.h"
@@ -101,6 +102,17 @@ __global__ __launch_bounds__(kDdcThreads) void ddc_array_kernel(const void* __re
     ddc_kernel_body((double2*)ddc_smem, in, hist, taps, ring, push, tile, DdcArrayLoad{lay, arr}, out_fmt, fcw, gain, ring_offset, capacity);
 }
 
+// The same kernel over a converter with space-time weights (sdr_ddc_create_stap): T frames of K elements combined per input.
+__global__ __launch_bounds__(kDdcThreads) void ddc_stap_kernel(const void* __restrict__ in, const void* __restrict__ hist,
+                                                               const double* __restrict__ tail, const double* __restrict__ taps,
+                                                               void* __restrict__ ring, DdcPush push, int tile, DdcLayout lay, DdcArray arr,
+                                                               DdcStap stap, int out_fmt, uint64_t fcw, double gain, int64_t ring_offset,
+                                                               int64_t capacity) {
+    extern __shared__ __attribute__((aligned(16))) char ddc_smem[];
+    ddc_kernel_body((double2*)ddc_smem, in, hist, taps, ring, push, tile, DdcStapLoad{lay, arr, stap, tail}, out_fmt, fcw, gain, ring_offset,
+                    capacity);
+}
+
 // The history after a push: one workgroup, every lane reads its element (out of the block, or -- a push shorter than T-1 --
 // further up the old history) before any lane writes.  `unit` = bytes per raw input.
 __global__ __launch_bounds__(kDdcMaxTaps) void ddc_history_kernel(const void* __restrict__ in, void* hist, int64_t n_in, int T, int unit) {
@@ -150,8 +162,33 @@ __global__ __launch_bounds__(kDdcMaxTaps) void ddc_array_history_kernel(const vo
     if (i < T - 1) ddc_array_history_store(hist, i, re, im);
 }
 
+// The same for a converter with space-time weights, and its raw tail: lane i < Tp - 1 takes element i of the history as the
+// array's kernel does, lane i < (T - 1) K element i % K of slot i / K of the tail -- out of the block, or, of a push shorter than
+// T - 1 frames, further up the old tail (a shift, ddc_stap_tail_next).  Every lane reads before any lane writes.
+__global__ __launch_bounds__(kDdcMaxTaps) void ddc_stap_history_kernel(const void* __restrict__ in, void* hist, double* tail, int64_t n_in, int Tp,
+                                                                       DdcLayout lay, DdcArray arr, DdcStap stap) {
+    const int i = threadIdx.x;
+    const int slot = i / arr.K, a = i - slot * arr.K;
+    const bool in_tail = i < (stap.T - 1) * arr.K;
+    double re = 0.0, im = 0.0, tr = 0.0, ti = 0.0;
+    if (i < Tp - 1) {
+        const int64_t src = ddc_hist_source(n_in, Tp, i);
+        if (src >= 0) ddc_stap_load(in, tail, src, lay, arr, stap, &re, &im);
+        else ddc_array_history_load((const void*)hist, ~src, &re, &im);
+    }
+    if (in_tail) ddc_stap_tail_next(in, tail, n_in, lay, arr, stap.T, slot, a, &tr, &ti);
+    __syncthreads();
+    if (i < Tp - 1) ddc_array_history_store(hist, i, re, im);
+    if (in_tail) ddc_stap_tail_store(tail, slot, arr.K, a, tr, ti);
+}
+
 void sdr::ddc_history_launch(sdr_engine* e, sdr_ddc* d, int64_t n_in) {
     ProfScope ps(e, "ddc_history_kernel");
+    if (d->has_stap) {
+        hipLaunchKernelGGL(ddc_stap_history_kernel, dim3(1), dim3(kDdcMaxTaps), 0, e->stream, (const void*)e->ddc_stage.ptr, d->hist, d->tail, n_in,
+                           d->Tp, d->layout, d->array, d->stap);
+        return;
+    }
     if (d->has_array) {
         hipLaunchKernelGGL(ddc_array_history_kernel, dim3(1), dim3(kDdcMaxTaps), 0, e->stream, (const void*)e->ddc_stage.ptr, d->hist, n_in,
                            d->Tp, d->layout, d->array);
@@ -217,7 +254,11 @@ static int ddc_push_impl(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in
         const int64_t tiles = ddc_tiles(push, tile);
         const size_t lds = (size_t)((tile - 1) * d->D + d->T) * sizeof(double2);
         ProfScope ps(e, "ddc_kernel");
-        if (d->has_array)
+        if (d->has_stap)
+            hipLaunchKernelGGL(ddc_stap_kernel, dim3((unsigned)tiles), dim3(kDdcThreads), lds, e->stream, (const void*)e->ddc_stage.ptr,
+                               (const void*)d->hist, (const double*)d->tail, (const double*)d->taps, dst, push, tile, d->layout, d->array, d->stap,
+                               dst_fmt, d->fcw, d->gain, dst_off, dst_cap);
+        else if (d->has_array)
             hipLaunchKernelGGL(ddc_array_kernel, dim3((unsigned)tiles), dim3(kDdcThreads), lds, e->stream, (const void*)e->ddc_stage.ptr,
                                (const void*)d->hist, (const double*)d->taps, dst, push, tile, d->layout, d->array, dst_fmt, d->fcw, d->gain, dst_off,
                                dst_cap);
@@ -231,7 +272,7 @@ static int ddc_push_impl(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in
     if (d->mit && push.n_out > 0)
         if (int rc = mit_push_finish(e, d->mit, push.m_first, push.n_out, off)) return rc;
     if (d->has_array) ddc_array_cov_launch(e, d, n_in);
-    if (d->T > 1) ddc_history_launch(e, d, n_in);
+    if (d->T > 1 || (d->has_stap && d->stap.T > 1)) ddc_history_launch(e, d, n_in);     // (a space-time converter's raw tail too)
     SDR_HIP(hipGetLastError());
     d->n_seen += n_in;
     if (wait) SDR_HIP(hipStreamSynchronize(e->stream));
@@ -325,6 +366,7 @@ void sdr_ddc_destroy(sdr_engine* e, sdr_ddc* d) {
     if (d->hist) (void)hipFree(d->hist);
     if (d->cov) (void)hipFree(d->cov);
     if (d->cov_slab.ptr) (void)hipFree(d->cov_slab.ptr);
+    if (d->tail) (void)hipFree(d->tail);
     mit_destroy(nullptr, d->mit);
     delete d;
 }
@@ -334,7 +376,8 @@ int sdr_ddc_reset(sdr_engine* e, sdr_ddc* d) {
     if (int rc = ddc_check(e, d)) return rc;
     const size_t hist_bytes = (size_t)(d->Tp > 1 ? d->Tp - 1 : 1) * ddc_hist_unit(d);
     SDR_HIP(hipMemsetAsync(d->hist, 0, hist_bytes, e->stream));
-    if (d->cov) SDR_HIP(hipMemsetAsync(d->cov, 0, kDdcArrayCovSlots * sizeof(int64_t), e->stream));     // (the weights stay)
+    if (d->cov) SDR_HIP(hipMemsetAsync(d->cov, 0, ddc_cov_bytes(d), e->stream));     // (the weights stay)
+    if (d->tail) SDR_HIP(hipMemsetAsync(d->tail, 0, ddc_stap_tail_bytes(d->stap.T, d->array.K), e->stream));
     d->cov_n = 0;
     if (d->mit)
         if (int rc = mit_reset(e, d->mit)) return rc;

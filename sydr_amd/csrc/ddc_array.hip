@@ -131,6 +131,7 @@ inline int64_t cov_workgroups(int64_t n_in) { return (n_in + kCovChunk - 1) / kC
 }  // namespace
 
 int sdr::ddc_array_cov_reserve(sdr_engine* e, sdr_ddc* d, int64_t n_in) {
+    if (d->has_stap) return ddc_stap_cov_reserve(e, d, n_in);
     if (!d->cov || n_in <= 0) return SDR_OK;
     const int64_t grid = cov_workgroups(n_in);
     if (grid > 0x7fffffff) return sdr_fail(SDR_ERR_RANGE, "%lld frames in one push of a measuring array", (long long)n_in);
@@ -139,6 +140,7 @@ int sdr::ddc_array_cov_reserve(sdr_engine* e, sdr_ddc* d, int64_t n_in) {
 }
 
 void sdr::ddc_array_cov_launch(sdr_engine* e, sdr_ddc* d, int64_t n_in) {
+    if (d->has_stap) return ddc_stap_cov_launch(e, d, n_in);
     if (!d->cov || n_in <= 0) return;
     ProfScope ps(e, "ddc_array_cov_kernel");
     const int mode = cov_mode(d->layout);
@@ -213,6 +215,7 @@ int sdr_ddc_array_weights(sdr_engine* e, sdr_ddc* d, const double* w) {
     if (int rc = sdr_set_device(e)) return rc;
     if (int rc = ddc_check(e, d)) return rc;
     if (!d->has_array) return sdr_fail(SDR_ERR_INVALID, "the converter has no array");
+    if (d->has_stap) return sdr_fail(SDR_ERR_INVALID, "a space-time converter takes sdr_ddc_stap_weights and sdr_ddc_stap_covariance");
     if (!w) return sdr_fail(SDR_ERR_INVALID, "weights is NULL");
     if (!ddc_array_weights_valid(d->array.K, w)) return sdr_fail(SDR_ERR_INVALID, "a weight is not finite");
     // the kernels take the weights by value with every launch: the pushes queued so far keep theirs, the next one has these
@@ -224,6 +227,7 @@ int sdr_ddc_array_covariance(sdr_engine* e, sdr_ddc* d, double* R, int64_t* n, i
     if (int rc = sdr_set_device(e)) return rc;
     if (int rc = ddc_check(e, d)) return rc;
     if (!d->has_array) return sdr_fail(SDR_ERR_INVALID, "the converter has no array");
+    if (d->has_stap) return sdr_fail(SDR_ERR_INVALID, "a space-time converter takes sdr_ddc_stap_weights and sdr_ddc_stap_covariance");
     if (!R || !n) return sdr_fail(SDR_ERR_INVALID, "no result block for the covariance or its count");
     if (!d->cov) return sdr_fail(SDR_ERR_STATE, "the converter was made without SDR_DDC_ARRAY_MEASURE");
     int64_t slots[kDdcArrayCovSlots];

@@ -5,6 +5,7 @@
 #include "engine_internal.h"
 #include "ddc_layout.h"
 #include "ddc_array.h"
+#include "ddc_stap.h"
 #include "mitigate.h"
 
 struct sdr_ddc {
@@ -32,7 +33,17 @@ struct sdr_ddc {
     void* cov = nullptr;
     int64_t cov_n = 0;
     DevBuf cov_slab;
+    // a converter made by sdr_ddc_create_stap (has_array too; array.w is not read): T taps per element, `tail` the device's raw
+    // tail of the last T - 1 decoded frames (ddc_stap.h) beside `hist`, and `cov` T lags of kDdcStapCovSlots slots each
+    bool has_stap = false;
+    sdr::DdcStap stap = {};
+    double* tail = nullptr;
 };
+
+// Bytes of the covariance slots of a measuring converter.
+inline size_t ddc_cov_bytes(const sdr_ddc* d) {
+    return d->has_stap ? (size_t)d->stap.T * sdr::kDdcStapCovSlots * sizeof(int64_t) : (size_t)sdr::kDdcArrayCovSlots * sizeof(int64_t);
+}
 
 inline size_t ddc_in_bytes(int in_fmt) {
     switch (in_fmt) {
@@ -87,6 +98,18 @@ struct DdcArrayLoad {
     __device__ __forceinline__ void history(const void* __restrict__ p, int64_t i, double* re, double* im) const { sdr::ddc_array_history_load(p, i, re, im); }
 };
 
+// ... or a space-time array's: T frames of K elements combined per input, earlier frames than the push's first out of the raw tail.
+struct DdcStapLoad {
+    sdr::DdcLayout lay;
+    sdr::DdcArray arr;
+    sdr::DdcStap stap;
+    const double* tail;
+    __device__ __forceinline__ void block(const void* __restrict__ p, int64_t i, double* re, double* im) const {
+        sdr::ddc_stap_load(p, tail, i, lay, arr, stap, re, im);
+    }
+    __device__ __forceinline__ void history(const void* __restrict__ p, int64_t i, double* re, double* im) const { sdr::ddc_array_history_load(p, i, re, im); }
+};
+
 __device__ __forceinline__ double ddc_clip_rint(double v, double lim) { return fmin(fmax(rint(v), -lim), lim); }
 
 inline int ddc_check(sdr_engine* e, const sdr_ddc* d) {
@@ -110,5 +133,9 @@ int rs_push_impl(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in, int64_
 // ddc_array_cov_reserve, before the push has changed anything, makes room for the float pass's rows (SDR_ERR_NOMEM otherwise).
 int ddc_array_cov_reserve(sdr_engine* e, sdr_ddc* d, int64_t n_in);
 void ddc_array_cov_launch(sdr_engine* e, sdr_ddc* d, int64_t n_in);
+// ddc_stap.hip: the same two for a converter of sdr_ddc_create_stap (ddc_array_cov_* hand over to them): a lag per grid row,
+// partners before the push's first frame out of the raw tail, under the scope "ddc_stap_cov_kernel".
+int ddc_stap_cov_reserve(sdr_engine* e, sdr_ddc* d, int64_t n_in);
+void ddc_stap_cov_launch(sdr_engine* e, sdr_ddc* d, int64_t n_in);
 
 }  // namespace sdr

@@ -23,7 +23,7 @@ using namespace sdr;
 // k ascending, product then sum (no contraction: the NumPy statement's own operations); then gain and the store in the ring's
 // format, a ci8 ring's bytes sign-flipped.
 // `load` reads an input as ddc.hip's kernels do: one of the four formats (resample_kernel), a layout's frames
-// (resample_layout_kernel) or an array's combined elements (resample_array_kernel).
+// (resample_layout_kernel), an array's combined elements (resample_array_kernel) or a space-time array's (resample_stap_kernel).
 template <class Load>
 __device__ __forceinline__ void resample_kernel_body(double2* z, const void* __restrict__ in, const void* __restrict__ hist,
                                                      const double* __restrict__ table, void* __restrict__ ring, const RsPush& push, int tile,
@@ -99,6 +99,16 @@ __global__ __launch_bounds__(kRsThreads) void resample_array_kernel(const void* 
     resample_kernel_body((double2*)rs_smem, in, hist, table, ring, push, tile, DdcArrayLoad{lay, arr}, out_fmt, fcw, gain, ring_offset, capacity);
 }
 
+__global__ __launch_bounds__(kRsThreads) void resample_stap_kernel(const void* __restrict__ in, const void* __restrict__ hist,
+                                                                   const double* __restrict__ tail, const double* __restrict__ table,
+                                                                   void* __restrict__ ring, RsPush push, int tile, DdcLayout lay, DdcArray arr,
+                                                                   DdcStap stap, int out_fmt, uint64_t fcw, double gain, int64_t ring_offset,
+                                                                   int64_t capacity) {
+    extern __shared__ __attribute__((aligned(16))) char rs_smem[];
+    resample_kernel_body((double2*)rs_smem, in, hist, table, ring, push, tile, DdcStapLoad{lay, arr, stap, tail}, out_fmt, fcw, gain, ring_offset,
+                         capacity);
+}
+
 namespace sdr {
 
 // sdr_ddc_push / _queue of a converter with L > 1: ddc.hip's push with the resampler's counts and kernels.
@@ -136,7 +146,11 @@ int rs_push_impl(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in, int64_
         const int64_t tiles = rs_tiles(push, tile);
         const size_t lds = (size_t)rs_tile_span_max(d->L, d->D, d->T, tile) * sizeof(double2);
         ProfScope ps(e, "resample_kernel");
-        if (d->has_array)
+        if (d->has_stap)
+            hipLaunchKernelGGL(resample_stap_kernel, dim3((unsigned)tiles), dim3(kRsThreads), lds, e->stream, (const void*)e->ddc_stage.ptr,
+                               (const void*)d->hist, (const double*)d->tail, (const double*)d->taps, dst, push, tile, d->layout, d->array, d->stap,
+                               dst_fmt, d->fcw, d->gain, dst_off, dst_cap);
+        else if (d->has_array)
             hipLaunchKernelGGL(resample_array_kernel, dim3((unsigned)tiles), dim3(kRsThreads), lds, e->stream, (const void*)e->ddc_stage.ptr,
                                (const void*)d->hist, (const double*)d->taps, dst, push, tile, d->layout, d->array, dst_fmt, d->fcw, d->gain, dst_off,
                                dst_cap);
@@ -150,7 +164,7 @@ int rs_push_impl(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in, int64_
     if (d->mit && push.n_out > 0)
         if (int rc = mit_push_finish(e, d->mit, push.m_first, push.n_out, off)) return rc;
     if (d->has_array) ddc_array_cov_launch(e, d, n_in);
-    if (push.Tp > 1) ddc_history_launch(e, d, n_in);     // (the last Tp - 1 raw inputs: the integer converter's splice and kernel)
+    if (push.Tp > 1 || (d->has_stap && d->stap.T > 1)) ddc_history_launch(e, d, n_in);     // (the last Tp - 1 raw inputs: the integer converter's splice and kernel)
     SDR_HIP(hipGetLastError());
     d->n_seen += n_in;
     if (wait) SDR_HIP(hipStreamSynchronize(e->stream));

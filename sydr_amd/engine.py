@@ -261,12 +261,21 @@ def array_struct(array) -> "_lib.DdcArray":
     return c
 
 
+def stap_array_struct(array) -> "_lib.DdcArray":
+    """sdr_ddc_array of a signal.stap.SpaceTimeGeometry: lanes and flags (its weights are not read)."""
+    c = _lib.DdcArray(int(array.n_elements), int(array.flags))
+    for a, lane in enumerate(array.lanes):
+        c.lanes[a] = lane
+    return c
+
+
 class _Ddc:
     """Handle of a device-resident down-converter (Engine.ddc_create)."""
-    __slots__ = ("handle", "in_fmt", "nfft", "layout", "n_elements")
+    __slots__ = ("handle", "in_fmt", "nfft", "layout", "n_elements", "n_taps")
 
-    def __init__(self, handle, in_fmt, layout=None, n_elements=0):
+    def __init__(self, handle, in_fmt, layout=None, n_elements=0, n_taps=0):
         self.handle, self.in_fmt = handle, in_fmt
+        self.n_taps = n_taps          # T of a converter made by sdr_ddc_create_stap, else 0
         self.n_elements = n_elements  # K of a converter made by sdr_ddc_create_array, else 0
         self.layout = layout          # signal.downconvert.InputLayout of a converter made by sdr_ddc_create_layout, else None
         self.nfft = 0                 # of the attached mitigator's excisor (Engine.ddc_mitigate)
@@ -408,7 +417,8 @@ class Engine:
     # ------------------------------------------------------------------ down-conversion into the ring (signal/downconvert.py)
     def ddc_create(self, cfg):
         """A device-resident down-converter (sdr_ddc_create; with cfg.interpolation != 1 sdr_ddc_create_rational; with
-        cfg.layout sdr_ddc_create_layout) of a signal.downconvert.DownConverterConfig -> its handle."""
+        cfg.layout sdr_ddc_create_layout; with cfg.array sdr_ddc_create_array, or, when the array has `taps` -- a
+        signal.stap.SpaceTimeGeometry --, sdr_ddc_create_stap) of a signal.downconvert.DownConverterConfig -> its handle."""
         taps = np.ascontiguousarray(cfg.taps, dtype=np.float64)
         c = _lib.DdcCfg(int(cfg.in_fmt), int(cfg.decimation), int(taps.size), 0, int(cfg.fcw), float(cfg.gain),
                         taps.ctypes.data_as(C.POINTER(C.c_double)))
@@ -416,6 +426,11 @@ class Engine:
         interpolation = int(cfg.interpolation)
         layout = getattr(cfg, "layout", None)
         array = getattr(cfg, "array", None)
+        if array is not None and hasattr(array, "taps"):     # space-time weights: T taps per element (signal/stap.py)
+            w = np.ascontiguousarray(np.stack([array.weights.real, array.weights.imag], axis=2))
+            check(self._lib.sdr_ddc_create_stap(self._h, C.byref(c), interpolation, C.byref(layout_struct(layout)), C.byref(stap_array_struct(array)),
+                                                int(array.taps), w.ctypes.data_as(C.POINTER(C.c_double)), C.byref(h)))
+            return _Ddc(h, int(cfg.in_fmt), layout, array.n_elements, int(array.taps))
         if array is not None:             # an antenna array: the K elements of the layout's frames combined (signal/array.py)
             check(self._lib.sdr_ddc_create_array(self._h, C.byref(c), interpolation, C.byref(layout_struct(layout)), C.byref(array_struct(array)),
                                                  C.byref(h)))
@@ -463,6 +478,21 @@ class Engine:
         R, n = np.zeros((K, K, 2)), C.c_int64(0)
         check(self._lib.sdr_ddc_array_covariance(self._h, ddc.handle, R.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n), int(bool(clear))))
         return R[..., 0] + 1j * R[..., 1], n.value
+
+    def ddc_stap_weights(self, ddc, weights):
+        """The [T][K] weights of a space-time converter from its next push on (sdr_ddc_stap_weights; ordered on the stream)."""
+        from .signal.stap import as_weights
+        w = as_weights(weights, ddc.n_taps or 1, ddc.n_elements or 1)
+        flat = np.ascontiguousarray(np.stack([w.real, w.imag], axis=2))
+        check(self._lib.sdr_ddc_stap_weights(self._h, ddc.handle, flat.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def ddc_stap_covariance(self, ddc, clear: bool = False):
+        """(C [T][K][K] complex128, n) of a space-time converter made with `measure` (sdr_ddc_stap_covariance; waits for the
+        stream)."""
+        T, K = max(ddc.n_taps, 1), max(ddc.n_elements, 1)
+        out, n = np.zeros((T, K, K, 2)), C.c_int64(0)
+        check(self._lib.sdr_ddc_stap_covariance(self._h, ddc.handle, out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n), int(bool(clear))))
+        return out[..., 0] + 1j * out[..., 1], n.value
 
     def ddc_push(self, ddc, raw: np.ndarray, ring_offset: int = 0) -> int:
         """Raw inputs (real: one integer each; complex: interleaved I,Q; a converter with a layout: the recording's bytes, whole

@@ -28,7 +28,10 @@ frame (array.py): `array_mode` is `fixed` (the default; `array_weights`, K re,im
 and `array_train_ms` (default 2) belong to the two adaptive modes, in which the receiver first pushes the recording's first
 `array_train_ms` milliseconds with unit weight on the reference element, reads the covariance, solves for the weights, sets
 them, resets the converter and begins the recording again from its first sample: the whole ring is made with one weight
-vector.  Mitigation keys beside array keys are refused.
+vector.  `array_taps` (T = 1..8, default 1: everything above as it is) gives every element a T-tap FIR (stap.py): `array_weights` is
+then T K pairs, tap by tap, an adaptive mode measures the lag covariance and solves on the K T x K T space-time matrix, and
+`array_reference_tap` (default (T - 1) // 2) is the tap at which the reference element (or the steering vector) passes -- the
+output is delayed by that many input samples (`ArrayPlan.delay`).  Mitigation keys beside array keys are refused.
 Such a recording may also ask for interference mitigation between the converter and the ring (mitigate.py; keys
 `blanking_factor` with `blanking_lead`, `blanking_hold`, and `excision_nfft` with `excision_margin_db`; `calibration_ms`):
 the blanker's level and the excisor's limits are measured once, on the host, over the converter's output of the recording's
@@ -49,7 +52,8 @@ from .packing import Packing, unpack
 
 
 LAYOUT_KEYS = ("sample_format", "frame_fields", "frame_lane", "swap_iq")
-ARRAY_KEYS = ("array_lanes", "array_mode", "array_weights", "array_steering", "array_reference", "array_loading", "array_train_ms")
+ARRAY_KEYS = ("array_lanes", "array_mode", "array_weights", "array_steering", "array_reference", "array_loading", "array_train_ms", "array_taps",
+              "array_reference_tap")
 MITIGATION_KEYS = ("blanking_factor", "blanking_lead", "blanking_hold", "excision_nfft", "excision_margin_db", "calibration_ms")
 
 
@@ -87,8 +91,14 @@ class ArrayPlan:
     """How the weights of a multi-antenna recording come about: `fixed` (those of the configuration) or, measured on the
     recording's first `train_ms` milliseconds, `power_inversion` / `mvdr` (array.py)."""
 
-    def __init__(self, mode: str, reference: int, loading: float, train_ms: int, steering=None):
+    def __init__(self, mode: str, reference: int, loading: float, train_ms: int, steering=None, taps: int = 1, reference_tap: int = 0):
         self.mode, self.reference, self.loading, self.train_ms, self.steering = mode, reference, loading, train_ms, steering
+        self.taps, self.reference_tap = taps, reference_tap          # `array_taps` > 1: space-time weights (stap.py)
+
+    @property
+    def delay(self) -> int:
+        """The reference tap's delay in INPUT samples -- common to all channels; reported, not compensated."""
+        return self.reference_tap if self.taps > 1 else 0
 
     @property
     def adaptive(self) -> bool:
@@ -97,6 +107,13 @@ class ArrayPlan:
     def solve(self, R, n):
         """The weights for the covariance R of n inputs."""
         from . import array as ar
+        if self.taps > 1:                 # R is the lag covariance C [T][K][K]; the weights are [T][K]
+            from . import stap
+            if self.mode == "power_inversion":
+                return stap.power_inversion(R, n, self.reference, self.reference_tap, self.loading)
+            if self.mode == "mvdr":
+                return stap.mvdr(R, n, self.steering, self.reference_tap, self.loading)
+            raise ValueError("fixed weights are not solved for")
         if self.mode == "power_inversion":
             return ar.power_inversion(R, n, self.reference, self.loading)
         if self.mode == "mvdr":
@@ -215,7 +232,8 @@ class RFSignal:
 
     def _array_keys(self, configuration):
         """The opt-in keys `array_lanes`, `array_mode`, `array_weights`, `array_steering`, `array_reference`, `array_loading`,
-        `array_train_ms` -> (array.ArrayGeometry, ArrayPlan), or (None, None) without `array_lanes`."""
+        `array_train_ms`, `array_taps`, `array_reference_tap` -> (array.ArrayGeometry -- with `array_taps` > 1 a
+        stap.SpaceTimeGeometry --, ArrayPlan), or (None, None) without `array_lanes`."""
         from . import array as ar
         if "array_lanes" not in configuration:
             for key in ARRAY_KEYS:
@@ -245,19 +263,35 @@ class RFSignal:
         train_ms = int(configuration["array_train_ms"]) if "array_train_ms" in configuration else 2
         if train_ms < 1:
             raise ValueError("array_train_ms is at least 1")
+        taps = int(configuration["array_taps"]) if "array_taps" in configuration else 1
+        if not 1 <= taps <= 8:
+            raise ValueError(f"array_taps {taps} outside 1..8")
+        reference_tap = int(configuration["array_reference_tap"]) if "array_reference_tap" in configuration else (taps - 1) // 2
+        if not 0 <= reference_tap < taps:
+            raise ValueError(f"array_reference_tap {reference_tap} outside 0..{taps - 1}")
         allowed = {"fixed": ("array_weights", "array_reference"), "power_inversion": ("array_reference", "array_loading", "array_train_ms"),
                    "mvdr": ("array_steering", "array_reference", "array_loading", "array_train_ms")}[mode]
-        for key in ARRAY_KEYS[2:]:
+        for key in ARRAY_KEYS[2:7]:
             if key in configuration and key not in allowed:
                 raise ValueError(f"`{key}` does not belong to array_mode {mode!r}")
         if mode == "mvdr" and "array_steering" not in configuration:
             raise ValueError("array_mode 'mvdr' needs `array_steering`")
         # (an adaptive mode trains with unit weight on the reference element and measures the covariance)
-        weights = pairs("array_weights", K) if "array_weights" in configuration else ar.unit_weights(K, reference)
+        weights = None
+        if taps == 1:
+            weights = pairs("array_weights", K) if "array_weights" in configuration else ar.unit_weights(K, reference)
         steering = pairs("array_steering", K) if mode == "mvdr" else None
-        geometry = ar.ArrayGeometry(lanes, weights, measure=mode != "fixed")
+        if taps > 1:                      # T taps per element: weights [T][K], unit weight on the reference element at the reference tap
+            from . import stap
+            if "array_weights" in configuration:
+                weights = pairs("array_weights", taps * K).reshape(taps, K)
+            else:
+                weights = stap.unit_weights(taps, K, reference, reference_tap)
+            geometry = stap.SpaceTimeGeometry(lanes, taps, weights, measure=mode != "fixed")
+        else:
+            geometry = ar.ArrayGeometry(lanes, weights, measure=mode != "fixed")
         geometry.check(self.layout)
-        return geometry, ArrayPlan(mode, reference, loading, train_ms, steering)
+        return geometry, ArrayPlan(mode, reference, loading, train_ms, steering, taps, reference_tap)
 
     def _layout_span(self, first: int, n_samples: int):
         """Frames [first, first + n_samples) of a recording with a layout as elements of the mapped file: whole bytes."""
