@@ -335,7 +335,8 @@ def ring_slice(ring: np.ndarray, start: int, n: int) -> np.ndarray:
 # BOC(1,1) code passed as its doubled half-chip sequence), `epochs_per_bit` = epochs per navigation symbol,
 # `dt` = the epoch duration the discriminators and filters are scaled with, `code_rate` = nominal chip rate of
 # `code`.  With the defaults every statement below is the reference's, operation for operation (pinned by
-# g6 / g6b / g6c bit for bit); the generalised arguments only replace the constants 1023, 20, 1e-3 and 1.023e6.
+# g6 / g6b / g6c bit for bit; KaplanLoop's downward branches, from seeded states, by g6d); the generalised arguments only
+# replace the constants 1023, 20, 1e-3 and 1.023e6.
 
 class BorreLoop:
     """runTracking of channel_l1ca_borre.py:333-451 (DLL NNEML + Costas PLL, Borre filters)."""

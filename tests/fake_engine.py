@@ -87,6 +87,68 @@ class OracleEngine:
         return out
 
 
+def loop_from_state(st, cfg, code):
+    """The oracle's closed-loop model (KaplanLoop / BorreLoop) continuing from one sdr_track_state / sdr_loop_cfg row:
+    -> (model, kaplan).  `code`: the +-1 chips of the channel's code slot."""
+    kaplan = int(cfg["loop_kind"]) == 1
+    m = object.__new__(orc.KaplanLoop if kaplan else orc.BorreLoop)
+    m.fs = float(cfg["fs"])
+    m.code = orc.pad_code(np.asarray(code, dtype=np.float64))
+    m.dll_tau1, m.dll_tau2, m.dll_pdi = float(cfg["dll_tau1"]), float(cfg["dll_tau2"]), float(cfg["dll_pdi"])
+    m.carrier_hz, m.code_hz = float(st["carrier_hz"]), float(st["code_hz"])
+    m.rem_carrier, m.rem_code, m.code_step = float(st["rem_carrier"]), float(st["rem_code"]), float(st["code_step"])
+    m.n, m.current_sample = int(st["n_samples"]), int(st["current_sample"])
+    m.flags, m.code_counter = int(st["track_flags"]), int(st["code_counter"])
+    m.nav_sum, m.nav_count, m.nav_bits = float(st["nav_prompt_sum"]), int(st["nav_sum_counter"]), []
+    nt = int(cfg["n_taps"])
+    m.prompt = nt // 2
+    m.epoch_chips = float(cfg["epoch_chips"]) if float(cfg["epoch_chips"]) > 0 else orc.CODE_CHIPS   # 0: the reference's
+    m.epochs_per_bit = int(cfg["epochs_per_bit"]) if int(cfg["epochs_per_bit"]) > 0 else orc.MS_PER_BIT
+    if kaplan:
+        m.dt = float(cfg["epoch_seconds"]) if float(cfg["epoch_seconds"]) > 0 else 1e-3
+        m.sp_wide, m.sp_narrow = list(cfg["spacing_wide"][:nt]), list(cfg["spacing_narrow"][:nt])
+        m.spacing = m.sp_narrow if int(st["spacing_sel"]) else m.sp_wide
+        m.cfg = dict(fll_threshold_narrow=cfg["fll_thr_narrow"], pll_threshold_narrow=cfg["pll_thr_narrow"],
+                     fll_threshold_wide=cfg["fll_thr_wide"], pll_threshold_wide=cfg["pll_thr_wide"],
+                     fll_bandwidth_narrow=cfg["fll_bw_narrow"], pll_bandwidth_narrow=cfg["pll_bw_narrow"],
+                     fll_bandwidth_wide=cfg["fll_bw_wide"], pll_bandwidth_wide=cfg["pll_bw_wide"],
+                     fll_bandwidth_pullin=cfg["fll_bw_pullin"])
+        m.cfg = {k: float(v) for k, v in m.cfg.items()}
+        m.dll_thr = float(cfg["dll_threshold"])
+        m.corr, m.accum_counter = [0.0] * (2 * nt), int(st["accum_counter"])
+        m.ip_prev, m.qp_prev = float(st["i_prompt_prev"]), float(st["q_prompt_prev"])
+        m.cn0_ratio, m.cn0 = float(st["cn0_ratio_acc"]), float(st["cn0"])
+        m.dll, m.pll, m.fll = float(st["dll_mem"]), 0.0, 0.0
+        m.fll_bw, m.pll_bw = float(st["fll_bw"]), float(st["pll_bw"])
+        m.dll_lock, m.fll_lock, m.pll_lock = float(st["cn0"]), float(st["fll_lock"]), float(st["pll_lock"])
+        m.vel_mem, m.time_in_state, m.lock_state = float(st["pll_mem"]), int(st["time_in_state"]), int(st["lock_state"])
+    else:
+        m.spacing = list(cfg["spacing_wide"][:nt])
+        m.pll_tau1, m.pll_tau2, m.pll_pdi = float(cfg["pll_tau1"]), float(cfg["pll_tau2"]), float(cfg["pll_pdi"])
+        m.code_err_mem, m.carrier_err_mem = float(st["dll_mem"]), float(st["pll_mem"])
+        m.ip_prev = float(st["i_prompt_prev"])
+    return m, kaplan
+
+
+def state_from_loop(m, kaplan, st, qp):
+    """The model's attributes written back into the sdr_track_state row `st` (qp: the last quadrature prompt, which the
+    Borre model does not keep)."""
+    st["carrier_hz"], st["code_hz"] = m.carrier_hz, m.code_hz
+    st["rem_carrier"], st["rem_code"], st["code_step"] = m.rem_carrier, m.rem_code, m.code_step
+    st["n_samples"], st["current_sample"] = m.n, m.current_sample
+    st["track_flags"], st["code_counter"] = m.flags, m.code_counter
+    st["nav_prompt_sum"], st["nav_sum_counter"] = m.nav_sum, m.nav_count
+    st["nav_bits_emitted"] += len(m.nav_bits)
+    if kaplan:
+        st["spacing_sel"] = 1 if m.spacing is m.sp_narrow else 0
+        st["accum_counter"], st["i_prompt_prev"], st["q_prompt_prev"] = m.accum_counter, m.ip_prev, m.qp_prev
+        st["cn0_ratio_acc"], st["cn0"], st["dll_mem"] = m.cn0_ratio, m.cn0, m.dll
+        st["fll_bw"], st["pll_bw"], st["fll_lock"], st["pll_lock"] = m.fll_bw, m.pll_bw, m.fll_lock, m.pll_lock
+        st["pll_mem"], st["time_in_state"], st["lock_state"] = m.vel_mem, m.time_in_state, m.lock_state
+    else:
+        st["dll_mem"], st["pll_mem"], st["i_prompt_prev"], st["q_prompt_prev"] = m.code_err_mem, m.carrier_err_mem, m.ip_prev, qp
+
+
 class OracleBank:
     """sydr_amd.engine.Bank on the oracle's closed-loop channel models (oracle.KaplanLoop / BorreLoop): every step
     rebuilds the model from the sdr_track_state / sdr_loop_cfg rows, runs it, and writes the rows back."""
@@ -107,61 +169,9 @@ class OracleBank:
         pass
 
     def _model(self, st, cfg):
-        kaplan = int(cfg["loop_kind"]) == 1
-        m = object.__new__(orc.KaplanLoop if kaplan else orc.BorreLoop)
-        m.fs = float(cfg["fs"])
-        m.code = orc.pad_code(self.e.codes[int(st["code_slot"])])
-        m.dll_tau1, m.dll_tau2, m.dll_pdi = float(cfg["dll_tau1"]), float(cfg["dll_tau2"]), float(cfg["dll_pdi"])
-        m.carrier_hz, m.code_hz = float(st["carrier_hz"]), float(st["code_hz"])
-        m.rem_carrier, m.rem_code, m.code_step = float(st["rem_carrier"]), float(st["rem_code"]), float(st["code_step"])
-        m.n, m.current_sample = int(st["n_samples"]), int(st["current_sample"])
-        m.flags, m.code_counter = int(st["track_flags"]), int(st["code_counter"])
-        m.nav_sum, m.nav_count, m.nav_bits = float(st["nav_prompt_sum"]), int(st["nav_sum_counter"]), []
-        nt = int(cfg["n_taps"])
-        m.prompt = nt // 2
-        m.epoch_chips = float(cfg["epoch_chips"]) if float(cfg["epoch_chips"]) > 0 else orc.CODE_CHIPS   # 0: the reference's
-        m.epochs_per_bit = int(cfg["epochs_per_bit"]) if int(cfg["epochs_per_bit"]) > 0 else orc.MS_PER_BIT
-        if kaplan:
-            m.dt = float(cfg["epoch_seconds"]) if float(cfg["epoch_seconds"]) > 0 else 1e-3
-            m.sp_wide, m.sp_narrow = list(cfg["spacing_wide"][:nt]), list(cfg["spacing_narrow"][:nt])
-            m.spacing = m.sp_narrow if int(st["spacing_sel"]) else m.sp_wide
-            m.cfg = dict(fll_threshold_narrow=cfg["fll_thr_narrow"], pll_threshold_narrow=cfg["pll_thr_narrow"],
-                         fll_threshold_wide=cfg["fll_thr_wide"], pll_threshold_wide=cfg["pll_thr_wide"],
-                         fll_bandwidth_narrow=cfg["fll_bw_narrow"], pll_bandwidth_narrow=cfg["pll_bw_narrow"],
-                         fll_bandwidth_wide=cfg["fll_bw_wide"], pll_bandwidth_wide=cfg["pll_bw_wide"],
-                         fll_bandwidth_pullin=cfg["fll_bw_pullin"])
-            m.cfg = {k: float(v) for k, v in m.cfg.items()}
-            m.dll_thr = float(cfg["dll_threshold"])
-            m.corr, m.accum_counter = [0.0] * (2 * nt), int(st["accum_counter"])
-            m.ip_prev, m.qp_prev = float(st["i_prompt_prev"]), float(st["q_prompt_prev"])
-            m.cn0_ratio, m.cn0 = float(st["cn0_ratio_acc"]), float(st["cn0"])
-            m.dll, m.pll, m.fll = float(st["dll_mem"]), 0.0, 0.0
-            m.fll_bw, m.pll_bw = float(st["fll_bw"]), float(st["pll_bw"])
-            m.dll_lock, m.fll_lock, m.pll_lock = float(st["cn0"]), float(st["fll_lock"]), float(st["pll_lock"])
-            m.vel_mem, m.time_in_state, m.lock_state = float(st["pll_mem"]), int(st["time_in_state"]), int(st["lock_state"])
-        else:
-            m.spacing = list(cfg["spacing_wide"][:nt])
-            m.pll_tau1, m.pll_tau2, m.pll_pdi = float(cfg["pll_tau1"]), float(cfg["pll_tau2"]), float(cfg["pll_pdi"])
-            m.code_err_mem, m.carrier_err_mem = float(st["dll_mem"]), float(st["pll_mem"])
-            m.ip_prev = float(st["i_prompt_prev"])
-        return m, kaplan
+        return loop_from_state(st, cfg, self.e.codes[int(st["code_slot"])])
 
-    @staticmethod
-    def _store(m, kaplan, st, qp):
-        st["carrier_hz"], st["code_hz"] = m.carrier_hz, m.code_hz
-        st["rem_carrier"], st["rem_code"], st["code_step"] = m.rem_carrier, m.rem_code, m.code_step
-        st["n_samples"], st["current_sample"] = m.n, m.current_sample
-        st["track_flags"], st["code_counter"] = m.flags, m.code_counter
-        st["nav_prompt_sum"], st["nav_sum_counter"] = m.nav_sum, m.nav_count
-        st["nav_bits_emitted"] += len(m.nav_bits)
-        if kaplan:
-            st["spacing_sel"] = 1 if m.spacing is m.sp_narrow else 0
-            st["accum_counter"], st["i_prompt_prev"], st["q_prompt_prev"] = m.accum_counter, m.ip_prev, m.qp_prev
-            st["cn0_ratio_acc"], st["cn0"], st["dll_mem"] = m.cn0_ratio, m.cn0, m.dll
-            st["fll_bw"], st["pll_bw"], st["fll_lock"], st["pll_lock"] = m.fll_bw, m.pll_bw, m.fll_lock, m.pll_lock
-            st["pll_mem"], st["time_in_state"], st["lock_state"] = m.vel_mem, m.time_in_state, m.lock_state
-        else:
-            st["dll_mem"], st["pll_mem"], st["i_prompt_prev"], st["q_prompt_prev"] = m.code_err_mem, m.carrier_err_mem, m.ip_prev, qp
+    _store = staticmethod(state_from_loop)
 
     def step(self, channels, n_epochs=1, want_records=True, want_bits=False, stream=0, epochs_per_bit=20):
         self.calls["step"] += 1

@@ -331,6 +331,91 @@ def make_trajectories(fname="g6_trajectories.npz", ms=510, amp=8.0, sigma=20.0, 
     save(fname, **out)
 
 
+# ---------------------------------------------------------------------------------------------- G6d
+# sdr_track_state field -> the attribute(s) of the reference's Kaplan plugin that hold it (the tap selector and the two
+# enumerations are set separately)
+_SEED_ATTRS = dict(fll_lock=("fllLockIndicator",), pll_lock=("pllLockIndicator",), cn0=("cn0", "dllLockIndicator"),
+                   fll_bw=("fllBandwidth",), pll_bw=("pllBandwidth",), code_counter=("codeCounter",),
+                   i_prompt_prev=("iPromptPrev",), q_prompt_prev=("qPromptPrev",), dll_mem=("dllDiscrim",),
+                   pll_mem=("fll_vel_memory",), accum_counter=("correlatorsAccumCounter",),
+                   cn0_ratio_acc=("cn0_PdPnRatio",), time_in_state=("timeSinceLastState",),
+                   nav_sum_counter=("navPromptSumCounter",), nav_prompt_sum=("navPromptSum",))
+
+
+def make_lock_edges(fname="g6d_kaplan_edges.npz"):
+    """The reference's Kaplan plugin from the seeded starts of tests/lock_edge_cases.py (cases A-G, 4 MHz, one stream):
+    the plugin acquires as usual; before its first tracking epoch its loop attributes are overwritten with the case's
+    seeded state, and then it runs on its own.  The same 25 columns as g6b per case; the IQ is not stored (seed + sha256)."""
+    from sydr.channel.channel_l1ca_kaplan import ChannelL1CA_Kaplan as RefKaplan
+    from sydr.utils.enumerations import LoopLockState
+    sys.path.insert(0, os.path.dirname(HERE))
+    import lock_edge_cases as lec
+
+    fs, sat = lec.FS_CPU, lec.SAT
+    spms = int(fs * 1e-3)
+    n = lec.stream_samples(fs)
+    raw = orc.synth_iq(fs, n, [sat], lec.SIGMA, lec.SEED)
+    rf = raw[0::2] + 1j * raw[1::2]
+    over = {"ACQUISITION": dict(doppler_steps=250, coherent_integration=1, non_coherent_integration=1),
+            "TRACKING": lec.OVERRIDES}
+    out = dict(iq_sha256=iq_hash(raw),
+               synth=np.array([fs, n, sat["prn"], sat["doppler"], sat["code_phase"], sat["phase"], sat["amp"], lec.SIGMA,
+                               lec.SEED]),
+               track_override_keys=np.array(sorted(lec.OVERRIDES)),
+               track_override_vals=np.array([float(lec.OVERRIDES[k]) for k in sorted(lec.OVERRIDES)]),
+               cases=np.array(lec.GOLDEN_CASES), seed_fields=np.array(sorted(_SEED_ATTRS) + ["lock_state", "track_flags",
+                                                                                             "spacing_sel"]))
+    for name in lec.GOLDEN_CASES:
+        cfg = _channel_config(os.path.join(REF, "config/channels/channel_GPS_L1CA_kaplan.ini"), over)
+        rfs = RFSignal(dict(filepath="none", sampling_frequency=fs, is_complex="true", intermediate_frequency=0.0,
+                            data_size=8))
+        buf = CircularBuffer(100 * spms, complex)
+        ch = RefKaplan(0, buf, None, rfs, cfg)
+        ch.setSatellite(sat["prn"])
+        acq, epochs, seeded = None, [], False
+        for k in range(n // spms):
+            buf.shift(rf[k * spms:(k + 1) * spms])
+            pre = None
+            if ch.channelState == ChannelState.TRACKING:
+                if not seeded:
+                    st = lec.seeded_state(name, fs, ch.carrierFrequency, ch.currentSample)
+                    assert st.n_samples == ch.track_requiredSamples and st.code_step == ch.codeStep
+                    if lec.CASES[name].seed is not None:
+                        for field, attrs in _SEED_ATTRS.items():
+                            for a in attrs:
+                                assert hasattr(ch, a), a
+                                setattr(ch, a, getattr(st, field))
+                        ch.loopLockState = LoopLockState(st.lock_state)
+                        ch.trackFlags = int(st.track_flags)       # (an IntEnum or-ed with itself is a plain int in the plugin too)
+                        ch.track_correlatorsSpacing = ch.dll_epl_narrow if st.spacing_sel else ch.dll_epl_wide
+                    out[f"{name}_seed"] = np.array([float(getattr(st, f)) for f in out["seed_fields"]])
+                    seeded = True
+                pre = [ch.currentSample, ch.track_requiredSamples, ch.carrierFrequency, ch.remainingCarrier,
+                       ch.remainingCode, ch.codeStep]
+            bits_before = ch.navBitsCounter
+            results = ch._processHandler()
+            nav_bit = float(ch.navBitsBuffer[ch.navBitsCounter - 1]) if ch.navBitsCounter == bits_before + 1 else -1.0
+            for r in results:
+                if "correlation_map" in r:
+                    acq = [r["frequency_idx"], r["code_idx"], r["peak_ratio"], r["carrierFrequency"], r["codeOffset"],
+                           ch.currentSample, ch.track_requiredSamples]
+                elif "i_prompt" in r:
+                    epochs.append(pre + [r["i_early"], r["q_early"], r["i_prompt"], r["q_prompt"], r["i_late"],
+                                         r["q_late"], r["dll"], r["pll"], r["fll"], r["carrier_frequency"],
+                                         r["code_frequency"], r["carrier_frequency_error"],
+                                         r["code_frequency_error"], r["cn0"], r["pll_lock"], r["fll_lock"],
+                                         float(int(r["lock_state"])), float(int(ch.trackFlags)), nav_bit])
+        out[f"{name}_acq"] = np.array(acq, dtype=np.float64)
+        out[f"{name}_epochs"] = np.array(epochs[:lec.EPOCHS], dtype=np.float64)
+        assert len(epochs) >= lec.EPOCHS
+        print(name, "acq", acq, "epochs", len(epochs), "lock states", sorted({int(e[22]) for e in epochs}))
+    out["epoch_columns"] = np.array(["currentSample", "n", "carrier_in", "rem_carrier_in", "rem_code_in",
+                                     "code_step_in", "ie", "qe", "ip", "qp", "il", "ql", "dll", "pll", "fll",
+                                     "carrier_hz", "code_hz", "carrier_err", "code_err", "cn0", "pll_lock",
+                                     "fll_lock", "lock_state", "flags", "nav_bit"])
+    save(fname, **out)
+
+
 # ---------------------------------------------------------------------------------------------- G10
 def make_decoding(fname="g10_decoding.npz", seconds=20.6, lead_bits=30, fs=4e6):
     """The Kaplan plugin over a stream that carries valid LNAV subframes (oracle/lnav.py encodes them): the
@@ -488,7 +573,7 @@ def make_loopmath():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["codes", "pcps", "peaks", "epl", "ref_c", "traj", "loop", "serial", "decoding"]
+    which = sys.argv[1:] or ["codes", "pcps", "peaks", "epl", "ref_c", "traj", "edges", "loop", "serial", "decoding"]
     if "serial" in which:
         make_serial()
     if "codes" in which:
@@ -510,6 +595,8 @@ if __name__ == "__main__":
         # the headline sampling rate (BASELINE configs 2-3): both plugins at 25 MHz, PCPS + ~300 epochs.  The IQ
         # (15 MB) is not stored: seed + sha256, regenerated by the tests
         make_trajectories("g6c_25mhz.npz", ms=310, amp=8.0, sigma=20.0, seed=20260625, fs=25e6)
+    if "edges" in which:
+        make_lock_edges()
     if "loop" in which:
         make_loopmath()
     if "decoding" in which:

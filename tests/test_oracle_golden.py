@@ -266,6 +266,49 @@ def test_closed_loop_kaplan_lock_state_machine():
     assert loop.nav_bits == [int(b) for b in ref[ref[:, 24] >= 0, 24]] and len(loop.nav_bits) >= 40
 
 
+def test_closed_loop_kaplan_every_lock_edge():
+    """The seeded starts of tests/lock_edge_cases.py (cases A-G) in the reference's own plugin (g6d): the downward edges
+    3>2, 3>1, 2>1, the direct 1>3, a fallen-back PULL_IN, CODE_LOCK cleared with bits still coming -- branches of
+    KaplanLoop that no healthy trajectory takes.  The oracle from the same seeded state, bit for bit."""
+    import lock_edge_cases as lec
+    g = load_golden("g6d_kaplan_edges.npz")
+    raw, stream, (carrier, cur) = lec.cpu_scene()
+    assert np.array_equal(np.frombuffer(hashlib.sha256(raw.tobytes()).digest(), dtype=np.uint8), g["iq_sha256"])
+    assert {str(k): float(v) for k, v in zip(g["track_override_keys"], g["track_override_vals"])} == lec.OVERRIDES
+    assert tuple(str(c) for c in g["cases"]) == lec.GOLDEN_CASES
+    ring = 100 * int(lec.FS_CPU * 1e-3)
+    edges = set()
+    for name in lec.GOLDEN_CASES:
+        acq, ref = g[f"{name}_acq"], g[f"{name}_epochs"]
+        assert (carrier, cur) == (acq[3], int(acq[5]))
+        state, recs, aux, end, bits = lec.cpu_run(name)
+        # the golden run started from the state the case module builds today
+        assert [float(getattr(state, str(f))) for f in g["seed_fields"]] == list(g[f"{name}_seed"]), name
+        assert len(ref) == len(recs) == lec.EPOCHS
+        for k, (row, rec) in enumerate(zip(ref, recs)):
+            assert (rec["start"] % ring, rec["n"]) == (int(row[0]), int(row[1])), (name, k)
+            assert (rec["carrier_hz_in"], rec["rem_carrier_in"], rec["rem_code_in"], rec["code_step_in"]) == tuple(row[2:6]), (name, k)
+            assert rec["corr"] == list(row[6:12]), (name, k)
+            assert (rec["dll"], rec["pll"], rec["fll"], rec["carrier_hz"], rec["code_hz"], rec["carrier_err"], rec["code_err"]) \
+                == tuple(row[12:19]), (name, k)
+            np.testing.assert_equal([rec["cn0"], rec["pll_lock"], rec["fll_lock"]], row[19:22])
+            assert (rec["lock_state"], rec["flags"], rec["nav_bit"]) == (int(row[22]), int(row[23]), int(row[24])), (name, k)
+        assert list(bits) == [int(b) for b in ref[ref[:, 24] >= 0, 24]]
+        edges |= lec.observed_edges(state, recs, aux)
+    assert lec.ALL_EDGES <= edges           # (H, the Borre case, adds none of its own)
+
+
+def test_lock_edge_cases_keep_their_conditions():
+    """tests/lock_edge_cases.py's own checks, as part of the suite: every case shows the edges it is there for, all
+    together show every edge, and the seeds in use pass the 1e-13 perturbation check."""
+    import lock_edge_cases as lec
+    for name in lec.CASES:
+        lec.test_each_case_shows_its_edges(name)
+        lec.test_seeds_pass_the_perturbation_check(name)
+        lec.test_decisions_keep_clear_of_their_thresholds(name)
+    lec.test_all_edges_are_covered()
+
+
 @pytest.mark.parametrize("plugin", ["borre", "kaplan_strong"])
 def test_generalised_loop_reduces_to_the_reference(plugin):
     """Configs 4-5 run 5 taps / multi-period epochs / BOC through the loops' generalised arguments (no reference
