@@ -1,5 +1,5 @@
 // Antenna arrays in the down-converter (sdr_ddc_create_array, sdr_ddc_array_weights, sdr_ddc_array_covariance): the K elements of
-// a multi-element recording are combined, x = w^H s, where ddc_kernel / resample_kernel load their inputs (DdcArrayLoad,
+// a multi-element recording are combined, x = w^H s, where ddc.hip's converter kernel loads its inputs (DdcArrayLoad,
 // ddc_handle.h; the arithmetic is ddc_array.h) -- before the mixer, the FIR, the mitigator and the ring, so nothing downstream
 // changes and a packed array recording stays packed over the link and in HBM.  This file holds the handle's new entry points
 // and the opt-in covariance pass; what both must give is stated in include/sydr_amd.h and, as NumPy, in
@@ -18,7 +18,7 @@
 // atomics: a workgroup stores its 64 sums as a row of a slab and ddc_array_cov_finish_kernel adds the rows in ascending order
 // onto the running sums -- the same pushes give the same bits.
 #include "engine_internal.h"
-#include "ddc_handle.h"
+#include "ddc_cov.h"
 
 #include <cmath>
 #include <new>
@@ -27,35 +27,11 @@ using namespace sdr;
 
 namespace {
 
-constexpr int kCovThreads = 256, kCovWaves = kCovThreads / 64, kCovRun = 64;
-constexpr int64_t kCovChunk = (int64_t)kCovThreads * kCovRun;     // frames of a workgroup
-constexpr int kCovNarrow = 0, kCovWide = 1, kCovFloat = 2;
-
-template <int MODE>
-struct CovAcc {
-    typedef int type;
-};
-template <>
-struct CovAcc<kCovWide> {
-    typedef long long type;
-};
-template <>
-struct CovAcc<kCovFloat> {
-    typedef double type;
-};
-
-template <class T>
-__device__ __forceinline__ T cov_wave_add(T v) {     // a fixed butterfly: the same bits every time
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
 // `out`: the 64 running sums (integer modes: added to atomically) or the slab [workgroups][64] (float: row blockIdx.x stored).
 template <int K, int MODE>
 __global__ __launch_bounds__(kCovThreads) void ddc_array_cov_kernel(const void* __restrict__ in, int64_t n_in, DdcLayout lay, DdcArray arr,
                                                                     void* __restrict__ out) {
-    typedef typename CovAcc<MODE>::type Acc;
+    typedef typename CovTypes<MODE>::acc Acc;
     __shared__ Acc part[kCovWaves][kDdcArrayCovSlots];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     Acc acc[K * K];     // (a, b), a <= b: the real part at a * K + b, the imaginary part (a < b) at b * K + a
@@ -113,48 +89,18 @@ __global__ __launch_bounds__(kDdcArrayCovSlots) void ddc_array_cov_finish_kernel
     cov[c] = t;
 }
 
-int cov_mode(const DdcLayout& l) { return l.kind == kDdcFieldFloat32 ? kCovFloat : l.kind == kDdcFieldInt16 ? kCovWide : kCovNarrow; }
-
-template <int K>
-void cov_launch_k(sdr_engine* e, sdr_ddc* d, int64_t n_in, unsigned grid, int mode, void* out) {
-    const void* in = (const void*)e->ddc_stage.ptr;
-    if (mode == kCovFloat)
-        hipLaunchKernelGGL((ddc_array_cov_kernel<K, kCovFloat>), dim3(grid), dim3(kCovThreads), 0, e->stream, in, n_in, d->layout, d->array, out);
-    else if (mode == kCovWide)
-        hipLaunchKernelGGL((ddc_array_cov_kernel<K, kCovWide>), dim3(grid), dim3(kCovThreads), 0, e->stream, in, n_in, d->layout, d->array, out);
-    else
-        hipLaunchKernelGGL((ddc_array_cov_kernel<K, kCovNarrow>), dim3(grid), dim3(kCovThreads), 0, e->stream, in, n_in, d->layout, d->array, out);
-}
-
-inline int64_t cov_workgroups(int64_t n_in) { return (n_in + kCovChunk - 1) / kCovChunk; }
-
 }  // namespace
 
-int sdr::ddc_array_cov_reserve(sdr_engine* e, sdr_ddc* d, int64_t n_in) {
-    if (d->has_stap) return ddc_stap_cov_reserve(e, d, n_in);
-    if (!d->cov || n_in <= 0) return SDR_OK;
-    const int64_t grid = cov_workgroups(n_in);
-    if (grid > 0x7fffffff) return sdr_fail(SDR_ERR_RANGE, "%lld frames in one push of a measuring array", (long long)n_in);
-    if (cov_mode(d->layout) != kCovFloat) return SDR_OK;
-    return sdr_devbuf_reserve(e, &d->cov_slab, (size_t)grid * kDdcArrayCovSlots * sizeof(double));
-}
-
 void sdr::ddc_array_cov_launch(sdr_engine* e, sdr_ddc* d, int64_t n_in) {
-    if (d->has_stap) return ddc_stap_cov_launch(e, d, n_in);
-    if (!d->cov || n_in <= 0) return;
     ProfScope ps(e, "ddc_array_cov_kernel");
     const int mode = cov_mode(d->layout);
     const unsigned grid = (unsigned)cov_workgroups(n_in);
+    const void* in = (const void*)e->ddc_stage.ptr;
     void* out = mode == kCovFloat ? d->cov_slab.ptr : d->cov;
-    switch (d->array.K) {
-        case 2: cov_launch_k<2>(e, d, n_in, grid, mode, out); break;
-        case 3: cov_launch_k<3>(e, d, n_in, grid, mode, out); break;
-        case 4: cov_launch_k<4>(e, d, n_in, grid, mode, out); break;
-        case 5: cov_launch_k<5>(e, d, n_in, grid, mode, out); break;
-        case 6: cov_launch_k<6>(e, d, n_in, grid, mode, out); break;
-        case 7: cov_launch_k<7>(e, d, n_in, grid, mode, out); break;
-        default: cov_launch_k<8>(e, d, n_in, grid, mode, out); break;
-    }
+    cov_dispatch(d->array.K, mode, [&](auto k, auto m) {
+        hipLaunchKernelGGL((ddc_array_cov_kernel<decltype(k)::value, decltype(m)::value>), dim3(grid), dim3(kCovThreads), 0, e->stream, in, n_in,
+                           d->layout, d->array, out);
+    });
     if (mode == kCovFloat)
         hipLaunchKernelGGL(ddc_array_cov_finish_kernel, dim3(1), dim3(kDdcArrayCovSlots), 0, e->stream, (const double*)d->cov_slab.ptr, (int64_t)grid,
                            (double*)d->cov);
@@ -165,57 +111,14 @@ extern "C" {
 
 int sdr_ddc_create_array(sdr_engine* e, const sdr_ddc_cfg* cfg, int interpolation, const sdr_ddc_layout* layout, const sdr_ddc_array* array,
                          sdr_ddc** out) {
-    if (int rc = sdr_set_device(e)) return rc;
-    if (!cfg || !out) return sdr_fail(SDR_ERR_INVALID, "NULL configuration or result pointer");
-    *out = nullptr;
-    if (!layout || !array) return sdr_fail(SDR_ERR_INVALID, "NULL layout or array");
-    // the frame is the layout's; its own lane is not read (every element brings one)
-    if (!ddc_layout_valid(layout->field, layout->bits, layout->stride, 0, layout->flags, layout->reserved))
-        return sdr_fail(SDR_ERR_INVALID, "the input layout is outside its limits");
-    DdcLayout lay = ddc_layout_make(layout->field, layout->bits, layout->stride, 0, layout->flags, layout->levels);
-    if (!ddc_array_lanes_valid(lay, array->n_elements, array->flags, array->lanes))
-        return sdr_fail(SDR_ERR_INVALID, "%d elements outside %d..%d, unknown flags 0x%x, or a repeated or out-of-frame lane", array->n_elements,
-                        kDdcArrayMin, kDdcArrayMax, array->flags);
-    if (!ddc_array_weights_valid(array->n_elements, &array->weights[0][0])) return sdr_fail(SDR_ERR_INVALID, "a weight is not finite");
-    // the converter itself is sdr_ddc_create_layout's, every check of cfg included; its history then holds combined inputs
-    sdr_ddc_layout plain = *layout;
-    plain.lane = 0;
-    sdr_ddc* d = nullptr;
-    if (int rc = sdr_ddc_create_layout(e, cfg, interpolation, &plain, &d)) return rc;
-    const size_t hist_bytes = (size_t)(d->Tp > 1 ? d->Tp - 1 : 1) * kDdcArrayHistoryUnit;
-    void* hist = nullptr;
-    void* cov = nullptr;
-    hipError_t err = hipMalloc(&hist, hist_bytes);
-    if (err == hipSuccess) err = hipMemsetAsync(hist, 0, hist_bytes, e->stream);
-    if (err == hipSuccess && (array->flags & kDdcArrayMeasure)) {
-        err = hipMalloc(&cov, kDdcArrayCovSlots * sizeof(int64_t));
-        if (err == hipSuccess) err = hipMemsetAsync(cov, 0, kDdcArrayCovSlots * sizeof(int64_t), e->stream);
-    }
-    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-    if (err != hipSuccess) {
-        if (hist) (void)hipFree(hist);
-        if (cov) (void)hipFree(cov);
-        sdr_ddc_destroy(e, d);
-        return sdr_fail(SDR_ERR_HIP, "sdr_ddc_create_array: %s", hipGetErrorString(err));
-    }
-    (void)hipFree(d->hist);
-    d->hist = hist, d->cov = cov;
-    d->has_array = true;
-    d->array.K = array->n_elements, d->array.flags = array->flags;
-    for (int a = 0; a < kDdcArrayMax; ++a) {
-        const bool in = a < d->array.K;
-        d->array.lanes[a] = in ? array->lanes[a] : 0;
-        d->array.w[a][0] = in ? array->weights[a][0] : 0.0, d->array.w[a][1] = in ? array->weights[a][1] : 0.0;
-    }
-    *out = d;
-    return SDR_OK;
+    return ddc_create(e, kDdcKindArray, cfg, interpolation, layout, array, 0, nullptr, out);
 }
 
 int sdr_ddc_array_weights(sdr_engine* e, sdr_ddc* d, const double* w) {
     if (int rc = sdr_set_device(e)) return rc;
     if (int rc = ddc_check(e, d)) return rc;
-    if (!d->has_array) return sdr_fail(SDR_ERR_INVALID, "the converter has no array");
-    if (d->has_stap) return sdr_fail(SDR_ERR_INVALID, "a space-time converter takes sdr_ddc_stap_weights and sdr_ddc_stap_covariance");
+    if (d->kind < kDdcKindArray) return sdr_fail(SDR_ERR_INVALID, "the converter has no array");
+    if (d->kind == kDdcKindStap) return sdr_fail(SDR_ERR_INVALID, "a space-time converter takes sdr_ddc_stap_weights and sdr_ddc_stap_covariance");
     if (!w) return sdr_fail(SDR_ERR_INVALID, "weights is NULL");
     if (!ddc_array_weights_valid(d->array.K, w)) return sdr_fail(SDR_ERR_INVALID, "a weight is not finite");
     // the kernels take the weights by value with every launch: the pushes queued so far keep theirs, the next one has these
@@ -226,8 +129,8 @@ int sdr_ddc_array_weights(sdr_engine* e, sdr_ddc* d, const double* w) {
 int sdr_ddc_array_covariance(sdr_engine* e, sdr_ddc* d, double* R, int64_t* n, int clear) {
     if (int rc = sdr_set_device(e)) return rc;
     if (int rc = ddc_check(e, d)) return rc;
-    if (!d->has_array) return sdr_fail(SDR_ERR_INVALID, "the converter has no array");
-    if (d->has_stap) return sdr_fail(SDR_ERR_INVALID, "a space-time converter takes sdr_ddc_stap_weights and sdr_ddc_stap_covariance");
+    if (d->kind < kDdcKindArray) return sdr_fail(SDR_ERR_INVALID, "the converter has no array");
+    if (d->kind == kDdcKindStap) return sdr_fail(SDR_ERR_INVALID, "a space-time converter takes sdr_ddc_stap_weights and sdr_ddc_stap_covariance");
     if (!R || !n) return sdr_fail(SDR_ERR_INVALID, "no result block for the covariance or its count");
     if (!d->cov) return sdr_fail(SDR_ERR_STATE, "the converter was made without SDR_DDC_ARRAY_MEASURE");
     int64_t slots[kDdcArrayCovSlots];

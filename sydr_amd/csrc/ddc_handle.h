@@ -1,5 +1,6 @@
-// The converter's handle and what ddc.hip (mixer, FIR low-pass, integer decimation) and resample.hip (interpolation by L,
-// decimation by M) share of its kernels: the raw input's formats and the rounding of an integer ring.
+// The converter's handle and its LOADERS: how the one converter kernel and the one history kernel of ddc.hip read an input of the
+// push's block or of the history, and what the history keeps of it.  The kind of a converter picks its loader in one place,
+// ddc_with_loader.
 #pragma once
 
 #include "engine_internal.h"
@@ -8,44 +9,47 @@
 #include "ddc_stap.h"
 #include "mitigate.h"
 
+// What a converter's inputs are; every kind has what the kinds before it have (an array has a layout, a space-time array an array).
+enum DdcKind {
+    kDdcKindFormat = 0,     // sdr_ddc_create / _rational: one of the four raw formats, `hist` raw inputs
+    kDdcKindLayout,         // sdr_ddc_create_layout: in_fmt is not read, the staged bytes are decoded by `layout` where the kernels
+                            // load them and `hist` holds the inputs DECODED (ddc_layout.h)
+    kDdcKindArray,          // sdr_ddc_create_array: the K elements of a frame combined where they are loaded, `hist` holds COMBINED
+                            // inputs as cf64 (ddc_array.h)
+    kDdcKindStap            // sdr_ddc_create_stap (array.w is not read): T taps per element, `tail` the raw tail (ddc_stap.h)
+};
+
 struct sdr_ddc {
     sdr_engine* engine = nullptr;
+    DdcKind kind = kDdcKindFormat;
     int in_fmt = 0, D = 1, T = 1;
     uint64_t fcw = 0;
     double gain = 1.0;
-    double* taps = nullptr;      // device [T]
-    void* hist = nullptr;        // device [max(T-1, 1)] raw inputs, oldest first
+    // interpolation by L (sdr_ddc_create_rational; 1: the integer converter, `taps` its T taps): D is M, T the prototype's length,
+    // `taps` the table [Tp][L'] of resample_tiles.h
+    int L = 1;
+    int Tp = 1;                  // ceil(T / L): the history holds Tp - 1 inputs
+    double* taps = nullptr;      // device
+    void* hist = nullptr;        // device [max(Tp-1, 1)] inputs as the kind keeps them, oldest first
     int64_t n_seen = 0;          // inputs since creation / reset
     sdr::Mitigator* mit = nullptr;    // between the filter's output and the ring's format (sdr_ddc_mitigate), or none
-    // a rational resampler (sdr_ddc_create_rational with L > 1, resample.hip): D is M, T the prototype's length, `taps` the
-    // table [Tp][L'] of resample_tiles.h and `hist` the last Tp - 1 raw inputs
-    int L = 1;
-    int Tp = 1;                  // ceil(T / L): the history holds Tp - 1 inputs (L = 1: T)
-    // a converter made by sdr_ddc_create_layout: in_fmt is not read, the staged bytes are decoded by `layout` where the kernels
-    // load them and `hist` holds the last Tp - 1 inputs DECODED (ddc_layout.h)
-    bool has_layout = false;
     sdr::DdcLayout layout = {};
-    // a converter made by sdr_ddc_create_array (has_layout too): the kernels combine the K elements of a frame where they load
-    // it and `hist` holds the last Tp - 1 COMBINED inputs as cf64 (ddc_array.h).  With SDR_DDC_ARRAY_MEASURE `cov` is the device's
-    // 64 covariance slots (int64, or fp64 of a float32 layout), cov_n the inputs they hold, cov_slab the float pass's rows
-    bool has_array = false;
     sdr::DdcArray array = {};
+    // with SDR_DDC_ARRAY_MEASURE `cov` is the device's covariance slots (int64, or fp64 of a float32 layout) -- an array's 64, a
+    // space-time array's T lags of kDdcStapCovSlots --, cov_n the inputs they hold, cov_slab the float pass's rows
     void* cov = nullptr;
     int64_t cov_n = 0;
     DevBuf cov_slab;
-    // a converter made by sdr_ddc_create_stap (has_array too; array.w is not read): T taps per element, `tail` the device's raw
-    // tail of the last T - 1 decoded frames (ddc_stap.h) beside `hist`, and `cov` T lags of kDdcStapCovSlots slots each
-    bool has_stap = false;
     sdr::DdcStap stap = {};
-    double* tail = nullptr;
+    double* tail = nullptr;      // device: the last stap.T - 1 decoded frames
 };
 
 // Bytes of the covariance slots of a measuring converter.
 inline size_t ddc_cov_bytes(const sdr_ddc* d) {
-    return d->has_stap ? (size_t)d->stap.T * sdr::kDdcStapCovSlots * sizeof(int64_t) : (size_t)sdr::kDdcArrayCovSlots * sizeof(int64_t);
+    return d->kind == kDdcKindStap ? (size_t)d->stap.T * sdr::kDdcStapCovSlots * sizeof(int64_t) : (size_t)sdr::kDdcArrayCovSlots * sizeof(int64_t);
 }
 
-inline size_t ddc_in_bytes(int in_fmt) {
+SDR_DDC_HD inline size_t ddc_in_bytes(int in_fmt) {
     switch (in_fmt) {
         case SDR_DDC_IN_R8: return 1;
         case SDR_DDC_IN_R16: return 2;
@@ -55,11 +59,12 @@ inline size_t ddc_in_bytes(int in_fmt) {
     return 0;
 }
 
-// Bytes one input takes in the history.
+// Bytes one input takes in the history, and the history's (at least one unit, so that there is always a buffer).
 inline size_t ddc_hist_unit(const sdr_ddc* d) {
-    if (d->has_array) return (size_t)sdr::kDdcArrayHistoryUnit;
-    return d->has_layout ? (size_t)sdr::ddc_layout_history_unit(d->layout) : ddc_in_bytes(d->in_fmt);
+    if (d->kind >= kDdcKindArray) return (size_t)sdr::kDdcArrayHistoryUnit;
+    return d->kind == kDdcKindLayout ? (size_t)sdr::ddc_layout_history_unit(d->layout) : ddc_in_bytes(d->in_fmt);
 }
+inline size_t ddc_hist_bytes(const sdr_ddc* d) { return (size_t)(d->Tp > 1 ? d->Tp - 1 : 1) * ddc_hist_unit(d); }
 
 __device__ __forceinline__ void ddc_load(const void* __restrict__ p, int64_t i, int in_fmt, double* re, double* im) {
     switch (in_fmt) {
@@ -78,37 +83,127 @@ __device__ __forceinline__ void ddc_load(const void* __restrict__ p, int64_t i, 
     }
 }
 
-// How phase 1 of ddc_kernel / resample_kernel reads input `i` of the push's block or of the history: one of the four formats ...
+// A loader is a kernel argument by value.  block / history: input `i` of the push's block or of the history as x = re + i im, for
+// the converter kernel.  Kept, kept_block / kept_history and keep: what the history holds of an input, its read out of the block or
+// out of the old history and its store as element i, for the history kernel.  kTail: whether a raw tail is kept beside the history.
+//
+// One of the four formats: the history holds raw inputs, copied as units of 1, 2 or 4 bytes ...
 struct DdcFormatLoad {
     int in_fmt;
+    typedef uint32_t Kept;
+    static constexpr bool kTail = false;
     __device__ __forceinline__ void block(const void* __restrict__ p, int64_t i, double* re, double* im) const { ddc_load(p, i, in_fmt, re, im); }
     __device__ __forceinline__ void history(const void* __restrict__ p, int64_t i, double* re, double* im) const { ddc_load(p, i, in_fmt, re, im); }
+    __device__ __forceinline__ Kept kept_block(const void* p, int64_t i) const {
+        const int unit = (int)ddc_in_bytes(in_fmt);
+        return unit == 1 ? ((const uint8_t*)p)[i] : unit == 2 ? ((const uint16_t*)p)[i] : ((const uint32_t*)p)[i];
+    }
+    __device__ __forceinline__ Kept kept_history(const void* p, int64_t i) const { return kept_block(p, i); }
+    __device__ __forceinline__ void keep(void* hist, int i, Kept v) const {
+        const int unit = (int)ddc_in_bytes(in_fmt);
+        if (unit == 1) ((uint8_t*)hist)[i] = (uint8_t)v;
+        else if (unit == 2) ((uint16_t*)hist)[i] = (uint16_t)v;
+        else ((uint32_t*)hist)[i] = v;
+    }
 };
-// ... or a layout's frames, the history holding decoded components.
+
+// ... or a layout's frames, decoded here and nowhere else; the history holds decoded components, itself a layout.
 struct DdcLayoutLoad {
-    sdr::DdcLayout lay, hist;
+    sdr::DdcLayout lay;
+    typedef double2 Kept;
+    static constexpr bool kTail = false;
     __device__ __forceinline__ void block(const void* __restrict__ p, int64_t i, double* re, double* im) const { sdr::ddc_layout_load(p, i, lay, re, im); }
-    __device__ __forceinline__ void history(const void* __restrict__ p, int64_t i, double* re, double* im) const { sdr::ddc_layout_load(p, i, hist, re, im); }
+    __device__ __forceinline__ void history(const void* __restrict__ p, int64_t i, double* re, double* im) const {
+        sdr::ddc_layout_load(p, i, sdr::ddc_layout_history(lay), re, im);
+    }
+    __device__ __forceinline__ Kept kept_block(const void* p, int64_t i) const {
+        Kept v;
+        block(p, i, &v.x, &v.y);
+        return v;
+    }
+    __device__ __forceinline__ Kept kept_history(const void* p, int64_t i) const {
+        Kept v;
+        history(p, i, &v.x, &v.y);
+        return v;
+    }
+    __device__ __forceinline__ void keep(void* hist, int i, Kept v) const { sdr::ddc_layout_history_store(hist, i, sdr::ddc_layout_history(lay), v.x, v.y); }
 };
-// ... or an array's: the K elements of a frame combined with the weights, the history holding combined inputs as cf64.
+
+// ... or an array's: the K elements of a frame combined with the push's weights; the history holds combined inputs as cf64, and
+// one out of the old history keeps the value it was combined to.
 struct DdcArrayLoad {
     sdr::DdcLayout lay;
     sdr::DdcArray arr;
+    typedef double2 Kept;
+    static constexpr bool kTail = false;
     __device__ __forceinline__ void block(const void* __restrict__ p, int64_t i, double* re, double* im) const { sdr::ddc_array_load(p, i, lay, arr, re, im); }
     __device__ __forceinline__ void history(const void* __restrict__ p, int64_t i, double* re, double* im) const { sdr::ddc_array_history_load(p, i, re, im); }
+    __device__ __forceinline__ Kept kept_block(const void* p, int64_t i) const {
+        Kept v;
+        block(p, i, &v.x, &v.y);
+        return v;
+    }
+    __device__ __forceinline__ Kept kept_history(const void* p, int64_t i) const {
+        Kept v;
+        history(p, i, &v.x, &v.y);
+        return v;
+    }
+    __device__ __forceinline__ void keep(void* hist, int i, Kept v) const { sdr::ddc_array_history_store(hist, i, v.x, v.y); }
 };
 
-// ... or a space-time array's: T frames of K elements combined per input, earlier frames than the push's first out of the raw tail.
+// ... or a space-time array's: T frames of K elements combined per input, earlier frames than the push's first out of the raw
+// tail.  The 64 weights are part of the argument: a queued push keeps the weights it was queued with.  The tail after a push:
+// lane i < (T - 1) K of the history kernel takes element i % K of slot i / K -- out of the block, or, of a push shorter than T - 1
+// frames, further up the old tail (a shift, ddc_stap_tail_next).
 struct DdcStapLoad {
     sdr::DdcLayout lay;
     sdr::DdcArray arr;
     sdr::DdcStap stap;
-    const double* tail;
+    double* tail;
+    typedef double2 Kept;
+    static constexpr bool kTail = true;
     __device__ __forceinline__ void block(const void* __restrict__ p, int64_t i, double* re, double* im) const {
         sdr::ddc_stap_load(p, tail, i, lay, arr, stap, re, im);
     }
     __device__ __forceinline__ void history(const void* __restrict__ p, int64_t i, double* re, double* im) const { sdr::ddc_array_history_load(p, i, re, im); }
+    // (the history kernel reads the parts through copies of their own: one 1.2 KiB argument read in place at some 600 points
+    // is more than the compiler follows, and it would copy the whole argument to scratch memory, lane by lane)
+    __device__ __forceinline__ Kept kept_block(const void* p, int64_t i) const {
+        const sdr::DdcLayout l = lay;
+        const sdr::DdcArray a = arr;
+        const sdr::DdcStap s = stap;
+        Kept v;
+        sdr::ddc_stap_load(p, tail, i, l, a, s, &v.x, &v.y);
+        return v;
+    }
+    __device__ __forceinline__ Kept kept_history(const void* p, int64_t i) const {
+        Kept v;
+        history(p, i, &v.x, &v.y);
+        return v;
+    }
+    __device__ __forceinline__ void keep(void* hist, int i, Kept v) const { sdr::ddc_array_history_store(hist, i, v.x, v.y); }
+    __device__ __forceinline__ double2 tail_next(const void* p, int64_t n_in, int i) const {
+        double2 v = make_double2(0.0, 0.0);
+        const int slot = i / arr.K;
+        if (i < (stap.T - 1) * arr.K) sdr::ddc_stap_tail_next(p, tail, n_in, lay, arr, stap.T, slot, i - slot * arr.K, &v.x, &v.y);
+        return v;
+    }
+    __device__ __forceinline__ void tail_keep(int i, double2 v) const {
+        const int slot = i / arr.K;
+        if (i < (stap.T - 1) * arr.K) sdr::ddc_stap_tail_store(tail, slot, arr.K, i - slot * arr.K, v.x, v.y);
+    }
 };
+
+// The one place where a converter's kind becomes its loader: f(load) with the loader as the kernels take it, by value.
+template <class F>
+inline void ddc_with_loader(const sdr_ddc* d, F&& f) {
+    switch (d->kind) {
+        case kDdcKindStap: return f(DdcStapLoad{d->layout, d->array, d->stap, d->tail});
+        case kDdcKindArray: return f(DdcArrayLoad{d->layout, d->array});
+        case kDdcKindLayout: return f(DdcLayoutLoad{d->layout});
+        default: return f(DdcFormatLoad{d->in_fmt});
+    }
+}
 
 __device__ __forceinline__ double ddc_clip_rint(double v, double lim) { return fmin(fmax(rint(v), -lim), lim); }
 
@@ -120,22 +215,9 @@ inline int ddc_check(sdr_engine* e, const sdr_ddc* d) {
 
 namespace sdr {
 
-// resample.hip: the push of a converter with L > 1 (the arguments already checked against NULL and the engine by the caller).
-// ddc.hip: the history launch behind a push's kernel -- the last d->Tp - 1 of the raw inputs in the staging buffer and the old
-// history, under the scope "ddc_history_kernel".
-void ddc_history_launch(sdr_engine* e, sdr_ddc* d, int64_t n_in);
-// ddc.hip: the bytes a push of n_in >= 0 inputs copies to the staging buffer; of a converter with a layout SDR_ERR_INVALID when
-// they are not whole (nothing has changed then).
-int ddc_push_bytes(const sdr_ddc* d, int64_t n_in, size_t* bytes);
-int rs_push_impl(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in, int64_t off, int64_t* n_out, bool wait);
-// ddc_array.hip: the covariance pass of a converter with SDR_DDC_ARRAY_MEASURE over the n_in frames in the staging buffer, behind
-// the converter's kernel on the engine's stream, under the scope "ddc_array_cov_kernel"; no-op for every other converter.
-// ddc_array_cov_reserve, before the push has changed anything, makes room for the float pass's rows (SDR_ERR_NOMEM otherwise).
-int ddc_array_cov_reserve(sdr_engine* e, sdr_ddc* d, int64_t n_in);
-void ddc_array_cov_launch(sdr_engine* e, sdr_ddc* d, int64_t n_in);
-// ddc_stap.hip: the same two for a converter of sdr_ddc_create_stap (ddc_array_cov_* hand over to them): a lag per grid row,
-// partners before the push's first frame out of the raw tail, under the scope "ddc_stap_cov_kernel".
-int ddc_stap_cov_reserve(sdr_engine* e, sdr_ddc* d, int64_t n_in);
-void ddc_stap_cov_launch(sdr_engine* e, sdr_ddc* d, int64_t n_in);
+// ddc.hip: the one constructor behind the five sdr_ddc_create*: a converter of `kind` with interpolation L; `layout` from
+// kDdcKindLayout on, `array` from kDdcKindArray on, stap_taps and stap_w ([stap_taps][K][2]) of kDdcKindStap, unread otherwise.
+int ddc_create(sdr_engine* e, DdcKind kind, const sdr_ddc_cfg* cfg, int L, const sdr_ddc_layout* layout, const sdr_ddc_array* array, int stap_taps,
+               const double* stap_w, sdr_ddc** out);
 
 }  // namespace sdr

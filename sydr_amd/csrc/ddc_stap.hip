@@ -1,6 +1,6 @@
 // Space-time adaptive weights in the array down-converter (sdr_ddc_create_stap, sdr_ddc_stap_weights, sdr_ddc_stap_covariance):
 // a T-tap FIR per antenna element in front of the mixer, x_j = sum_t sum_a conj(w[t][a]) s_a[j - t], combined where
-// ddc_kernel / resample_kernel load their inputs (DdcStapLoad, ddc_handle.h; the arithmetic and the raw tail are ddc_stap.h).
+// ddc.hip's converter kernel loads its inputs (DdcStapLoad, ddc_handle.h; the arithmetic and the raw tail are ddc_stap.h).
 // The time taps give nulls that depend on frequency: two elements remove several partial-band jammers from different
 // directions.  This file holds the handle's entry points and the opt-in lag-covariance pass; what both must give is stated in
 // include/sydr_amd.h and, as NumPy, in sydr_amd/signal/stap.py.
@@ -19,7 +19,7 @@
 // every partial is int64; ONE 64-bit integer atomic add per entry per workgroup reaches memory.  FLOAT32 fields: fp64 partials,
 // a workgroup stores its row of a slab [x][tau][slots] and ddc_stap_cov_finish_kernel adds the rows in ascending x.
 #include "engine_internal.h"
-#include "ddc_handle.h"
+#include "ddc_cov.h"
 
 #include <cmath>
 #include <new>
@@ -27,33 +27,6 @@
 using namespace sdr;
 
 namespace {
-
-constexpr int kCovThreads = 256, kCovWaves = kCovThreads / 64, kCovRun = 64;
-constexpr int64_t kCovChunk = (int64_t)kCovThreads * kCovRun;     // frames of a workgroup
-constexpr int kCovNarrow = 0, kCovWide = 1, kCovFloat = 2;
-
-template <int MODE>
-struct CovTypes {
-    typedef int acc;
-    typedef int el;
-};
-template <>
-struct CovTypes<kCovWide> {
-    typedef long long acc;
-    typedef int el;
-};
-template <>
-struct CovTypes<kCovFloat> {
-    typedef double acc;
-    typedef double el;
-};
-
-template <class T>
-__device__ __forceinline__ T cov_wave_add(T v) {     // a fixed butterfly: the same bits every time
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
 
 // The K elements of frame f of the push (f >= 0: the staged bytes; f < 0: slot T - 1 + f of the raw tail, whose doubles hold the
 // integers of an integer field exactly).
@@ -149,50 +122,18 @@ __global__ __launch_bounds__(kDdcStapCovSlots) void ddc_stap_cov_finish_kernel(c
     cov[c] = t;
 }
 
-int cov_mode(const DdcLayout& l) { return l.kind == kDdcFieldFloat32 ? kCovFloat : l.kind == kDdcFieldInt16 ? kCovWide : kCovNarrow; }
-
-template <int K>
-void cov_launch_k(sdr_engine* e, sdr_ddc* d, int64_t n_in, unsigned grid, int mode, void* out) {
-    const void* in = (const void*)e->ddc_stage.ptr;
-    const dim3 g(grid, (unsigned)d->stap.T);
-    if (mode == kCovFloat)
-        hipLaunchKernelGGL((ddc_stap_cov_kernel<K, kCovFloat>), g, dim3(kCovThreads), 0, e->stream, in, (const double*)d->tail, n_in, d->stap.T,
-                           d->layout, d->array, out);
-    else if (mode == kCovWide)
-        hipLaunchKernelGGL((ddc_stap_cov_kernel<K, kCovWide>), g, dim3(kCovThreads), 0, e->stream, in, (const double*)d->tail, n_in, d->stap.T,
-                           d->layout, d->array, out);
-    else
-        hipLaunchKernelGGL((ddc_stap_cov_kernel<K, kCovNarrow>), g, dim3(kCovThreads), 0, e->stream, in, (const double*)d->tail, n_in, d->stap.T,
-                           d->layout, d->array, out);
-}
-
-inline int64_t cov_workgroups(int64_t n_in) { return (n_in + kCovChunk - 1) / kCovChunk; }
-
 }  // namespace
 
-int sdr::ddc_stap_cov_reserve(sdr_engine* e, sdr_ddc* d, int64_t n_in) {
-    if (!d->cov || n_in <= 0) return SDR_OK;
-    const int64_t grid = cov_workgroups(n_in);
-    if (grid > 0x7fffffff) return sdr_fail(SDR_ERR_RANGE, "%lld frames in one push of a measuring array", (long long)n_in);
-    if (cov_mode(d->layout) != kCovFloat) return SDR_OK;
-    return sdr_devbuf_reserve(e, &d->cov_slab, (size_t)grid * d->stap.T * kDdcStapCovSlots * sizeof(double));
-}
-
 void sdr::ddc_stap_cov_launch(sdr_engine* e, sdr_ddc* d, int64_t n_in) {
-    if (!d->cov || n_in <= 0) return;
     ProfScope ps(e, "ddc_stap_cov_kernel");
     const int mode = cov_mode(d->layout);
     const unsigned grid = (unsigned)cov_workgroups(n_in);
+    const void* in = (const void*)e->ddc_stage.ptr;
     void* out = mode == kCovFloat ? d->cov_slab.ptr : d->cov;
-    switch (d->array.K) {
-        case 2: cov_launch_k<2>(e, d, n_in, grid, mode, out); break;
-        case 3: cov_launch_k<3>(e, d, n_in, grid, mode, out); break;
-        case 4: cov_launch_k<4>(e, d, n_in, grid, mode, out); break;
-        case 5: cov_launch_k<5>(e, d, n_in, grid, mode, out); break;
-        case 6: cov_launch_k<6>(e, d, n_in, grid, mode, out); break;
-        case 7: cov_launch_k<7>(e, d, n_in, grid, mode, out); break;
-        default: cov_launch_k<8>(e, d, n_in, grid, mode, out); break;
-    }
+    cov_dispatch(d->array.K, mode, [&](auto k, auto m) {
+        hipLaunchKernelGGL((ddc_stap_cov_kernel<decltype(k)::value, decltype(m)::value>), dim3(grid, (unsigned)d->stap.T), dim3(kCovThreads), 0,
+                           e->stream, in, (const double*)d->tail, n_in, d->stap.T, d->layout, d->array, out);
+    });
     if (mode == kCovFloat)
         hipLaunchKernelGGL(ddc_stap_cov_finish_kernel, dim3((unsigned)d->stap.T), dim3(kDdcStapCovSlots), 0, e->stream, (const double*)d->cov_slab.ptr,
                            (int64_t)grid, d->stap.T, (double*)d->cov);
@@ -203,54 +144,13 @@ extern "C" {
 
 int sdr_ddc_create_stap(sdr_engine* e, const sdr_ddc_cfg* cfg, int interpolation, const sdr_ddc_layout* layout, const sdr_ddc_array* array,
                         int n_taps, const double* w, sdr_ddc** out) {
-    if (int rc = sdr_set_device(e)) return rc;
-    if (!cfg || !out) return sdr_fail(SDR_ERR_INVALID, "NULL configuration or result pointer");
-    *out = nullptr;
-    if (!layout || !array) return sdr_fail(SDR_ERR_INVALID, "NULL layout or array");
-    if (!ddc_stap_taps_valid(n_taps)) return sdr_fail(SDR_ERR_INVALID, "%d taps per element outside %d..%d", n_taps, kDdcStapMinTaps, kDdcStapMaxTaps);
-    if (!w) return sdr_fail(SDR_ERR_INVALID, "weights is NULL");
-    if (array->n_elements < kDdcArrayMin || array->n_elements > kDdcArrayMax)
-        return sdr_fail(SDR_ERR_INVALID, "%d elements outside %d..%d", array->n_elements, kDdcArrayMin, kDdcArrayMax);
-    const int K = array->n_elements;
-    if (!ddc_stap_weights_valid(n_taps, K, w)) return sdr_fail(SDR_ERR_INVALID, "a weight is not finite");
-    // the converter itself is sdr_ddc_create_array's, every check of cfg, layout, lanes and flags included (the array's own
-    // weights are not read: tap 0's stand in for them, and no kernel of this converter reads them)
-    sdr_ddc_array plain = *array;
-    for (int a = 0; a < kDdcArrayMax; ++a) plain.weights[a][0] = a < K ? w[2 * a] : 0.0, plain.weights[a][1] = a < K ? w[2 * a + 1] : 0.0;
-    sdr_ddc* d = nullptr;
-    if (int rc = sdr_ddc_create_array(e, cfg, interpolation, layout, &plain, &d)) return rc;
-    const size_t tail_bytes = ddc_stap_tail_bytes(n_taps, K);
-    const size_t cov_bytes = (size_t)n_taps * kDdcStapCovSlots * sizeof(int64_t);
-    void* tail = nullptr;
-    void* cov = nullptr;
-    hipError_t err = hipMalloc(&tail, tail_bytes);
-    if (err == hipSuccess) err = hipMemsetAsync(tail, 0, tail_bytes, e->stream);
-    if (err == hipSuccess && d->cov) {
-        err = hipMalloc(&cov, cov_bytes);
-        if (err == hipSuccess) err = hipMemsetAsync(cov, 0, cov_bytes, e->stream);
-    }
-    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-    if (err != hipSuccess) {
-        if (tail) (void)hipFree(tail);
-        if (cov) (void)hipFree(cov);
-        sdr_ddc_destroy(e, d);
-        return sdr_fail(SDR_ERR_HIP, "sdr_ddc_create_stap: %s", hipGetErrorString(err));
-    }
-    if (d->cov) {
-        (void)hipFree(d->cov);
-        d->cov = cov;
-    }
-    d->tail = (double*)tail;
-    d->has_stap = true;
-    ddc_stap_set(&d->stap, n_taps, K, w);
-    *out = d;
-    return SDR_OK;
+    return ddc_create(e, kDdcKindStap, cfg, interpolation, layout, array, n_taps, w, out);
 }
 
 int sdr_ddc_stap_weights(sdr_engine* e, sdr_ddc* d, const double* w) {
     if (int rc = sdr_set_device(e)) return rc;
     if (int rc = ddc_check(e, d)) return rc;
-    if (!d->has_stap) return sdr_fail(SDR_ERR_INVALID, "the converter was not made by sdr_ddc_create_stap");
+    if (d->kind != kDdcKindStap) return sdr_fail(SDR_ERR_INVALID, "the converter was not made by sdr_ddc_create_stap");
     if (!w) return sdr_fail(SDR_ERR_INVALID, "weights is NULL");
     if (!ddc_stap_weights_valid(d->stap.T, d->array.K, w)) return sdr_fail(SDR_ERR_INVALID, "a weight is not finite");
     // the kernels take the weights by value with every launch: the pushes queued so far keep theirs, the next one has these
@@ -261,7 +161,7 @@ int sdr_ddc_stap_weights(sdr_engine* e, sdr_ddc* d, const double* w) {
 int sdr_ddc_stap_covariance(sdr_engine* e, sdr_ddc* d, double* C, int64_t* n, int clear) {
     if (int rc = sdr_set_device(e)) return rc;
     if (int rc = ddc_check(e, d)) return rc;
-    if (!d->has_stap) return sdr_fail(SDR_ERR_INVALID, "the converter was not made by sdr_ddc_create_stap");
+    if (d->kind != kDdcKindStap) return sdr_fail(SDR_ERR_INVALID, "the converter was not made by sdr_ddc_create_stap");
     if (!C || !n) return sdr_fail(SDR_ERR_INVALID, "no result block for the covariance or its count");
     if (!d->cov) return sdr_fail(SDR_ERR_STATE, "the converter was made without SDR_DDC_ARRAY_MEASURE");
     int64_t slots[kDdcStapMaxTaps * kDdcStapCovSlots];

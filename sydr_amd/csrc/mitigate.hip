@@ -2,7 +2,7 @@
 // (sdr_ddc_mitigate, include/sydr_amd.h).  What the ring must hold is stated in sydr_amd/signal/mitigate.py; which values a
 // push needs, which segments it transforms, which of them it counts and where its outputs land is mit_plan.h.
 //
-// With a mitigator attached ddc_kernel (ddc.hip, unchanged) writes its outputs as cf64 behind the kept state in a linear work
+// With a mitigator attached the converter kernel (ddc.hip) writes its outputs as cf64 behind the kept state in a linear work
 // buffer W = [the last K values of v][this push's v].  Behind it on the engine's stream:
 // mit_blank_kernel    a workgroup per tile of kMitBlankTile u: the triggers of the tile and of its hold / lead halo into LDS
 //   (p = re*re + im*im with explicitly rounded products and sum), an exclusive prefix count over them, so that "any trigger

@@ -137,7 +137,9 @@ def test_fractional_float32_against_the_statement(engine, ring_fmt, cplx):
 
 # ------------------------------------------------------------------------------------------------ 4. the cut
 CUTS = [(cases.packed_layout(2), (33, 2)), (cases.packed_layout(1, stride=3, lane=1), (33, 2)), (dc.InputLayout(dc.FIELD_FLOAT32, complex=True), (512, 16)),
-        (cases.packed_layout(4, complex=True), (1, 1)), (cases.packed_layout(2), (250, 341, 1500))]
+        (cases.packed_layout(4, complex=True), (1, 1)), (cases.packed_layout(2), (250, 341, 1500)),
+        # (frames of whole bytes behind a resampler: pushes of exactly 1, Tp - 2, Tp - 1 and Tp = 3 frames, none rounded up)
+        (dc.InputLayout(dc.FIELD_INT8, 0, 8, 5, True), (3, 2, 7))]
 
 
 @pytest.mark.parametrize("layout,shape", CUTS, ids=lambda v: repr(v) if isinstance(v, dc.InputLayout) else cases.shape_id(v))
