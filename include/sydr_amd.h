@@ -106,7 +106,10 @@ int sdr_prof_reset(sdr_engine* e);
  * workgroups of the tick's launch; "pcps_no_shared_spectra" = 1 transforms the Doppler-mixed millisecond once per bin
  * even where bins a whole number of FFT bins apart could share a spectrum; "epl_no_chip_variant",
  * "epl_no_split_variant", "epl_no_half_chip_view" = 1 keep the E/P/L correlator from its chip-aligned core, from the
- * kernel with the tap switch positions compiled in, from the half-chip view of 32-52 samples per chip.  Integer
+ * kernel with the tap switch positions compiled in, from the half-chip view of 32-52 samples per chip;
+ * "epl_xcd_run" = R (0 .. 65536) lets each of the device's 8 XCDs take runs of R consecutive items of an E/P/L launch, so
+ * that the channel-epochs of one millisecond of an epoch-major list read the ring through one L2 (0: the workgroups take the
+ * items in linear order, dealt round-robin to the XCDs; -1: the library's default, 64); plans read it when they run; outputs are the same bits.  Integer
  * results do not depend on any of them, floating ones to rounding. */
 int sdr_set_option(sdr_engine* e, const char* name, int value);
 

@@ -272,6 +272,10 @@ int sdr_set_option(sdr_engine* e, const char* name, int value) {
     else if (!strcmp(name, "pcps_prn_chunk")) e->pcps_prn_chunk = value;
     else if (!strcmp(name, "epl_no_chip_variant")) e->epl_no_chip = value != 0;
     else if (!strcmp(name, "epl_no_split_variant")) e->epl_no_split = value != 0;
+    else if (!strcmp(name, "epl_xcd_run")) {
+        if (value < -1 || value > kEplXcdRunMax) return sdr_fail(SDR_ERR_RANGE, "epl_xcd_run %d outside -1..%d", value, kEplXcdRunMax);
+        e->epl_xcd_run = value < 0 ? kEplXcdRunDefault : value;
+    }
     else if (!strcmp(name, "epl_no_half_chip_view")) e->epl_no_double = value != 0;
     else if (!strcmp(name, "epl_no_two_chip_variant")) e->epl_no_chip2 = value != 0;
     else if (!strcmp(name, "corr_profile_per_sample")) e->corr_per_sample = value != 0;

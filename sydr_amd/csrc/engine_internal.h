@@ -30,6 +30,16 @@ int sdr_fail(int status, const char* fmt, ...);
 // [c[L-1], c[0..L-1], c[0]] (channel_l1ca_kaplan.py:104-107) extended periodically.
 #define SDR_LUT_PAD 4
 
+// "epl_xcd_run" (xcd_order.h): the run of consecutive items of an E/P/L launch that one XCD takes.  The default is two
+// milliseconds of the headline's 32 channels -- the channel-epochs of one millisecond of an epoch-major list read the same
+// stretch of the ring, and, their code phases differing, half of the next millisecond's -- chosen by the sweep in
+// docs/notes/K1.md; the largest value keeps a tile of 8 runs far inside 32 bits.
+#ifndef SDR_EPL_XCD_RUN
+#define SDR_EPL_XCD_RUN 64
+#endif
+constexpr int kEplXcdRunDefault = SDR_EPL_XCD_RUN;
+constexpr int kEplXcdRunMax = 1 << 16;
+
 struct ProfRecord {
     const char* name;
     hipEvent_t start, stop;
@@ -125,6 +135,7 @@ struct sdr_engine {
     bool prof_calls_only = false;    // sdr_prof_enable(e, 2): only the "call_*" scopes record
     bool epl_no_chip2 = false;       // diagnostics: keep the 8-sample boundary variant where the two-chip kernel would run
     bool epl_no_split = false;       // diagnostics: keep the run-time switch positions where the KS = 12 kernel would run
+    int epl_xcd_run = kEplXcdRunDefault;// "epl_xcd_run": consecutive items of an E/P/L launch an XCD takes (xcd_order.h), 0 = linear order
     int pcps_prn_chunk = 0;          // diagnostics: PRNs per inverse sweep (0 = as many as the work buffers hold)
     bool pcps_force_map = false;     // diagnostics / tests: materialise the map even when the caller does not ask for it
     bool pcps_no_overlap = false;    // diagnostics: one stream for the inverse sweeps of a map-free search

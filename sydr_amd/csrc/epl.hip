@@ -87,12 +87,12 @@ __global__ __launch_bounds__(kWaveThreads, (sizeof...(P) > 4 ? 2 : SDR_EPL2_WAVE
                                                             int64_t capacity, const sdr_epl_item* __restrict__ items, int n_items,
                                                             const uint32_t* __restrict__ luts, int lut_words, int lut_stride,
                                                             const double* __restrict__ spacing, double fs, double* __restrict__ out,
-                                                            const ChipNSetup<P...>* __restrict__ setups) {
+                                                            const ChipNSetup<P...>* __restrict__ setups, int xcd_run) {
     extern __shared__ double smem[];
     uint32_t* zero_words = reinterpret_cast<uint32_t*>(smem);
     uint32_t* lut = zero_words + 8;
     const int lane = threadIdx.x;
-    const int item = blockIdx.x;
+    const int item = __builtin_amdgcn_readfirstlane((int)xcd_order(blockIdx.x, gridDim.x, (unsigned)xcd_run));   // (xcd_order.h: runs of consecutive items per XCD)
     const sdr_epl_item it = items[item];
     EpochParams ep;
     ep.start_sample = it.start_sample;
@@ -121,7 +121,7 @@ __global__ __launch_bounds__(kWaveThreads, (sizeof...(P) > 4 ? 2 : SDR_EPL2_WAVE
 template <int FMT, int NT>
 void launch_one(sdr_engine* e, hipStream_t stream, const sdr_epl_item* d_items, int n_items, const double* d_spacing, double fs,
                 int tap0, int n_taps_total, int lut_words, int wide, int group_stride, bool doubled, double* d_out,
-                const void* d_setups) {
+                const void* d_setups, int xcd_run) {
     // long replicas: four waves (four epochs of one channel) per workgroup around one staged table
     const int wpw = (lut_words >= kLongLutWords && group_stride > 0) ? 4 : 1;
     const int threads = kWaveThreads * wpw;
@@ -136,7 +136,7 @@ void launch_one(sdr_engine* e, hipStream_t stream, const sdr_epl_item* d_items, 
             (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), shmem, stream, e->iq, (const void*)e->iq, e->iq_capacity, d_items, n_items, stride,
                            doubled ? e->luts2 : e->luts, lut_words, doubled ? e->lut2_stride : e->lut_stride, d_spacing, fs, tap0,
-                           n_taps_total, d_out, d_setups);
+                           n_taps_total, d_out, d_setups, xcd_run);
     };
     constexpr bool kOdd = NT == 3 || NT == 5;               // (the compile-time tap geometries exist for these)
     // (the straight-line kernels read the plan's per-item setups: without them the run-time-position kernel serves the list)
@@ -166,7 +166,8 @@ void launch_one(sdr_engine* e, hipStream_t stream, const sdr_epl_item* d_items, 
         int64_t cap = e->iq_capacity;
         int n = n_items, gs = stride, lw = lut_words, ls = doubled ? e->lut2_stride : e->lut_stride, t0 = tap0, nt = n_taps_total;
         const uint32_t* luts = doubled ? e->luts2 : e->luts;
-        void* args[] = {&ring, &flipped, &cap, &d_items, &n, &gs, &luts, &lw, &ls, &d_spacing, &fs, &t0, &nt, &d_out, &d_setups};
+        int xr = xcd_run;
+        void* args[] = {&ring, &flipped, &cap, &d_items, &n, &gs, &luts, &lw, &ls, &d_spacing, &fs, &t0, &nt, &d_out, &d_setups, &xr};
         if (shmem > 64u * 1024u) (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
         (void)hipLaunchKernel(kernel, dim3(grid), dim3(threads), args, shmem, stream);
     };
@@ -203,22 +204,22 @@ void launch_one(sdr_engine* e, hipStream_t stream, const sdr_epl_item* d_items, 
 
 template <int FMT>
 void launch_fmt(sdr_engine* e, hipStream_t stream, const sdr_epl_item* d_items, int n_items, const double* d_spacing, double fs,
-                int n_taps, int lut_words, int wide, int group_stride, bool doubled, double* d_out, const void* d_setups) {
+                int n_taps, int lut_words, int wide, int group_stride, bool doubled, double* d_out, const void* d_setups, int xcd_run) {
     // Taps are served in register-resident chunks of 5/3/2/1.
     int t0 = 0;
     while (t0 < n_taps) {
         int left = n_taps - t0;
         if (left >= 5) {
-            launch_one<FMT, 5>(e, stream, d_items, n_items, d_spacing, fs, t0, n_taps, lut_words, wide, group_stride, doubled, d_out, d_setups);
+            launch_one<FMT, 5>(e, stream, d_items, n_items, d_spacing, fs, t0, n_taps, lut_words, wide, group_stride, doubled, d_out, d_setups, xcd_run);
             t0 += 5;
         } else if (left >= 3) {
-            launch_one<FMT, 3>(e, stream, d_items, n_items, d_spacing, fs, t0, n_taps, lut_words, wide, group_stride, doubled, d_out, d_setups);
+            launch_one<FMT, 3>(e, stream, d_items, n_items, d_spacing, fs, t0, n_taps, lut_words, wide, group_stride, doubled, d_out, d_setups, xcd_run);
             t0 += 3;
         } else if (left == 2) {
-            launch_one<FMT, 2>(e, stream, d_items, n_items, d_spacing, fs, t0, n_taps, lut_words, wide, group_stride, doubled, d_out, d_setups);
+            launch_one<FMT, 2>(e, stream, d_items, n_items, d_spacing, fs, t0, n_taps, lut_words, wide, group_stride, doubled, d_out, d_setups, xcd_run);
             t0 += 2;
         } else {
-            launch_one<FMT, 1>(e, stream, d_items, n_items, d_spacing, fs, t0, n_taps, lut_words, wide, group_stride, doubled, d_out, d_setups);
+            launch_one<FMT, 1>(e, stream, d_items, n_items, d_spacing, fs, t0, n_taps, lut_words, wide, group_stride, doubled, d_out, d_setups, xcd_run);
             t0 += 1;
         }
     }
@@ -895,6 +896,8 @@ int sdr_epl_plan_run_range_on(sdr_engine* e, sdr_epl_plan* p, int64_t first, int
     double* out = p->d_out + (size_t)first * 2 * p->n_taps;
     const int n = (int)count;
     const void* setups = p->d_setups ? p->d_setups + (size_t)first * p->setup_bytes : nullptr;
+    // (the order in which the range's own workgroups, 0 .. count - 1, take its items: xcd_order.h; read when the plan runs)
+    const int xcd_run = e->epl_xcd_run;
     if (e->iq_fmt == SDR_FMT_CI8 && (p->wide & (3 * kVariantC2)) && setups) {      // two chips per lane: its own kernel
         hipStream_t st = ctx->stream;
         ProfScope ps(e, "epl_kernel", st);
@@ -902,7 +905,7 @@ int sdr_epl_plan_run_range_on(sdr_engine* e, sdr_epl_plan* p, int64_t first, int
         const int shape = (p->wide / kVariantC2) & 3;
         auto launch2 = [&](auto kernel, auto* typed) {
             hipLaunchKernelGGL(kernel, dim3(n), dim3(kWaveThreads), shmem, st, e->iq, (const void*)e->iq, e->iq_capacity,
-                               items, n, e->luts, p->lut_words, e->lut_stride, p->d_spacing, p->fs, out, typed);
+                               items, n, e->luts, p->lut_words, e->lut_stride, p->d_spacing, p->fs, out, typed, xcd_run);
         };
         if (shape == 1) launch2(epl2_kernel<4, 9, 14, 19>, reinterpret_cast<const sdr::ChipNSetup<4, 9, 14, 19>*>(setups));
         else if (shape == 2) launch2(epl2_kernel<5, 11, 17, 23>, reinterpret_cast<const sdr::ChipNSetup<5, 11, 17, 23>*>(setups));
@@ -911,10 +914,10 @@ int sdr_epl_plan_run_range_on(sdr_engine* e, sdr_epl_plan* p, int64_t first, int
         hipStream_t st = ctx->stream;
         ProfScope ps(e, "epl_kernel", st);
         switch (e->iq_fmt) {
-            case SDR_FMT_CI8: launch_fmt<SDR_FMT_CI8>(e, st, items, n, p->d_spacing, p->fs, p->n_taps, p->lut_words, p->wide, p->group_stride, p->doubled, out, setups); break;
-            case SDR_FMT_CI16: launch_fmt<SDR_FMT_CI16>(e, st, items, n, p->d_spacing, p->fs, p->n_taps, p->lut_words, p->wide, p->group_stride, p->doubled, out, setups); break;
-            case SDR_FMT_CF32: launch_fmt<SDR_FMT_CF32>(e, st, items, n, p->d_spacing, p->fs, p->n_taps, p->lut_words, p->wide, p->group_stride, p->doubled, out, setups); break;
-            default: launch_fmt<SDR_FMT_CF64>(e, st, items, n, p->d_spacing, p->fs, p->n_taps, p->lut_words, p->wide, p->group_stride, p->doubled, out, setups); break;
+            case SDR_FMT_CI8: launch_fmt<SDR_FMT_CI8>(e, st, items, n, p->d_spacing, p->fs, p->n_taps, p->lut_words, p->wide, p->group_stride, p->doubled, out, setups, xcd_run); break;
+            case SDR_FMT_CI16: launch_fmt<SDR_FMT_CI16>(e, st, items, n, p->d_spacing, p->fs, p->n_taps, p->lut_words, p->wide, p->group_stride, p->doubled, out, setups, xcd_run); break;
+            case SDR_FMT_CF32: launch_fmt<SDR_FMT_CF32>(e, st, items, n, p->d_spacing, p->fs, p->n_taps, p->lut_words, p->wide, p->group_stride, p->doubled, out, setups, xcd_run); break;
+            default: launch_fmt<SDR_FMT_CF64>(e, st, items, n, p->d_spacing, p->fs, p->n_taps, p->lut_words, p->wide, p->group_stride, p->doubled, out, setups, xcd_run); break;
         }
     }
     SDR_HIP(hipGetLastError());

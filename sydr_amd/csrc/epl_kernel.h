@@ -4,6 +4,7 @@
 #pragma once
 #include "correlator.h"
 #include "correlator_chip.h"
+#include "xcd_order.h"
 
 namespace {
 
@@ -50,7 +51,7 @@ __global__ __launch_bounds__(kWaveThreads * WPW, (KS != 0 ? SDR_EPL_KS_WAVES : (
                                                        int lut_words, int lut_stride,
                                                        const double* __restrict__ spacing, double fs,
                                                        int tap0, int n_taps_total,
-                                                       double* __restrict__ out, const void* __restrict__ setups) {
+                                                       double* __restrict__ out, const void* __restrict__ setups, int xcd_run) {
     constexpr int kThreads = kWaveThreads * WPW;
     constexpr bool kPre = W == kChipMax && FMT == SDR_FMT_CI8 && KM != 0 && (KS != 0 || KI != 0);   // the plan holds a ChipSetup per item
     extern __shared__ double smem[];
@@ -65,15 +66,19 @@ __global__ __launch_bounds__(kWaveThreads * WPW, (KS != 0 ? SDR_EPL_KS_WAVES : (
 #ifdef SDR_TRACE_WG
     const unsigned long long t_start = wall_clock64();
 #endif
-    int item = blockIdx.x;
+    // (the workgroup's place in the launch: runs of xcd_run consecutive places per XCD -- xcd_order.h; four waves per
+    // workgroup: the columns of a group then share an XCD)
+    // (a scalar, as blockIdx.x was: the division's quotient comes out of the vector unit)
+    const int wg = __builtin_amdgcn_readfirstlane((int)xcd_order(blockIdx.x, gridDim.x, (unsigned)xcd_run));
+    int item = wg;
     if (WPW > 1) {
-        const int g = blockIdx.x / group_stride, c = blockIdx.x - g * group_stride;
+        const int g = wg / group_stride, c = wg - g * group_stride;
         item = (g * WPW + wave) * group_stride + c;
     }
     const bool have = item < n_items;
     // (a wave without an item still stages its share of the table: the slot of its group's column c = item c of the
     // range -- clamped, because a range shorter than the stride launches columns that hold no item at all)
-    const int column = (int)(blockIdx.x % group_stride);
+    const int column = (int)((unsigned)wg % group_stride);
     const sdr_epl_item it = items[have ? item : (column < n_items ? column : n_items - 1)];
     stage_lut<kThreads>(lut, luts + (size_t)it.code_slot * lut_stride, lut_words, tid);
     double dphi;
@@ -162,14 +167,14 @@ __global__ __launch_bounds__(kWaveThreads * WPW, (KS != 0 ? SDR_EPL_KS_WAVES : (
         if (lane < 2 * NT) out[(size_t)item * 2 * n_taps_total + 2 * tap0 + lane] = total;
     }
 #ifdef SDR_TRACE_WG
-    if (tid == 0 && blockIdx.x < 65536) {
+    if (tid == 0 && wg < 65536) {     // (one record per place in the launch -- with one wave per workgroup: per item)
         unsigned hw;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
         unsigned xcc;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        g_wg_trace[3 * blockIdx.x] = t_start;
-        g_wg_trace[3 * blockIdx.x + 1] = wall_clock64();
-        g_wg_trace[3 * blockIdx.x + 2] = ((unsigned long long)xcc << 32) | hw;
+        g_wg_trace[3 * wg] = t_start;
+        g_wg_trace[3 * wg + 1] = wall_clock64();
+        g_wg_trace[3 * wg + 2] = ((unsigned long long)xcc << 32) | hw;
     }
 #endif
 }

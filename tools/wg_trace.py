@@ -1,4 +1,6 @@
-"""Debug: per-workgroup timeline of epl_kernel (needs a build with -DSDR_TRACE_WG loaded from SYDR_TRACE_LIB)."""
+"""Debug: per-workgroup timeline of epl_kernel (needs a build with -DSDR_TRACE_WG: tools/build_trace_lib.sh, loaded through
+SYDR_AMD_LIB).  --xcd-run R: the launch runs with "epl_xcd_run" = R (default: the library's own) and the placement is reported
+-- of every run of R consecutive items (R = 0: of 32), how many carry the XCC_ID most of the run carries."""
 import ctypes, os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -15,6 +17,8 @@ rng = np.random.default_rng(1)
 n_items, n, step = 32000, 25000, 0.04092
 items = make_items(np.arange(n_items) % 32, n, rng.integers(0, cap, n_items), 1000.0, 0.3, 0.01, step)
 plan = e.epl_plan(items, (-0.5, 0.0, 0.5), 25e6)
+xcd_run = int(sys.argv[sys.argv.index("--xcd-run") + 1]) if "--xcd-run" in sys.argv else -1
+e.set_option("epl_xcd_run", xcd_run)
 for _ in range(3):
     plan.run()
 e.sync()
@@ -43,3 +47,13 @@ print("simd use", np.bincount(simd[live]), "wave slots", np.bincount(wave[live])
 # dispatch: how long after a WG ends does the next one start on the same CU?
 order = np.argsort(t0)
 print("start times: first 10 WG starts (ticks)", (np.sort(t0)[:3000:300] - t0.min()))
+# placement: the trace is indexed by the workgroup's place in the launch -- with one wave per workgroup its item
+R = xcd_run if xcd_run > 0 else 32
+full = (n_items // (8 * R)) * 8 * R
+runs = xcc[:full].reshape(-1, R)
+major = np.array([np.bincount(r, minlength=8).max() for r in runs])
+print("epl_xcd_run %d: %d runs of %d items in full tiles; items on their run's XCC_ID: %d of %d (%.4f); runs wholly on one XCC_ID: %d of %d"
+      % (xcd_run, len(runs), R, major.sum(), full, major.sum() / full, (major == R).sum(), len(runs)))
+per_x = [np.unique(xcc[:full].reshape(-1, 8, R)[:, x, :]) for x in range(8)]
+print("XCC_IDs seen by the x-th run of a tile:", [list(map(int, u)) for u in per_x])
+print("XCC_ID of items 0..15:", xcc[:16].tolist(), " items per XCC_ID:", np.bincount(xcc, minlength=8).tolist())
