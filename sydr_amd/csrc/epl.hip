@@ -118,111 +118,76 @@ __global__ __launch_bounds__(kWaveThreads, (sizeof...(P) > 4 ? 2 : SDR_EPL2_WAVE
     if (lane < 8) out[(size_t)item * 6 + slot] = total;
 }
 
+// One chunk of NT taps of a list: the kernel its variant word decodes to (epl_variant.h), launched through its address --
+// every epl_kernel has the same arguments.
 template <int FMT, int NT>
-void launch_one(sdr_engine* e, hipStream_t stream, const sdr_epl_item* d_items, int n_items, const double* d_spacing, double fs,
-                int tap0, int n_taps_total, int lut_words, int wide, int group_stride, bool doubled, double* d_out,
-                const void* d_setups, int xcd_run) {
+int launch_one(sdr_engine* e, hipStream_t stream, const sdr_epl_item* d_items, int n_items, const double* d_spacing, double fs,
+               int tap0, int n_taps_total, int lut_words, int wide, int group_stride, bool doubled, double* d_out,
+               const void* d_setups, int xcd_run) {
     // long replicas: four waves (four epochs of one channel) per workgroup around one staged table
     const int wpw = (lut_words >= kLongLutWords && group_stride > 0) ? 4 : 1;
+    // (the straight-line kernels read the plan's per-item setups: without them the run-time-position kernel serves the list)
+    const EplForm f = decode(wide, FMT, NT, wpw, d_setups != nullptr);
+    // (the chip-aligned cores are compiled for a ci8 ring alone, and chosen for one alone: the other formats name the 16-sample
+    // boundary kernel where ci8 names a chip-aligned one)
+    constexpr int kW = FMT == SDR_FMT_CI8 ? kChipMax : 16;
+    constexpr int kOdd = NT == 3 || NT == 5 ? 1 : 0;          // (the compile-time tap geometries exist for these)
+    const void* kernel = nullptr;
+    if (f.row) {
+#define SDR_ROW(N, KM, KS, KI) \
+    if (NT == N && f.km == KM && f.ks == KS && f.ki == KI) kernel = (const void*)epl_kernel<FMT, N, kW, KM, 1, KS, KI>;
+        SDR_EPL_ROWS_HEADLINE(SDR_ROW)
+#undef SDR_ROW
+        if (!kernel) kernel = sdr_epl_straight_kernel(NT, f.km, f.ks, f.ki);
+    } else if (f.km2) {                  // 15.x or 16.x samples per chip, epoch by epoch
+        if constexpr (FMT == SDR_FMT_CI8 && NT == 3) kernel = (const void*)epl_kernel<FMT, NT, kChipMax, 15, 1, 0, 0, 16>;
+    } else if (f.w == kChipMax) {        // chip-aligned, tap positions at run time; 24: every epoch with 24 or 25 samples per chip
+        if (wpw == 4)                    // (... and its form with taps whole (half-)chips apart: configs 4-5)
+            kernel = f.ki   ? (const void*)epl_kernel<FMT, NT, kW, 24, 4, 0, kOdd>
+                     : f.km ? (const void*)epl_kernel<FMT, NT, kW, 24, 4>
+                            : (const void*)epl_kernel<FMT, NT, kW, 0, 4>;
+        else
+            kernel = f.km ? (const void*)epl_kernel<FMT, NT, kW, 24> : (const void*)epl_kernel<FMT, NT, kW>;
+    } else if (wpw == 4) {
+        kernel = f.w == 16  ? (const void*)epl_kernel<FMT, NT, 16, 0, 4>
+                 : f.w == 8 ? (const void*)epl_kernel<FMT, NT, 8, 0, 4>
+                            : (const void*)epl_kernel<FMT, NT, 0, 0, 4>;
+    } else {
+        kernel = f.w == 16 ? (const void*)epl_kernel<FMT, NT, 16> : f.w == 8 ? (const void*)epl_kernel<FMT, NT, 8> : (const void*)epl_kernel<FMT, NT, 0>;
+    }
+    if (!kernel) return sdr_fail(SDR_ERR_STATE, "no E/P/L kernel is compiled for variant %d with %d taps", wide, NT);
     const int threads = kWaveThreads * wpw;
-    const size_t scratch = wide >= kChipMax ? (size_t)threads * chip_strip_slots<NT>() + wpw * kChipRotSlots
-                                            : (wide ? (size_t)threads * kPrefixSlots : 0);
+    const size_t scratch = f.w == kChipMax ? (size_t)threads * chip_strip_slots<NT>() + wpw * kChipRotSlots
+                                           : (f.w ? (size_t)threads * kPrefixSlots : 0);
     size_t shmem = (size_t)(wpw * 2 * NT) * sizeof(double) + (size_t)((lut_words + 3) & ~3) * sizeof(uint32_t) +
                    scratch * sizeof(double2);
-    const int stride = wpw > 1 ? group_stride : 1;
+    int stride = wpw > 1 ? group_stride : 1;
     const int grid = wpw > 1 ? (int)(((int64_t)n_items + (int64_t)wpw * stride - 1) / ((int64_t)wpw * stride)) * stride : n_items;
-    auto launch = [&](auto kernel) {
-        if (shmem > 64u * 1024u)  // beyond the default dynamic-LDS grant (long multi-period replicas)
-            (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), shmem, stream, e->iq, (const void*)e->iq, e->iq_capacity, d_items, n_items, stride,
-                           doubled ? e->luts2 : e->luts, lut_words, doubled ? e->lut2_stride : e->lut_stride, d_spacing, fs, tap0,
-                           n_taps_total, d_out, d_setups, xcd_run);
-    };
-    constexpr bool kOdd = NT == 3 || NT == 5;               // (the compile-time tap geometries exist for these)
-    // (the straight-line kernels read the plan's per-item setups: without them the run-time-position kernel serves the list)
-    const bool ki = (wide & kVariantKI) != 0 && FMT == SDR_FMT_CI8 && kOdd && d_setups != nullptr;
-    const int ks_of = FMT == SDR_FMT_CI8 && NT == 3 && d_setups != nullptr ? (wide & kVariantKSMask) / 256 : 0;
-    const bool ks = ks_of != 0;
-    wide &= 255;
-    if (wpw == 4) {
-        if (ki && wide == kChipMax + 24)                     // taps whole (half-)chips apart: configs 4-5
-            launch(epl_kernel<FMT, NT, (FMT == SDR_FMT_CI8 ? kChipMax : 16), 24, 4, 0, (kOdd ? 1 : 0)>);
-        else if (wide == kChipMax + 24 && FMT == SDR_FMT_CI8)     // (every epoch with 24 or 25 samples per chip: BOC(1,1) half-chips at 50 MHz)
-            launch(epl_kernel<FMT, NT, (FMT == SDR_FMT_CI8 ? kChipMax : 16), 24, 4>);
-        else if (wide >= kChipMax && FMT == SDR_FMT_CI8)
-            launch(epl_kernel<FMT, NT, (FMT == SDR_FMT_CI8 ? kChipMax : 16), 0, 4>);
-        else if (wide == 16)
-            launch(epl_kernel<FMT, NT, 16, 0, 4>);
-        else if (wide == 8)
-            launch(epl_kernel<FMT, NT, 8, 0, 4>);
-        else
-            launch(epl_kernel<FMT, NT, 0, 0, 4>);
-        return;
-    }
-    // the straight-line kernels of the other block lengths (ci8, three taps) live in epl_straight.hip: launched through their address
-    auto launch_by_address = [&](const void* kernel) {
-        const void* ring = e->iq;
-        const void* flipped = (const void*)e->iq;
-        int64_t cap = e->iq_capacity;
-        int n = n_items, gs = stride, lw = lut_words, ls = doubled ? e->lut2_stride : e->lut_stride, t0 = tap0, nt = n_taps_total;
-        const uint32_t* luts = doubled ? e->luts2 : e->luts;
-        int xr = xcd_run;
-        void* args[] = {&ring, &flipped, &cap, &d_items, &n, &gs, &luts, &lw, &ls, &d_spacing, &fs, &t0, &nt, &d_out, &d_setups, &xr};
-        if (shmem > 64u * 1024u) (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        (void)hipLaunchKernel(kernel, dim3(grid), dim3(threads), args, shmem, stream);
-    };
-    const int km = wide - kChipMax;
-    const void* elsewhere = (ks && km != 24 && km != 19)                    ? sdr_epl_ks_kernel(km)
-                            : (ki && NT == 3 && km != 24 && km != 15)       ? sdr_epl_ki_kernel(km)
-                            : (ki && NT == 5 && km != 24)                   ? sdr_epl_ki5_kernel(km)
-                            : (!ks && !ki && FMT == SDR_FMT_CI8 && NT == 3 && km >= 17 && km != 24) ? sdr_epl_km_kernel(km)
-                                                                            : nullptr;
-    if (elsewhere)
-        launch_by_address(elsewhere);
-    else if (ks && ks_of == 9)                               // 19 / 20 samples per chip, the outer taps switching at sample 9 or 10
-        launch(epl_kernel<FMT, NT, (FMT == SDR_FMT_CI8 ? kChipMax : 16), (NT == 3 ? 19 : 0), 1, (NT == 3 ? 9 : 0)>);
-    else if (ks)                                             // 24 / 25 samples per chip, both outer taps switching at sample 12 or 13
-        launch(epl_kernel<FMT, NT, (FMT == SDR_FMT_CI8 ? kChipMax : 16), 24, 1, (NT == 3 ? 12 : 0)>);
-    else if (ki && wide == kChipMax + 15)                    // 15 / 16 samples per half chip (31-32.7 MHz on the half-chip view)
-        launch(epl_kernel<FMT, NT, (FMT == SDR_FMT_CI8 ? kChipMax : 16), (NT == 3 ? 15 : 24), 1, 0, (kOdd ? 1 : 0)>);
-    else if (ki)
-        launch(epl_kernel<FMT, NT, (FMT == SDR_FMT_CI8 ? kChipMax : 16), 24, 1, 0, (kOdd ? 1 : 0)>);
-    else if (wide == kChipMax + 24 && FMT == SDR_FMT_CI8)   // chip-aligned, every epoch with 24 or 25 samples per chip
-        launch(epl_kernel<FMT, NT, (FMT == SDR_FMT_CI8 ? kChipMax : 16), 24>);
-    else if (wide == kChipMax + kVariantKM1516 && FMT == SDR_FMT_CI8 && NT == 3) {   // 15.x or 16.x samples per chip, epoch by epoch
-        if constexpr (FMT == SDR_FMT_CI8 && NT == 3) launch(epl_kernel<FMT, NT, kChipMax, 15, 1, 0, 0, 16>);
-    }
-    else if (wide >= kChipMax && FMT == SDR_FMT_CI8)
-        launch(epl_kernel<FMT, NT, (FMT == SDR_FMT_CI8 ? kChipMax : 16)>);
-    else if (wide == 16)
-        launch(epl_kernel<FMT, NT, 16>);
-    else if (wide == 8)
-        launch(epl_kernel<FMT, NT, 8>);
-    else
-        launch(epl_kernel<FMT, NT, 0>);
+    const void* ring = e->iq;
+    const void* flipped = (const void*)e->iq;
+    int64_t cap = e->iq_capacity;
+    int lut_stride = doubled ? e->lut2_stride : e->lut_stride;
+    const uint32_t* luts = doubled ? e->luts2 : e->luts;
+    void* args[] = {&ring, &flipped, &cap, &d_items, &n_items, &stride, &luts, &lut_words, &lut_stride, &d_spacing, &fs, &tap0,
+                    &n_taps_total, &d_out, &d_setups, &xcd_run};
+    if (shmem > 64u * 1024u)  // beyond the default dynamic-LDS grant (long multi-period replicas)
+        (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+    (void)hipLaunchKernel(kernel, dim3(grid), dim3(threads), args, shmem, stream);
+    return SDR_OK;
 }
 
 template <int FMT>
-void launch_fmt(sdr_engine* e, hipStream_t stream, const sdr_epl_item* d_items, int n_items, const double* d_spacing, double fs,
-                int n_taps, int lut_words, int wide, int group_stride, bool doubled, double* d_out, const void* d_setups, int xcd_run) {
+int launch_fmt(sdr_engine* e, hipStream_t stream, const sdr_epl_item* d_items, int n_items, const double* d_spacing, double fs,
+               int n_taps, int lut_words, int wide, int group_stride, bool doubled, double* d_out, const void* d_setups, int xcd_run) {
     // Taps are served in register-resident chunks of 5/3/2/1.
-    int t0 = 0;
-    while (t0 < n_taps) {
-        int left = n_taps - t0;
-        if (left >= 5) {
-            launch_one<FMT, 5>(e, stream, d_items, n_items, d_spacing, fs, t0, n_taps, lut_words, wide, group_stride, doubled, d_out, d_setups, xcd_run);
-            t0 += 5;
-        } else if (left >= 3) {
-            launch_one<FMT, 3>(e, stream, d_items, n_items, d_spacing, fs, t0, n_taps, lut_words, wide, group_stride, doubled, d_out, d_setups, xcd_run);
-            t0 += 3;
-        } else if (left == 2) {
-            launch_one<FMT, 2>(e, stream, d_items, n_items, d_spacing, fs, t0, n_taps, lut_words, wide, group_stride, doubled, d_out, d_setups, xcd_run);
-            t0 += 2;
-        } else {
-            launch_one<FMT, 1>(e, stream, d_items, n_items, d_spacing, fs, t0, n_taps, lut_words, wide, group_stride, doubled, d_out, d_setups, xcd_run);
-            t0 += 1;
-        }
+    for (int t0 = 0; t0 < n_taps;) {
+        const int left = n_taps - t0, nt = left >= 5 ? 5 : (left >= 3 ? 3 : left);
+        auto chunk = [&](auto launch) { return launch(e, stream, d_items, n_items, d_spacing, fs, t0, n_taps, lut_words, wide, group_stride, doubled, d_out, d_setups, xcd_run); };
+        const int rc = nt == 5 ? chunk(launch_one<FMT, 5>) : nt == 3 ? chunk(launch_one<FMT, 3>) : nt == 2 ? chunk(launch_one<FMT, 2>) : chunk(launch_one<FMT, 1>);
+        if (rc) return rc;
+        t0 += nt;
     }
+    return SDR_OK;
 }
 
 }  // namespace
@@ -299,6 +264,97 @@ __global__ __launch_bounds__(256) void chipn_setup_kernel(const sdr_epl_item* __
     if (!sdr::chipn_setup<P...>(it.n_samples, it.start_sample, capacity, it.carrier_hz, it.rem_code, it.code_step, sp, fs, S))
         atomicAdd(missed, 1);
     out[i] = S;
+}
+
+// What plan creation needs of a straight-line form with per-item setups -- a row of SDR_EPL_ROWS_* (epl_variant.h) with KS or
+// KI: the size of its ChipSetup<NT>, the setups of a short list on the host (sdr_epl_batch, one call per EPL(): the same
+// function, ~2 us per item, instead of a launch), those of a long one in one launch.
+struct RowSetups {
+    size_t bytes;
+    void (*on_host)(const sdr_epl_item* items, int n_items, const double* spacing, double fs, int64_t capacity, void* out);
+    void (*on_device)(hipStream_t stream, const sdr_epl_item* d_items, int n_items, const double* d_spacing, double fs, int64_t capacity,
+                      void* d_out);
+};
+template <int NT, int KM, int KS, int KI>
+struct RowSetupsOf {
+    static void on_host(const sdr_epl_item* items, int n_items, const double* spacing, double fs, int64_t capacity, void* out) {
+        sdr::ChipSetup<NT>* const S = static_cast<sdr::ChipSetup<NT>*>(out);
+        for (int i = 0; i < n_items; ++i) {
+            const sdr_epl_item& it = items[i];
+            sdr::chip_setup<NT, KM, KS, KI>(it.n_samples, it.start_sample, capacity, it.carrier_hz, it.rem_code, it.code_step, spacing, fs,
+                                            kWaveThreads, S[i]);
+        }
+    }
+    static void on_device(hipStream_t stream, const sdr_epl_item* d_items, int n_items, const double* d_spacing, double fs, int64_t capacity,
+                          void* d_out) {
+        hipLaunchKernelGGL((chip_setup_kernel<NT, KM, KS, KI>), dim3((unsigned)((n_items + 63) / 64)), dim3(64), 0, stream, d_items, n_items,
+                           d_spacing, fs, capacity, static_cast<sdr::ChipSetup<NT>*>(d_out));      // (a wave per 64 items)
+    }
+    static const RowSetups* get() {
+        if constexpr (KS != 0 || KI != 0) {
+            static const RowSetups ops = {sizeof(sdr::ChipSetup<NT>), &on_host, &on_device};
+            return &ops;
+        } else {
+            return nullptr;      // (the block length alone: tap positions at run time)
+        }
+    }
+};
+static const RowSetups* row_setups(const EplForm& f) {
+#define SDR_ROW(NT, KM, KS, KI) \
+    if (f.nt == NT && f.km == KM && f.ks == KS && f.ki == KI) return RowSetupsOf<NT, KM, KS, KI>::get();
+    SDR_EPL_ROWS_HEADLINE(SDR_ROW)
+    SDR_EPL_ROWS_STRAIGHT(SDR_ROW)
+#undef SDR_ROW
+    return nullptr;
+}
+
+// The same of a several-chips-per-lane shape (SDR_EPL_CHIPN_SHAPES), and the launch of its kernel.  on_host returns, on_device
+// leaves in *d_missed, the number of items the scheme does not cover.
+struct ShapeOps {
+    size_t bytes;
+    int (*on_host)(const sdr_epl_item* items, int n_items, const double* spacing, double fs, int64_t capacity, void* out);
+    void (*on_device)(hipStream_t stream, const sdr_epl_item* d_items, int n_items, const double* d_spacing, double fs, int64_t capacity,
+                      void* d_out, int* d_missed);
+    void (*launch)(hipStream_t stream, size_t shmem, const void* ring, int64_t capacity, const sdr_epl_item* d_items, int n_items,
+                   const uint32_t* luts, int lut_words, int lut_stride, const double* d_spacing, double fs, double* d_out,
+                   const void* d_setups, int xcd_run);
+};
+template <int... P>
+struct ShapeOpsOf {
+    using Setup = sdr::ChipNSetup<P...>;
+    static int on_host(const sdr_epl_item* items, int n_items, const double* spacing, double fs, int64_t capacity, void* out) {
+        int missed = 0;
+        for (int i = 0; i < n_items; ++i) {
+            const sdr_epl_item& it = items[i];
+            missed += sdr::chipn_setup<P...>(it.n_samples, it.start_sample, capacity, it.carrier_hz, it.rem_code, it.code_step, spacing, fs,
+                                             static_cast<Setup*>(out)[i]) ? 0 : 1;
+        }
+        return missed;
+    }
+    static void on_device(hipStream_t stream, const sdr_epl_item* d_items, int n_items, const double* d_spacing, double fs, int64_t capacity,
+                          void* d_out, int* d_missed) {
+        hipLaunchKernelGGL((chipn_setup_kernel<P...>), dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, stream, d_items, n_items,
+                           d_spacing, fs, capacity, static_cast<Setup*>(d_out), d_missed);
+    }
+    static void launch(hipStream_t stream, size_t shmem, const void* ring, int64_t capacity, const sdr_epl_item* d_items, int n_items,
+                       const uint32_t* luts, int lut_words, int lut_stride, const double* d_spacing, double fs, double* d_out,
+                       const void* d_setups, int xcd_run) {
+        hipLaunchKernelGGL((epl2_kernel<P...>), dim3(n_items), dim3(kWaveThreads), shmem, stream, ring, ring, capacity, d_items, n_items, luts,
+                           lut_words, lut_stride, d_spacing, fs, d_out, static_cast<const Setup*>(d_setups), xcd_run);
+    }
+    static const ShapeOps* get() {
+        static const ShapeOps ops = {sizeof(Setup), &on_host, &on_device, &launch};
+        return &ops;
+    }
+};
+static const ShapeOps* chipn_shape(int shape) {
+    switch (shape) {
+#define SDR_SHAPE(S, ...) \
+    case S: return ShapeOpsOf<__VA_ARGS__>::get();
+        SDR_EPL_CHIPN_SHAPES(SDR_SHAPE)
+#undef SDR_SHAPE
+        default: return nullptr;
+    }
 }
 
 // ---- validation of a list: no item may index outside the ring or the staged replica, and what the list as a whole
@@ -422,46 +478,15 @@ static int item_error(const sdr_engine* e, const sdr_epl_item& it, int index, in
     }
 }
 
-// The kernel variant a list of these statistics gets (0: per sample; 8 / 16: boundary variants; kChipMax + ...: chip-aligned).
+// The kernel variant a list of these statistics gets (epl_variant.h: choose_variant).
 // m_lo / m_hi: the list's range of whole samples per chip; all_split: ItemStats::all_split.
 static int variant_of(const sdr_engine* e, const ItemRules& r, const double* spacing, double max_step, double min_step, int m_lo, int m_hi,
                       bool all_split) {
-    bool all_ki = r.n_taps == 3 || r.n_taps == 5;   // tap t exactly (t - A) chips from the anchor (KI kernel)
-    for (int t = 0; all_ki && t < r.n_taps; ++t) all_ki = r.scale * spacing[t] - r.s_anchor == (double)(t - r.n_taps / 2);
-    const bool all_m24 = m_lo == 24 && m_hi == 24;
-    const bool all_m15 = m_lo == 15 && m_hi == 15;                      // (31-32.7 MHz on the half-chip view: KM = 15, whole-chip taps)
-    const bool all_m1516 = m_lo >= 15 && m_hi <= 16 && r.n_taps == 3 && r.scale == 1.0;   // (16.368 MHz: 16.0 -- 15.x or 16.x by the Doppler's sign)
-    // one block length KM throughout, three taps: the straight-line kernels exist for KM = 16 .. 25 (epl.hip's own: 24 / 12,
-    // 19 / 9, the whole-chip-tap forms of 24 and 15; the rest: epl_straight.hip) -- with the outer taps' switch position
-    // floor(KM / 2) compiled in (+-0.5 chip, `all_split`) or with taps whole (half-)chips apart (`all_ki`)
-    const int km_one = m_lo == m_hi && m_lo >= 16 && m_lo <= 25 && r.n_taps == 3 ? m_lo : 0;
-    const bool boundary_ok = min_step >= sdr::kFastMinCodeStep && r.scale * e->lut_stride < sdr::kFastMaxLutWords;
-    int wide = !boundary_ok ? 0 : (max_step <= sdr::kFastMaxCodeStep ? 16 : (max_step <= sdr::kFastMaxCodeStep8 ? 8 : 0));
-    // every item inside the chip-aligned variant's range (ci8 ring): lanes own whole chips instead of 16 samples
-    // (the half-chip view only where a half chip holds 16 samples or more: at 31-32 MHz -- 15.6 per half chip -- the
-    // 16-sample boundary groups of the plain list were measured faster, 0.47 against 0.37 of the roof)
-    // ... unless every half chip holds 15.x samples and the taps sit whole half-chips apart: the KM = 15 whole-chip-tap kernel
-    const double chip_max_step = r.scale == 2.0 && !(all_m15 && all_ki && r.n_taps == 3 && !e->epl_no_split) ? 1.0 / 16.0 : sdr::kChipMaxCodeStep;
-    if (boundary_ok && e->iq_fmt == SDR_FMT_CI8 && min_step >= sdr::kChipMinCodeStep && max_step <= chip_max_step &&
-        !e->epl_no_chip) {
-        wide = sdr::kChipMax;
-        const int km5 = m_lo == m_hi && m_lo >= 16 && m_lo <= 25 && r.n_taps == 5 ? m_lo : 0;
-        if (km5 && all_ki && !e->epl_no_split)              // five taps whole (half-)chips apart
-            wide += km5 + kVariantKI;
-        else if (all_m24 && r.n_taps != 3)                  // (other tap counts: the 24 / 25 form with run-time positions alone)
-            wide += 24;
-        else if (km_one && all_split && !e->epl_no_split)
-            wide += km_one + 256 * (km_one / 2);
-        else if (km_one && all_ki && !e->epl_no_split)
-            wide += km_one + kVariantKI;
-        else if (all_m24 || (km_one >= 17 && !e->epl_no_split))   // block length compiled in, tap positions at run time
-            wide += all_m24 ? 24 : km_one;
-        else if (all_m15 && all_ki && r.n_taps == 3 && r.scale == 2.0 && !e->epl_no_split)
-            wide += 15 + kVariantKI;
-        else if (all_m1516 && !e->epl_no_split)
-            wide += kVariantKM1516;
-    }
-    return wide;
+    VariantInputs v = {};
+    v.n_taps = r.n_taps, v.scale = r.scale, v.s_anchor = r.s_anchor, v.spacing = spacing;
+    v.max_step = max_step, v.min_step = min_step, v.m_lo = m_lo, v.m_hi = m_hi, v.all_split = all_split;
+    v.iq_fmt = e->iq_fmt, v.lut_stride = e->lut_stride, v.no_chip = e->epl_no_chip, v.no_split = e->epl_no_split;
+    return choose_variant(v);
 }
 
 // Host walk (short lists; and the one bad item of a long list, for its message: index0 = its place in the list).
@@ -486,15 +511,15 @@ static int validate_items(sdr_engine* e, const sdr_epl_item* items, int n_items,
         if (step < min_step) min_step = step;
         if (ml > maxlen) maxlen = ml;
     }
-    *lut_words = maxlen + SDR_LUT_PAD + 2;
+    if (lut_words) *lut_words = maxlen + SDR_LUT_PAD + 2;
     *wide = variant_of(e, r, spacing, max_step, min_step, m_lo, m_hi, all_split);
     return SDR_OK;
 }
 
 // The same for a list that is already on the device (long lists: behind their upload).  ok2: the half-chip view's rules
-// were met as well (lw2 / wide2 then hold its answers).
+// were met as well (wide2 then holds its answer).
 static int validate_items_dev(sdr_engine* e, const sdr_epl_item* d_items, const sdr_epl_item* h_items, int n_items,
-                              const double* spacing, int n_taps, int* lut_words, int* wide, bool* ok2, int* lw2, int* wide2) {
+                              const double* spacing, int n_taps, int* lut_words, int* wide, bool* ok2, int* wide2) {
     const ItemRules r1 = item_rules(e, spacing, n_taps, 1.0), r2 = item_rules(e, spacing, n_taps, 2.0);
     if (int rc = sdr_devbuf_reserve(e, &e->ws_stats, 2 * sizeof(ItemStats))) return rc;
     if (int rc = sdr_pinned_reserve(e, &e->ctx0, 2 * sizeof(ItemStats))) return rc;
@@ -515,19 +540,17 @@ static int validate_items_dev(sdr_engine* e, const sdr_epl_item* d_items, const 
         sdr_epl_item it;
         if (h_items) it = h_items[i];
         else SDR_HIP(hipMemcpy(&it, d_items + i, sizeof(it), hipMemcpyDeviceToHost));
-        int lw, wd;
-        const int rc = validate_items(e, &it, 1, spacing, n_taps, 1.0, &lw, &wd, i);   // (the message, from the host's own walk of that item)
+        int wd;
+        const int rc = validate_items(e, &it, 1, spacing, n_taps, 1.0, nullptr, &wd, i);   // (the message, from the host's own walk of that item)
         return rc ? rc : sdr_fail(SDR_ERR_INVALID, "item %d: rejected by the device check", i);
     }
     *lut_words = host[0].maxlen + SDR_LUT_PAD + 2;
     *wide = variant_of(e, r1, spacing, as_double(host[0].max_step_bits), as_double(host[0].min_step_bits), host[0].m_lo, host[0].m_hi,
                        host[0].all_split != 0);
     *ok2 = host[1].first_bad == 0x7fffffff;
-    if (*ok2) {
-        *lw2 = host[1].maxlen + SDR_LUT_PAD + 2;
+    if (*ok2)
         *wide2 = variant_of(e, r2, spacing, as_double(host[1].max_step_bits), as_double(host[1].min_step_bits), host[1].m_lo, host[1].m_hi,
                             host[1].all_split != 0);
-    }
     return SDR_OK;
 }
 
@@ -616,23 +639,24 @@ static int plan_create_impl(sdr_engine* e, const sdr_epl_item* items, const sdr_
     // a list that misses the chip-aligned correlator only because a chip holds too many samples (32-52: GPS L1 C/A at
     // 50 MHz) runs on the half-chip view of its replicas
     bool doubled = false;
-    auto consider_half_chip_view = [&](bool ok2, int lw2, int wide2) -> int {
-        if (wide < sdr::kChipMax && e->iq_fmt == SDR_FMT_CI8 && !e->epl_no_chip && !e->epl_no_double && ok2 && wide2 >= sdr::kChipMax) {
+    auto half_chip_view_allowed = [&] {
+        return !variant_chip_aligned(wide) && e->iq_fmt == SDR_FMT_CI8 && !e->epl_no_chip && !e->epl_no_double;
+    };
+    auto consider_half_chip_view = [&](bool ok2, int wide2) -> int {
+        if (half_chip_view_allowed() && ok2 && variant_chip_aligned(wide2)) {
             if (int rc = ensure_doubled_luts(e, e->stream)) return rc;
             doubled = true;
             wide = wide2;
             lut_words = 2 * lut_words < e->lut2_stride ? 2 * lut_words : e->lut2_stride;
-            (void)lw2;
         }
         return SDR_OK;
     };
     if (!long_list) {
         if (int rc = validate_items(e, items, n_items, spacing, n_taps, 1.0, &lut_words, &wide)) return rc;
-        int lw2 = 0, wide2 = 0;
+        int wide2 = 0;
         bool ok2 = false;
-        if (wide < sdr::kChipMax && e->iq_fmt == SDR_FMT_CI8 && !e->epl_no_chip && !e->epl_no_double)
-            ok2 = validate_items(e, items, n_items, spacing, n_taps, 2.0, &lw2, &wide2) == SDR_OK;
-        if (int rc = consider_half_chip_view(ok2, lw2, wide2)) return rc;
+        if (half_chip_view_allowed()) ok2 = validate_items(e, items, n_items, spacing, n_taps, 2.0, nullptr, &wide2) == SDR_OK;
+        if (int rc = consider_half_chip_view(ok2, wide2)) return rc;
     }
     const double t_valid = now();
 
@@ -666,10 +690,10 @@ static int plan_create_impl(sdr_engine* e, const sdr_epl_item* items, const sdr_
         err = hipMemcpyAsync(p->d_items, d_src ? d_src : items, (size_t)n_items * sizeof(sdr_epl_item),
                              d_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, e->stream);
     if (err == hipSuccess && long_list) {
-        int lw2 = 0, wide2 = 0;
+        int wide2 = 0;
         bool ok2 = false;
-        int rc = validate_items_dev(e, p->d_items, items, n_items, spacing, n_taps, &lut_words, &wide, &ok2, &lw2, &wide2);
-        if (!rc) rc = consider_half_chip_view(ok2, lw2, wide2);
+        int rc = validate_items_dev(e, p->d_items, items, n_items, spacing, n_taps, &lut_words, &wide, &ok2, &wide2);
+        if (!rc) rc = consider_half_chip_view(ok2, wide2);
         if (rc) {
             sdr_epl_plan_destroy(e, p);
             return rc;
@@ -722,70 +746,19 @@ static int plan_create_impl(sdr_engine* e, const sdr_epl_item* items, const sdr_
             err = plan_take(e, (void**)&p->d_setups, bytes + 64, &p->bytes_setups);     // (+ the counter of items a scheme does not cover)
         }
     };
-    const unsigned setup_grid = (unsigned)((n_items + 255) / 256);       // (the two-chips-per-lane setups: 256 items per block)
-    const unsigned setup_grid64 = (unsigned)((n_items + 63) / 64);        // (the one-chip-per-lane setups: a wave per 64 items)
-    if (err == hipSuccess && e->iq_fmt == SDR_FMT_CI8 && (wide & 255) >= kChipMax && (wide & (kVariantKSMask | kVariantKI)) &&
-        (n_taps == 3 || n_taps == 5)) {
-        reserve_setups(n_taps == 3 ? sizeof(sdr::ChipSetup<3>) : sizeof(sdr::ChipSetup<5>));
+    // (setups exist for lists of three or five taps, served as one chunk; `true`: whether a plan of this word is to hold them)
+    const EplForm form = decode(wide, e->iq_fmt, n_taps, 1, true);
+    if (err == hipSuccess && form.setups) {
+        const RowSetups* const row = row_setups(form);
+        if (!row) err = hipErrorInvalidValue;     // (a word whose tuple is no row of the lists)
+        else reserve_setups(row->bytes);
         if (err == hipSuccess && !long_list) {
-            // a short list (sdr_epl_batch: one call per EPL()): the same function on the host, ~2 us per item, instead of a launch
-            const sdr_epl_item* src = doubled ? items2.data() : items;
-            const double* spc = doubled ? spacing2 : spacing;
             host_setups.resize(p->setup_bytes * (size_t)n_items);
-            const int km = (wide & 255) - kChipMax;
-            const bool ks = (wide & kVariantKSMask) != 0;
-            for (int i = 0; i < n_items; ++i) {
-                const sdr_epl_item& it = src[i];
-                if (n_taps == 5) {
-                    sdr::ChipSetup<5>& S5 = reinterpret_cast<sdr::ChipSetup<5>*>(host_setups.data())[i];
-                    switch (km) {
-#define SDR_SETUP5_CASE(K) \
-    case K: sdr::chip_setup<5, K, 0, 1>(it.n_samples, it.start_sample, e->iq_capacity, it.carrier_hz, it.rem_code, it.code_step, spc, fs, kWaveThreads, S5); break;
-                        SDR_SETUP5_CASE(16) SDR_SETUP5_CASE(17) SDR_SETUP5_CASE(18) SDR_SETUP5_CASE(19) SDR_SETUP5_CASE(20) SDR_SETUP5_CASE(21)
-                        SDR_SETUP5_CASE(22) SDR_SETUP5_CASE(23) SDR_SETUP5_CASE(24) SDR_SETUP5_CASE(25)
-#undef SDR_SETUP5_CASE
-                        default: err = hipErrorInvalidValue; break;
-                    }
-                    continue;
-                }
-                sdr::ChipSetup<3>& S = reinterpret_cast<sdr::ChipSetup<3>*>(host_setups.data())[i];
-                switch (km * 2 + (ks ? 1 : 0)) {
-#define SDR_SETUP_CASE(K)                                                                                                                      \
-    case 2 * K + 1: sdr::chip_setup<3, K, K / 2, 0>(it.n_samples, it.start_sample, e->iq_capacity, it.carrier_hz, it.rem_code, it.code_step, spc, fs, kWaveThreads, S); break; \
-    case 2 * K: sdr::chip_setup<3, K, 0, 1>(it.n_samples, it.start_sample, e->iq_capacity, it.carrier_hz, it.rem_code, it.code_step, spc, fs, kWaveThreads, S); break;
-                    SDR_SETUP_CASE(15) SDR_SETUP_CASE(16) SDR_SETUP_CASE(17) SDR_SETUP_CASE(18) SDR_SETUP_CASE(19) SDR_SETUP_CASE(20)
-                    SDR_SETUP_CASE(21) SDR_SETUP_CASE(22) SDR_SETUP_CASE(23) SDR_SETUP_CASE(24) SDR_SETUP_CASE(25)
-#undef SDR_SETUP_CASE
-                    default: err = hipErrorInvalidValue; break;
-                }
-            }
-            if (err == hipSuccess) err = hipMemcpyAsync(p->d_setups, host_setups.data(), host_setups.size(), hipMemcpyHostToDevice, e->stream);
+            row->on_host(doubled ? items2.data() : items, n_items, doubled ? spacing2 : spacing, fs, e->iq_capacity, host_setups.data());
+            err = hipMemcpyAsync(p->d_setups, host_setups.data(), host_setups.size(), hipMemcpyHostToDevice, e->stream);
         } else if (err == hipSuccess) {
-            const int km = (wide & 255) - kChipMax;
-            const bool ks = (wide & kVariantKSMask) != 0;
-            if (n_taps == 5) {
-                sdr::ChipSetup<5>* d5 = reinterpret_cast<sdr::ChipSetup<5>*>(p->d_setups);
-                switch (km) {
-#define SDR_SETUP5_CASE(K) \
-    case K: hipLaunchKernelGGL((chip_setup_kernel<5, K, 0, 1>), dim3(setup_grid64), dim3(64), 0, e->stream, p->d_items, n_items, p->d_spacing, fs, e->iq_capacity, d5); break;
-                    SDR_SETUP5_CASE(16) SDR_SETUP5_CASE(17) SDR_SETUP5_CASE(18) SDR_SETUP5_CASE(19) SDR_SETUP5_CASE(20) SDR_SETUP5_CASE(21)
-                    SDR_SETUP5_CASE(22) SDR_SETUP5_CASE(23) SDR_SETUP5_CASE(24) SDR_SETUP5_CASE(25)
-#undef SDR_SETUP5_CASE
-                    default: err = hipErrorInvalidValue; break;
-                }
-            } else {
-                sdr::ChipSetup<3>* d3 = reinterpret_cast<sdr::ChipSetup<3>*>(p->d_setups);
-                switch (km * 2 + (ks ? 1 : 0)) {
-#define SDR_SETUP_CASE(K)                                                                                                              \
-    case 2 * K + 1: hipLaunchKernelGGL((chip_setup_kernel<3, K, K / 2, 0>), dim3(setup_grid64), dim3(64), 0, e->stream, p->d_items, n_items, p->d_spacing, fs, e->iq_capacity, d3); break; \
-    case 2 * K: hipLaunchKernelGGL((chip_setup_kernel<3, K, 0, 1>), dim3(setup_grid64), dim3(64), 0, e->stream, p->d_items, n_items, p->d_spacing, fs, e->iq_capacity, d3); break;
-                    SDR_SETUP_CASE(15) SDR_SETUP_CASE(16) SDR_SETUP_CASE(17) SDR_SETUP_CASE(18) SDR_SETUP_CASE(19) SDR_SETUP_CASE(20)
-                    SDR_SETUP_CASE(21) SDR_SETUP_CASE(22) SDR_SETUP_CASE(23) SDR_SETUP_CASE(24) SDR_SETUP_CASE(25)
-#undef SDR_SETUP_CASE
-                    default: err = hipErrorInvalidValue; break;
-                }
-            }
-            if (err == hipSuccess) err = hipGetLastError();
+            row->on_device(e->stream, p->d_items, n_items, p->d_spacing, fs, e->iq_capacity, p->d_setups);
+            err = hipGetLastError();
         }
     }
     // three taps half a chip apart and chips of 9.5 .. 10 or 11.5 .. 12 samples (the reference's shipped 10 MHz; 12 MHz): two
@@ -795,7 +768,7 @@ static int plan_create_impl(sdr_engine* e, const sdr_epl_item* items, const sdr_
     // spill 27 registers at three waves per SIMD: 0.44 instead of 0.57 of the roof.  Neither is instantiated.)
     // ... and chips of 3.75 .. 4 samples (the reference's 4 MHz, BASELINE configs[0]): FOUR chips per lane, where the list
     // would otherwise go per sample (round 6)
-    if (err == hipSuccess && e->iq_fmt == SDR_FMT_CI8 && n_taps == 3 && !doubled && !e->epl_no_chip2 && ((wide & 255) == 8 || (wide & 255) == 0) &&
+    if (err == hipSuccess && e->iq_fmt == SDR_FMT_CI8 && n_taps == 3 && !doubled && !e->epl_no_chip2 && (form.w == 8 || form.w == 0) &&
         lut_words < kLongLutWords) {          // (long multi-period replicas keep the four-epochs-per-workgroup kernels)
         sdr_epl_item first = {};
         if (items) first = items[0];
@@ -803,53 +776,29 @@ static int plan_create_impl(sdr_engine* e, const sdr_epl_item* items, const sdr_
         const double two_chips = err == hipSuccess ? std::floor(2.0 / first.code_step) : 0.0;   // samples in two chips (any positive step got here)
         const double four_chips = err == hipSuccess ? std::floor(4.0 / first.code_step) : 0.0;
         const bool half_apart = spacing[0] == -0.5 && spacing[1] == 0.0 && spacing[2] == 0.5;
-        const int shape = (wide & 255) == 8 ? (two_chips == 19.0 ? 1 : (two_chips == 23.0 ? 2 : 0)) : (four_chips == 15.0 && half_apart ? 3 : 0);
-        if (shape) {
-            reserve_setups(shape == 1 ? sizeof(sdr::ChipNSetup<4, 9, 14, 19>) : shape == 2 ? sizeof(sdr::ChipNSetup<5, 11, 17, 23>)
-                                                                                           : sizeof(sdr::ChipNSetup<1, 3, 5, 7, 9, 11, 13, 15>));
+        const int shape = form.w == 8 ? (two_chips == 19.0 ? 1 : (two_chips == 23.0 ? 2 : 0)) : (four_chips == 15.0 && half_apart ? 3 : 0);
+        if (const ShapeOps* const ops = chipn_shape(shape)) {
+            reserve_setups(ops->bytes);
             int* d_missed = p->d_setups ? reinterpret_cast<int*>(p->d_setups + p->setup_bytes * (size_t)n_items) : nullptr;
             int missed = n_items;
             if (err == hipSuccess && !long_list) {
-                // a short list (sdr_epl_batch: one call per EPL()): the same function on the host, ~2 us per item, instead of a
-                // launch and a round trip for the count -- the call is latency, not throughput
+                // a short list (sdr_epl_batch: one call per EPL()): on the host, instead of a launch and a round trip for the
+                // count -- the call is latency, not throughput
                 host_setups.resize(p->setup_bytes * (size_t)n_items);
-                missed = 0;
-                for (int i = 0; i < n_items; ++i) {
-                    const sdr_epl_item& it = items[i];
-                    const bool ok = shape == 1
-                        ? sdr::chipn_setup<4, 9, 14, 19>(it.n_samples, it.start_sample, e->iq_capacity, it.carrier_hz, it.rem_code, it.code_step,
-                                                         spacing, fs, reinterpret_cast<sdr::ChipNSetup<4, 9, 14, 19>*>(host_setups.data())[i])
-                        : shape == 2
-                        ? sdr::chipn_setup<5, 11, 17, 23>(it.n_samples, it.start_sample, e->iq_capacity, it.carrier_hz, it.rem_code, it.code_step,
-                                                          spacing, fs, reinterpret_cast<sdr::ChipNSetup<5, 11, 17, 23>*>(host_setups.data())[i])
-                        : sdr::chipn_setup<1, 3, 5, 7, 9, 11, 13, 15>(it.n_samples, it.start_sample, e->iq_capacity, it.carrier_hz, it.rem_code, it.code_step,
-                                                                      spacing, fs, reinterpret_cast<sdr::ChipNSetup<1, 3, 5, 7, 9, 11, 13, 15>*>(host_setups.data())[i]);
-                    missed += ok ? 0 : 1;
-                }
+                missed = ops->on_host(items, n_items, spacing, fs, e->iq_capacity, host_setups.data());
                 if (missed <= n_items / 64)      // (host_setups lives until the synchronisation that ends the plan's creation)
                     err = hipMemcpyAsync(p->d_setups, host_setups.data(), host_setups.size(), hipMemcpyHostToDevice, e->stream);
             } else if (err == hipSuccess) {
-              err = hipMemsetAsync(d_missed, 0, sizeof(int), e->stream);
-              if (err == hipSuccess) {
-                if (shape == 1)
-                    hipLaunchKernelGGL((chipn_setup_kernel<4, 9, 14, 19>), dim3(setup_grid), dim3(256), 0, e->stream, p->d_items,
-                                       n_items, p->d_spacing, fs, e->iq_capacity,
-                                       reinterpret_cast<sdr::ChipNSetup<4, 9, 14, 19>*>(p->d_setups), d_missed);
-                else if (shape == 2)
-                    hipLaunchKernelGGL((chipn_setup_kernel<5, 11, 17, 23>), dim3(setup_grid), dim3(256), 0, e->stream, p->d_items,
-                                       n_items, p->d_spacing, fs, e->iq_capacity,
-                                       reinterpret_cast<sdr::ChipNSetup<5, 11, 17, 23>*>(p->d_setups), d_missed);
-                else
-                    hipLaunchKernelGGL((chipn_setup_kernel<1, 3, 5, 7, 9, 11, 13, 15>), dim3(setup_grid), dim3(256), 0, e->stream, p->d_items,
-                                       n_items, p->d_spacing, fs, e->iq_capacity,
-                                       reinterpret_cast<sdr::ChipNSetup<1, 3, 5, 7, 9, 11, 13, 15>*>(p->d_setups), d_missed);
-                err = hipGetLastError();
-              }
-              if (err == hipSuccess) err = hipMemcpyAsync(&missed, d_missed, sizeof(int), hipMemcpyDeviceToHost, e->stream);
-              if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+                err = hipMemsetAsync(d_missed, 0, sizeof(int), e->stream);
+                if (err == hipSuccess) {
+                    ops->on_device(e->stream, p->d_items, n_items, p->d_spacing, fs, e->iq_capacity, p->d_setups, d_missed);
+                    err = hipGetLastError();
+                }
+                if (err == hipSuccess) err = hipMemcpyAsync(&missed, d_missed, sizeof(int), hipMemcpyDeviceToHost, e->stream);
+                if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
             }
             if (err == hipSuccess && missed <= n_items / 64) {
-                p->wide = wide = (wide & 255) + kVariantC2 * shape;
+                p->wide = wide = variant_with_shape(wide, shape);
             } else if (err == hipSuccess) {                 // too many strays: the boundary variant serves the list
                 if (!use_workspaces && p->d_setups) plan_give(e, p->d_setups, p->bytes_setups);
                 p->d_setups = nullptr;
@@ -898,26 +847,22 @@ int sdr_epl_plan_run_range_on(sdr_engine* e, sdr_epl_plan* p, int64_t first, int
     const void* setups = p->d_setups ? p->d_setups + (size_t)first * p->setup_bytes : nullptr;
     // (the order in which the range's own workgroups, 0 .. count - 1, take its items: xcd_order.h; read when the plan runs)
     const int xcd_run = e->epl_xcd_run;
-    if (e->iq_fmt == SDR_FMT_CI8 && (p->wide & (3 * kVariantC2)) && setups) {      // two chips per lane: its own kernel
+    {
         hipStream_t st = ctx->stream;
         ProfScope ps(e, "epl_kernel", st);
-        const size_t shmem = 8 * sizeof(uint32_t) + (size_t)((p->lut_words + 3) & ~3) * sizeof(uint32_t);
-        const int shape = (p->wide / kVariantC2) & 3;
-        auto launch2 = [&](auto kernel, auto* typed) {
-            hipLaunchKernelGGL(kernel, dim3(n), dim3(kWaveThreads), shmem, st, e->iq, (const void*)e->iq, e->iq_capacity,
-                               items, n, e->luts, p->lut_words, e->lut_stride, p->d_spacing, p->fs, out, typed, xcd_run);
-        };
-        if (shape == 1) launch2(epl2_kernel<4, 9, 14, 19>, reinterpret_cast<const sdr::ChipNSetup<4, 9, 14, 19>*>(setups));
-        else if (shape == 2) launch2(epl2_kernel<5, 11, 17, 23>, reinterpret_cast<const sdr::ChipNSetup<5, 11, 17, 23>*>(setups));
-        else launch2(epl2_kernel<1, 3, 5, 7, 9, 11, 13, 15>, reinterpret_cast<const sdr::ChipNSetup<1, 3, 5, 7, 9, 11, 13, 15>*>(setups));
-    } else {
-        hipStream_t st = ctx->stream;
-        ProfScope ps(e, "epl_kernel", st);
-        switch (e->iq_fmt) {
-            case SDR_FMT_CI8: launch_fmt<SDR_FMT_CI8>(e, st, items, n, p->d_spacing, p->fs, p->n_taps, p->lut_words, p->wide, p->group_stride, p->doubled, out, setups, xcd_run); break;
-            case SDR_FMT_CI16: launch_fmt<SDR_FMT_CI16>(e, st, items, n, p->d_spacing, p->fs, p->n_taps, p->lut_words, p->wide, p->group_stride, p->doubled, out, setups, xcd_run); break;
-            case SDR_FMT_CF32: launch_fmt<SDR_FMT_CF32>(e, st, items, n, p->d_spacing, p->fs, p->n_taps, p->lut_words, p->wide, p->group_stride, p->doubled, out, setups, xcd_run); break;
-            default: launch_fmt<SDR_FMT_CF64>(e, st, items, n, p->d_spacing, p->fs, p->n_taps, p->lut_words, p->wide, p->group_stride, p->doubled, out, setups, xcd_run); break;
+        // (several chips per lane: a kernel of its own, three taps in one launch)
+        if (const ShapeOps* const ops = chipn_shape(decode(p->wide, e->iq_fmt, 3, 1, setups != nullptr).shape)) {
+            const size_t shmem = 8 * sizeof(uint32_t) + (size_t)((p->lut_words + 3) & ~3) * sizeof(uint32_t);
+            ops->launch(st, shmem, e->iq, e->iq_capacity, items, n, e->luts, p->lut_words, e->lut_stride, p->d_spacing, p->fs, out, setups, xcd_run);
+        } else {
+            int rc;
+            switch (e->iq_fmt) {
+                case SDR_FMT_CI8: rc = launch_fmt<SDR_FMT_CI8>(e, st, items, n, p->d_spacing, p->fs, p->n_taps, p->lut_words, p->wide, p->group_stride, p->doubled, out, setups, xcd_run); break;
+                case SDR_FMT_CI16: rc = launch_fmt<SDR_FMT_CI16>(e, st, items, n, p->d_spacing, p->fs, p->n_taps, p->lut_words, p->wide, p->group_stride, p->doubled, out, setups, xcd_run); break;
+                case SDR_FMT_CF32: rc = launch_fmt<SDR_FMT_CF32>(e, st, items, n, p->d_spacing, p->fs, p->n_taps, p->lut_words, p->wide, p->group_stride, p->doubled, out, setups, xcd_run); break;
+                default: rc = launch_fmt<SDR_FMT_CF64>(e, st, items, n, p->d_spacing, p->fs, p->n_taps, p->lut_words, p->wide, p->group_stride, p->doubled, out, setups, xcd_run); break;
+            }
+            if (rc) return rc;
         }
     }
     SDR_HIP(hipGetLastError());

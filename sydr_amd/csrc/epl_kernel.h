@@ -1,9 +1,10 @@
-// The E/P/L kernel template (K1) and the words of a plan's variant code: included by epl.hip, which instantiates the general
-// forms and the headline geometries, and by epl_straight.hip, which instantiates the straight-line forms of the other block
-// lengths (one translation unit each: they compile side by side).  Everything here has internal linkage.
+// The E/P/L kernel template (K1): included by epl.hip, which instantiates the general forms and the headline geometries, and
+// by epl_straight.hip, which instantiates the straight-line forms of the other block lengths (one translation unit each: they
+// compile side by side; epl_variant.h lists what each holds).  Everything here has internal linkage.
 #pragma once
 #include "correlator.h"
 #include "correlator_chip.h"
+#include "epl_variant.h"
 #include "xcd_order.h"
 
 namespace {
@@ -11,14 +12,11 @@ namespace {
 using namespace sdr;
 
 constexpr int kWaveThreads = 64;  // one wave per channel-epoch: the ~5 us fixed latency of a workgroup is amortised over 4x more work
-// plan variant word (sdr_epl_plan_variant): low byte = samples a lane owns (0 / 8 / 16 / 26, + 24 when the block length is
-// compiled in), then the compile-time tap geometry
-constexpr int kVariantKS12 = 256 * 12;   // three taps, the outer ones switching 12.x samples into the anchor's block (24 / 25 samples per chip)
-constexpr int kVariantKSMask = 256 * 15; // ... in general: KS in bits 8-11, with the block length KM in the low byte (kChipMax + KM)
-constexpr int kVariantKS9 = 256 * 9;     // 19 / 20 samples per chip (20 MHz): KM = 19, KS = 9
-constexpr int kVariantKM1516 = 16;       // (added to kChipMax) 15.x or 16.x samples per chip by the epoch: both block lengths compiled in
-constexpr int kVariantKI = 4096;         // taps whole (half-)chips apart: no switch inside a block
-constexpr int kVariantC2 = 8192;         // several chips per lane (correlator_chip2.h), x 1 / 2: boundaries <4,9,14,19> / <5,11,17,23>
+// (the words of a plan's variant code -- epl_variant.h, host arithmetic alone -- carry these limits under names of their own)
+static_assert(kVariantChip == kChipMax && kVariantFastMaxStep == kFastMaxCodeStep && kVariantFastMaxStep8 == kFastMaxCodeStep8 &&
+                  kVariantFastMinStep == kFastMinCodeStep && kVariantFastMaxLutWords == kFastMaxLutWords &&
+                  kVariantChipMinStep == kChipMinCodeStep && kVariantChipMaxStep == kChipMaxCodeStep,
+              "epl_variant.h restates the correlator cores' limits");
 constexpr int kLongLutWords = 4096;  // replicas of 16 KB and more (multi-period / BOC half-chip codes): four epochs share a staged copy
 
 // Dynamic LDS: [red: WPW*2*NT doubles][scratch: strips / rotations][lut: lut_words uint32]

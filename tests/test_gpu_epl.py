@@ -765,6 +765,44 @@ def test_long_lists_are_checked_on_the_device_like_short_ones_on_the_host(engine
         hip.hipFree(d)
 
 
+WHOLE3, WHOLE5 = (-1.0, 0.0, 1.0), (-2.0, -1.0, 0.0, 1.0, 2.0)
+
+
+# The rows of the tables of compiled forms (sydr_amd/csrc/epl_variant.h) that no other test of the E/P/L files takes through
+# both setup paths (found by logging plan.variant over those files): five taps whole chips apart at every block length,
+# three at 19, the block length 19 alone, and the shape <5,11,17,23> of the several-chips-per-lane kernel.
+@pytest.mark.parametrize("per_chip, spacing, want",
+                         [(km + 0.5, WHOLE5, 26 + km + 4096) for km in (16, 17, 18, 19, 20, 21, 22, 23, 24, 25)] +
+                         [(19.5, WHOLE3, 26 + 19 + 4096), (19.5, (-0.25, 0.0, 0.25), 26 + 19), (11.7, (-0.5, 0.0, 0.5), 8 + 2 * 8192)])
+def test_setups_by_the_launch_equal_setups_on_the_host(engine, per_chip, spacing, want):
+    """One list of 4160 one-millisecond epochs (over the 4096 from which a plan's per-item setups are made by a launch, and
+    no multiple of 64: the last wave of that launch is partial) and its first 96 as a list of their own (setups on the
+    host): the same variant word, the same bytes."""
+    fs = per_chip * 1.023e6
+    rng = np.random.default_rng(int(10 * per_chip) + len(spacing))
+    cap = 1 << 19
+    engine.iq_alloc(cap, FMT_CI8)
+    engine.iq_upload(rng.integers(-100, 100, 2 * cap).astype(np.int8), 0)
+    engine.code_slots(4, 1023, 2)
+    for s in range(4):
+        engine.load_gps_code(s, 5 * s + 3)
+    count = 4160
+    step = (1.023e6 + rng.uniform(-4, 4, count)) / fs
+    rem_code = rng.uniform(0, step)
+    n = np.ceil((1023 - rem_code) / step).astype(np.int64)
+    items = make_items(rng.integers(0, 4, count), n, rng.integers(0, cap - 40000, count), rng.uniform(-5000, 5000, count),
+                       rng.uniform(0, 6.28, count), rem_code, step)
+    long_plan, short_plan = engine.epl_plan(items, spacing, fs), engine.epl_plan(items[:96], spacing, fs)
+    try:
+        assert long_plan.variant == short_plan.variant == want
+        long_plan.run()
+        short_plan.run()
+        assert long_plan.fetch()[:96].tobytes() == short_plan.fetch().tobytes()
+    finally:
+        long_plan.close()
+        short_plan.close()
+
+
 def test_compile_time_tap_switch_variant_at_20_mhz(engine):
     """The straight-line kernel is written for a block length KM and a switch position KS = floor(KM / 2); besides 24 / 12
     (25 MHz) it is instantiated for 19 / 9: 20 MHz, 19.55 samples per chip, the outer taps switching 9.8 samples into the
