@@ -39,7 +39,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define SDR_ABI_VERSION 5   /* 5 (still): + sdr_iq_cancel, sdr_cancel_stats (additive); 5 (still): + sdr_acq_deep, sdr_acq_deep_shift (additive); 5 (still): + sdr_ddc_cfg, sdr_ddc_create / _destroy / _reset / _push / _push_queue / _out_count (additive); 5 (still): + sdr_iq_probe (additive); 5 (still): + sdr_corr_profile, option "corr_profile_per_sample" (additive); 5 (still): + sdr_iq_packing, sdr_iq_packed_bytes, sdr_iq_upload_packed / _begin / _queue (additive); 5 (still): + sdr_acq_refine, sdr_acq_refine_bins (additive); 5: + sdr_bank_tick_mirrored_begin / _end, sdr_iq_upload_queue, sdr_host_alloc / _free, options "tick_server" + sdr_tick_server_stats, "bind_thread_to_device" (additive); 4: + sdr_build_id, sdr_epl_plan_create_dev, sdr_bank_tick_mirrored, sdr_iq_upload_begin, sdr_block_schedule, sdr_bank_step_begin / _end (additive) */
+#define SDR_ABI_VERSION 5   /* 5 (still): + sdr_acq_deep_detect, sdr_detect_cfg / _peak / _noise (additive); 5 (still): + sdr_iq_cancel, sdr_cancel_stats (additive); 5 (still): + sdr_acq_deep, sdr_acq_deep_shift (additive); 5 (still): + sdr_ddc_cfg, sdr_ddc_create / _destroy / _reset / _push / _push_queue / _out_count (additive); 5 (still): + sdr_iq_probe (additive); 5 (still): + sdr_corr_profile, option "corr_profile_per_sample" (additive); 5 (still): + sdr_iq_packing, sdr_iq_packed_bytes, sdr_iq_upload_packed / _begin / _queue (additive); 5 (still): + sdr_acq_refine, sdr_acq_refine_bins (additive); 5: + sdr_bank_tick_mirrored_begin / _end, sdr_iq_upload_queue, sdr_host_alloc / _free, options "tick_server" + sdr_tick_server_stats, "bind_thread_to_device" (additive); 4: + sdr_build_id, sdr_epl_plan_create_dev, sdr_bank_tick_mirrored, sdr_iq_upload_begin, sdr_block_schedule, sdr_bank_step_begin / _end (additive) */
 
 typedef struct sdr_engine sdr_engine;
 
@@ -465,6 +465,45 @@ int sdr_acq_deep(sdr_engine* e, const int32_t* code_slots, int n_prn, int64_t st
 /* q[b][i] above for b = bin, i = block (host helper like sdr_pcps_bins; block = noncoh gives the shift of peak_code_end;
  * 0 for a NULL cfg, a negative bin or block, or carrier_rf_hz == 0). */
 int64_t sdr_acq_deep_shift(const sdr_deep_cfg* cfg, int bin, int64_t block);
+
+/* ------------------------------- detection statistics of a deep search: K separated peaks and the noise floor (opt-in)
+ * sdr_acq_deep's search, and then, on the maps while they are resident on the device, per PRN (M[G][B][N] its map as
+ * above, dist(n, m) the circular distance mod N):
+ *   peak k, k = 0 .. n_peaks-1: the first maximum, in row-major (g, b, n) order, of M over the cells outside every zone Z_j,
+ *     j < k;  Z_j = {(g, b, n): |b - b_j| <= excl_bins and dist(n, n_j) <= excl_code} for EVERY g (the groups are the same
+ *     signal on interleaved blocks).  Peak 0 is sdr_acq_deep's peak.  group, bin, code, value = M there, code_end =
+ *     peak_code_end's expression with the peak's own bin; group = -1 and value = 0.0 where no cell is left.
+ *   noise cells Omega: every (g, b, n) with dist(n, n_j) > excl_code for every reported peak j, in all bins and all groups
+ *     (a signal's ridge runs along the Doppler axis: whole code columns are left out).  n_cells = |Omega| (exact),
+ *     mean = (sum over Omega of M) / n_cells, variance = (sum over Omega of (M - mean)^2) / n_cells with `mean` the double
+ *     returned (two passes, population variance).
+ *   z_k = (value_k - mean) / sqrt(variance), fp64 in this order, made on the host side of the library from the numbers it
+ *     returns.  The call reports sigma units; it says nothing about the distribution behind them.
+ * The sums are fixed-order fp64 sums of non-negative terms: mean and variance lie within (n_cells + 4) * 2^-53, relative, of
+ * the exactly rounded sums of the same cells; indices, counts and peak values are exact.  The parts the sums are made of are
+ * runs of 2048 columns of one map row -- a constant, not derived from n_prn or the device: a PRN's figures depend on its own
+ * map alone and two identical calls return identical bits.  `results` and `corr_map` are bit for bit sdr_acq_deep's.  With
+ * groups = 1 and carrier_rf_hz = 0 this is a plain PCPS map with statistics.
+ * SDR_ERR_INVALID: sdr_acq_deep's causes, NULL det / peaks / noise, n_peaks outside 1..8, a negative window, a non-zero
+ * `reserved`, n_peaks * (2*excl_code + 1) >= N (Omega could be empty).  A refused call changes nothing.
+ * sdr_prof_enable scopes: sdr_acq_deep's, and "deep_detect_peaks", "deep_detect_noise", "call_acq_deep_detect" (in place of
+ * "call_acq_deep"). */
+typedef struct sdr_detect_cfg {
+    int32_t n_peaks /* 1..8 */, excl_code /* samples, >= 0 */, excl_bins /* >= 0 */, reserved;
+} sdr_detect_cfg;
+typedef struct sdr_detect_peak {
+    int64_t bin, code, code_end;
+    int32_t group, reserved;
+    double value, z;
+} sdr_detect_peak;
+typedef struct sdr_detect_noise {
+    int64_t n_cells;
+    double mean, variance;
+} sdr_detect_noise;
+int sdr_acq_deep_detect(sdr_engine* e, const int32_t* code_slots, int n_prn, int64_t start_sample, const sdr_deep_cfg* cfg,
+                        const sdr_detect_cfg* det, sdr_deep_result* results /* as sdr_acq_deep */,
+                        sdr_detect_peak* peaks /* [n_prn][n_peaks] */, sdr_detect_noise* noise /* [n_prn] */,
+                        double* corr_map /* nullable, as sdr_acq_deep */);
 
 /* ------------------------------------------------- closed-loop tracking
  * On-device loop closure: one persistent workgroup per

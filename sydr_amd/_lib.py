@@ -88,6 +88,16 @@ DEEP_RESULT_DTYPE = np.dtype([("peak_bin", np.int64), ("peak_code", np.int64), (
                               ("peak_value", np.float64)], align=True)
 
 
+class DetectCfg(C.Structure):
+    """sdr_detect_cfg (include/sydr_amd.h): peaks wanted and the exclusion windows around each."""
+    _fields_ = [("n_peaks", C.c_int32), ("excl_code", C.c_int32), ("excl_bins", C.c_int32), ("reserved", C.c_int32)]
+
+
+DETECT_PEAK_DTYPE = np.dtype([("bin", np.int64), ("code", np.int64), ("code_end", np.int64), ("group", np.int32),
+                              ("reserved", np.int32), ("value", np.float64), ("z", np.float64)], align=True)
+DETECT_NOISE_DTYPE = np.dtype([("n_cells", np.int64), ("mean", np.float64), ("variance", np.float64)], align=True)
+
+
 class CancelStats(C.Structure):
     """sdr_cancel_stats (include/sydr_amd.h): what sdr_iq_cancel wrote, changed and clipped."""
     _fields_ = [("samples_written", C.c_int64), ("samples_changed", C.c_int64), ("clipped_components", C.c_int64)]
@@ -270,6 +280,7 @@ _PROTOTYPES = {
     "sdr_acq_refine": (C.c_int, [_VP, _VP, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double, _VP, _VP, _VP]),
     "sdr_acq_deep": (C.c_int, [_VP, _VP, C.c_int, C.c_int64, C.POINTER(DeepCfg), _VP, _VP]),
     "sdr_acq_deep_shift": (C.c_int64, [C.POINTER(DeepCfg), C.c_int, C.c_int64]),
+    "sdr_acq_deep_detect": (C.c_int, [_VP, _VP, C.c_int, C.c_int64, C.POINTER(DeepCfg), C.POINTER(DetectCfg), _VP, _VP, _VP, _VP]),
     "sdr_corr_profile": (C.c_int, [_VP, _VP, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, _VP]),
     "sdr_ddm_bins": (C.c_int, [C.c_double, C.c_double]),
     "sdr_ddm": (C.c_int, [_VP, _VP, C.c_int, C.POINTER(DdmCfg), _VP, _VP, _VP]),

@@ -766,10 +766,16 @@ class ChannelManager:
         out.add_lazy(rows)
         return out
 
+    def acquisitionDetections(self):
+        """cid -> dict(peaks, noise, sigmas, acquired) of every channel's last search through sdr_acq_deep_detect (channels
+        configured with `detection_sigmas`; tracked.py `acquisitionDetection`)."""
+        return {cid: ch.acq_detection for cid, ch in self.channels.items() if getattr(ch, "acq_detection", None) is not None}
+
     def _acquire(self, acquiring):
         """Channels with enough samples for their search, grouped by search geometry: ONE sdr_pcps call per group
         (the forward transforms of the Doppler-mixed slab are shared by all PRNs) -- ONE sdr_acq_deep call for a group
-        configured for the deep search (`bit_edge_groups` / `code_doppler_compensation`).  Plugins that replace the
+        configured for the deep search (`bit_edge_groups` / `code_doppler_compensation`), ONE sdr_acq_deep_detect call for
+        a group with equal detection settings (`detection_sigmas` and its keys).  Plugins that replace the
         search seam (e.g. the SerialSearch plugin) run their own.  Channels configured for the fine frequency search
         (`fine_frequency_ms`) wait for its window as well, and a group's channels are refined in ONE sdr_acq_refine call
         behind their search."""
@@ -790,11 +796,22 @@ class ChannelManager:
             fine = (ch.acq_fineFrequencyMs, ch.acq_fineFrequencyStep, ch.FINE_FREQUENCY_SEGMENTS) \
                 if getattr(ch, "fineFrequencySearch", False) else None
             deep = getattr(ch, "acq_deep", None)       # (bit-edge groups, carrier_rf_hz): the deep search, tracked.py
-            key = (r["start"], r["fs"], r["if_hz"], r["doppler_range"], r["doppler_step"], r["coh"], r["noncoh"], fine, deep)
+            detect = getattr(ch, "acq_detect", None)   # (sigmas, peaks, excl_code, excl_bins): sdr_acq_deep_detect, tracked.py
+            if detect is not None:
+                deep, detect = deep if deep is not None else (1, 0.0), detect[1:]     # (the sigmas decide per channel)
+            key = (r["start"], r["fs"], r["if_hz"], r["doppler_range"], r["doppler_step"], r["coh"], r["noncoh"], fine, deep,
+                   detect)
             groups.setdefault(key, []).append(ch)
-        for (start, fs, if_hz, rng, step, coh, noncoh, fine, deep), chans in groups.items():
-            rows = None
-            if deep is None:
+        for (start, fs, if_hz, rng, step, coh, noncoh, fine, deep, detect), chans in groups.items():
+            rows = det_rows = None
+            if detect is not None:
+                rows, det_peaks, det_noise, gmap = self.engine.acq_deep_detect(
+                    [c.codeSlot for c in chans], start, fs, if_hz, rng, step, coh, noncoh, deep[0], deep[1], *detect,
+                    want_map=self.keepCorrelationMap)
+                det_rows = (det_peaks, det_noise)
+                pb, pc, pr, code_start = rows["peak_bin"], rows["peak_code"], rows["peak_ratio"], rows["peak_code_end"]
+                cmap = [gmap[k][int(rows["peak_group"][k])] for k in range(len(chans))] if gmap is not None else None
+            elif deep is None:
                 pb, pc, pr, cmap = self.engine.pcps([c.codeSlot for c in chans], start, fs, if_hz, rng, step, coh, noncoh,
                                                     want_map=self.keepCorrelationMap)
                 code_start = pc
@@ -813,6 +830,8 @@ class ChannelManager:
                 ch._injectedAcquisition = (cmap[k] if cmap is not None else None, [int(pb[k]), int(pc[k])], float(pr[k]))
                 if rows is not None:
                     ch._acqDeep = rows[k]
+                if det_rows is not None:
+                    ch._acqDetect = (det_rows[0][k], det_rows[1][k])
                 if refined is not None:
                     ch._injectedFine = refined[k]
                 packets.append(ch.runAcquisition())

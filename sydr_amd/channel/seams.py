@@ -26,6 +26,8 @@ class GpuCorrelatorSeams:
     _injectedAcquisition = None   # set by a batching manager: (map or None, [bin, code], ratio)
     acq_deep = None               # (bit-edge groups, carrier_rf_hz) of a channel configured for the deep search (tracked.py)
     _acqDeep = None               # ... its sdr_deep_result row of the search that just ran
+    acq_detect = None             # (sigmas, peaks, excl_code, excl_bins) of a channel configured with `detection_sigmas` (tracked.py)
+    _acqDetect = None             # ... the (sdr_detect_peak rows, sdr_detect_noise row) of the search that just ran
 
     # ------------------------------------------------------------------ plumbing
     def _engine(self):
@@ -73,10 +75,18 @@ class GpuCorrelatorSeams:
             return cmap
         eng = self._ensure_code()
         start = self._stage_slice(eng, self.currentSample, self.acq_requiredSamples)
-        if self.acq_deep is not None:
+        if self.acq_detect is not None:
+            groups, carrier_rf = self.acq_deep if self.acq_deep is not None else (1, 0.0)
+            res, peaks, noise, cmap = eng.acq_deep_detect(
+                [self.codeSlot], start, self.rfSignal.samplingFrequency, self.rfSignal.interFrequency, self.acq_dopplerRange,
+                self.acq_dopplerSteps, self.acq_coherentIntegration, self.acq_nonCoherentIntegration, groups, carrier_rf,
+                *self.acq_detect[1:], want_map=True)
+            self._acqDetect = (peaks[0], noise[0])
+        elif self.acq_deep is not None:
             res, cmap = eng.acq_deep([self.codeSlot], start, self.rfSignal.samplingFrequency, self.rfSignal.interFrequency,
                                      self.acq_dopplerRange, self.acq_dopplerSteps, self.acq_coherentIntegration,
                                      self.acq_nonCoherentIntegration, *self.acq_deep, want_map=True)
+        if self.acq_detect is not None or self.acq_deep is not None:
             self._acqDeep = res[0]
             self._acqMap = cmap[0][int(res[0]["peak_group"])]
             self._acqPeak = [int(res[0]["peak_bin"]), int(res[0]["peak_code"])]

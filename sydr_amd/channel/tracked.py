@@ -126,6 +126,32 @@ class DeviceTrackedChannel(GpuCorrelatorSeams, Channel, metaclass=_ViewMeta):
                                  "bit_edge_groups non-coherent blocks")
             self.acq_deep = (groups, GPS_L1CA_CARRIER_FREQ if compensate else 0.0)
         self._acqDeep = None
+        # optional (no counterpart in the reference): with `detection_sigmas` the channel searches through
+        # sdr_acq_deep_detect -- the deep search with the two keys above if given, else one group and no compensation -- and
+        # counts as acquired iff its strongest peak stands `detection_sigmas` standard deviations or more above the mean of
+        # the map's noise cells (z_0 of include/sydr_amd.h); `threshold` is still parsed and no longer decides anything.
+        # `detection_peaks` (1..8) separated peaks are kept, each clear of the others by `detection_exclusion_chips` chips
+        # of code and `detection_exclusion_bins` Doppler bins.  A channel that is not acquired goes back to IDLE.
+        self.acq_detect = None
+        if 'detection_sigmas' in configuration:
+            sigmas = float(configuration['detection_sigmas'])
+            n_peaks = int(configuration.get('detection_peaks', 1))
+            chips = float(configuration.get('detection_exclusion_chips', 1.0))
+            excl_bins = int(configuration.get('detection_exclusion_bins', 1))
+            if not sigmas > 0.0 or not 1 <= n_peaks <= 8 or not chips >= 0.0 or excl_bins < 0:
+                raise ValueError("detection_sigmas must be positive, detection_peaks lie in 1..8 and the exclusion windows "
+                                 "not be negative")
+            groups = 1 if self.acq_deep is None else self.acq_deep[0]
+            if not 1 <= self.acq_coherentIntegration <= LNAV_MS_PER_BIT or self.acq_nonCoherentIntegration < groups:
+                raise ValueError(f"detection statistics take coherent_integration in 1..{LNAV_MS_PER_BIT} and at least "
+                                 "bit_edge_groups non-coherent blocks")
+            excl_code = int(np.rint(chips * (self.rfSignal.samplingFrequency / GPS_L1CA_CODE_FREQ)))
+            per_code = int(np.rint(self.rfSignal.samplingFrequency * GPS_L1CA_CODE_SIZE_BITS / GPS_L1CA_CODE_FREQ))
+            if n_peaks * (2 * excl_code + 1) >= per_code:
+                raise ValueError("detection_peaks x the excluded code columns leave no noise cell")
+            self.acq_detect = (sigmas, n_peaks, excl_code, excl_bins)
+        self._acqDetect = None
+        self.acq_detection = None       # the last search's peaks and noise figures: see acquisitionDetection
 
     def setTracking(self, configuration):
         """Fill this channel's sdr_loop_cfg row and the state tracking starts from (kaplan:256-338, borre:206-259)."""
@@ -298,9 +324,28 @@ class DeviceTrackedChannel(GpuCorrelatorSeams, Channel, metaclass=_ViewMeta):
         # (the deep search's window is long enough for the code to drift: tracking starts behind the window, so it takes
         # the code start referred to the window's end -- peak_code_end -- where the packet reports the map's own index)
         start = indices if self._acqDeep is None else [indices[0], int(self._acqDeep["peak_code_end"])]
+        if self._acqDetect is not None and not self.acquisitionDetection():     # (set by the default search seam alone)
+            # not acquired: no tracking state is made, the channel is free for another satellite (the packet reports
+            # the search as any acquisition packet does)
+            self._acqFine = self._injectedFine = None
+            self.channelState = ChannelState.IDLE
+            return self.prepareResultsAcquisition(correlationMap, indices, ratio)
         self._acqFine = self.runFineFrequencySearch(start) if self.fineFrequencySearch else None
         self.postAcquisitionUpdate(start)
         return self.prepareResultsAcquisition(correlationMap, indices, ratio)
+
+    def acquisitionDetection(self) -> bool:
+        """Keep the search's detection figures as `acq_detection` -- dict(peaks=[dict(group, bin, code, code_end, value, z)],
+        noise=dict(n_cells, mean, variance), sigmas, acquired) -- and decide: acquired iff z_0 >= detection_sigmas."""
+        peaks, noise = self._acqDetect
+        self._acqDetect = None
+        acquired = bool(float(peaks[0]["z"]) >= self.acq_detect[0])
+        self.acq_detection = dict(
+            peaks=[dict(group=int(p["group"]), bin=int(p["bin"]), code=int(p["code"]), code_end=int(p["code_end"]),
+                        value=float(p["value"]), z=float(p["z"])) for p in peaks],
+            noise=dict(n_cells=int(noise["n_cells"]), mean=float(noise["mean"]), variance=float(noise["variance"])),
+            sigmas=self.acq_detect[0], acquired=acquired)
+        return acquired
 
     # ------------------------------------------------------------------ warm acquisition (sdr_ddm around a hint)
     _warmHint = None                # a prediction for this channel's next acquisition: see setWarmHint

@@ -12,3 +12,20 @@ int sdr_deep_fold(sdr_engine* e, int64_t first, int N, int coh, int nbins, doubl
 // (n + q[b]) % N], 0 <= q[b] < N on the device; `store`: the group's first block (0.0 + mag, as the map routes of sdr_pcps).
 int sdr_deep_shift_acc(sdr_engine* e, const double* mag, double* map, const int32_t* q, int n_prn, int nbins, int N, int groups,
                        int g, int store);
+
+// sdr_acq_deep_detect's passes over the resident maps (acq_detect.hip): the further peaks and the noise cells' moments.
+struct DeepDetectPeak {      // a peak as the kernels leave it: row = group * nbins + bin, -1 where no cell was left
+    int32_t row, code;
+    double value;
+};
+struct DeepDetectWs {        // the work space of one call, cut from one buffer of sdr_deep_detect_bytes()
+    DeepDetectPeak* peaks;   // [n_prn][8]
+    sdr_detect_noise* noise; // [n_prn]
+    void* parts;             // the partial results of a pass
+};
+size_t sdr_deep_detect_bytes(int n_prn, int rows, int N);
+DeepDetectWs sdr_deep_detect_ws(void* buf, int n_prn);
+// map = [n_prn][rows][N] with rows = groups * nbins; (row0, code0, value0)[n_prn]: peak 0 as the peak kernels of the search
+// left it in device memory.  Everything is queued on the engine's stream; nothing comes back to the host.
+int sdr_deep_detect(sdr_engine* e, const double* map, int n_prn, int rows, int nbins, int N, const sdr_detect_cfg* det,
+                    const long long* row0, const long long* code0, const double* value0, const DeepDetectWs& ws);

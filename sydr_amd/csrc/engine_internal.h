@@ -117,6 +117,7 @@ struct sdr_engine {
     std::vector<char> refine_host;   // ... and the host image of its item list (the source of the upload)
     DevBuf deep_fold, deep_mag, deep_q;   // sdr_acq_deep (pcps.hip run_deep): a block's folded periods [bins][N], the magnitudes of one
                                           // inverse sweep [PRNs of the sweep][bins][N], the shift table [blocks][bins]
+    DevBuf deep_det;                      // sdr_acq_deep_detect (acq_detect.hip): the peaks, the noise figures and a pass's partials
     DevBuf track_state, track_cfg;
     int n_cus = 0;              // compute units of the device (sizes the closed-loop clusters)
     int track_force_parts = 0;  // diagnostics / tests: 0 = choose, else 1, 2, 4 or 8 workgroups per channel

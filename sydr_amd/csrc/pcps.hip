@@ -18,6 +18,7 @@
 #include "sincos_reduced.h"
 #include "pcps_codelets.h"
 #include "acq_deep.h"
+#include "detect_zone.h"
 
 #include <cmath>
 #include <cstring>
@@ -1812,10 +1813,20 @@ int sdr_pcps_spectra(sdr_engine* e, const double* code_spectra, int n_prn, int n
 }
 
 
-int sdr_acq_deep(sdr_engine* e, const int32_t* code_slots, int n_prn, int64_t start_sample, const sdr_deep_cfg* cfg,
-                 sdr_deep_result* results, double* corr_map) {
+// sdr_acq_deep (det == nullptr: nothing below differs from the search alone) and sdr_acq_deep_detect (det, peaks, noise): the
+// detection passes run behind the search's own peak kernels, on the maps where they lie.
+static int acq_deep_impl(sdr_engine* e, const int32_t* code_slots, int n_prn, int64_t start_sample, const sdr_deep_cfg* cfg,
+                         sdr_deep_result* results, double* corr_map, const sdr_detect_cfg* det, sdr_detect_peak* peaks,
+                         sdr_detect_noise* noise) {
     if (int rc = sdr_set_device(e)) return rc;
     if (!code_slots || !cfg || !results) return sdr_fail(SDR_ERR_INVALID, "NULL argument");
+    if (det) {
+        if (!peaks || !noise) return sdr_fail(SDR_ERR_INVALID, "NULL peaks / noise");
+        if (det->n_peaks < 1 || det->n_peaks > sdr::kDetectMaxPeaks)
+            return sdr_fail(SDR_ERR_INVALID, "n_peaks = %d outside 1..%d", det->n_peaks, sdr::kDetectMaxPeaks);
+        if (det->excl_code < 0 || det->excl_bins < 0 || det->reserved != 0)
+            return sdr_fail(SDR_ERR_INVALID, "negative exclusion window or non-zero reserved field");
+    }
     if (n_prn < 1) return sdr_fail(SDR_ERR_INVALID, "no PRN to search");
     const int C = cfg->coh, K = cfg->noncoh, G = cfg->groups;
     if (C < 1 || C > 20) return sdr_fail(SDR_ERR_INVALID, "coh = %d outside 1..20", C);
@@ -1839,6 +1850,10 @@ int sdr_acq_deep(sdr_engine* e, const int32_t* code_slots, int n_prn, int64_t st
         return sdr_fail(SDR_ERR_RANGE, "deep acquisition needs %d x %d x %d samples from %lld, ring holds %lld", C, K, N,
                         (long long)start_sample, (long long)e->iq_capacity);
     if (nbins > 65535 || n_prn > 65535) return sdr_fail(SDR_ERR_UNSUPPORTED, "grid too large");
+    if (det && !sdr::detect_windows_fit(det->n_peaks, det->excl_code, N))
+        return sdr_fail(SDR_ERR_INVALID, "%d peaks x (2 x %d + 1) excluded columns leave no noise cell of %d", det->n_peaks,
+                        det->excl_code, N);
+    if (det && sdr::detect_row_parts(N) > 65535) return sdr_fail(SDR_ERR_UNSUPPORTED, "grid too large");
     const double bin_start = -cfg->doppler_range;
     const double bin_delta = (bin_start + cfg->doppler_step) - bin_start;
     // the map route's plan of coh = 1 (transforms, PRN chunks, work buffers); the deep route's own buffers on top
@@ -1854,6 +1869,7 @@ int sdr_acq_deep(sdr_engine* e, const int32_t* code_slots, int n_prn, int64_t st
                                                {&e->deep_q, (size_t)K * nbins * sizeof(int32_t)}};
     for (const auto& b : bufs)
         if ((rc = sdr_devbuf_reserve(e, b.first, b.second))) return rc;
+    if (det && (rc = sdr_devbuf_reserve(e, &e->deep_det, sdr_deep_detect_bytes(n_prn, G * nbins, N)))) return rc;
     BluPlan blu;
     if ((rc = prepare_tables(e, p, &blu))) return rc;
     if ((rc = sdr_pinned_reserve(e, &e->ctx0, (size_t)n_prn * sizeof(int32_t)))) return rc;
@@ -1884,10 +1900,14 @@ int sdr_acq_deep(sdr_engine* e, const int32_t* code_slots, int n_prn, int64_t st
     d.q = (const int32_t*)e->deep_q.ptr;
     d.fold = (double2*)e->deep_fold.ptr;
     d.mag = (double*)e->deep_mag.ptr;
+    const DeepDetectWs ws = det ? sdr_deep_detect_ws(e->deep_det.ptr, n_prn) : DeepDetectWs{};
     {
-        ProfScope whole(e, "call_acq_deep");
+        ProfScope whole(e, det ? "call_acq_deep_detect" : "call_acq_deep");
         rc = code_spectra<SDR_FMT_CF64>(e, p, c);
         if (!rc) rc = run_deep(e, p, c, d);
+        if (!rc && det)
+            rc = sdr_deep_detect(e, (const double*)e->pcps_map.ptr, n_prn, G * nbins, nbins, N, det, c.res_bin, c.res_code,
+                                 c.res_ratio + n_prn, ws);
     }
     if (rc) {
         e->pcps_spec_key.clear();      // (a search that stopped half way: what the code-spectra buffer holds is unknown)
@@ -1895,9 +1915,33 @@ int sdr_acq_deep(sdr_engine* e, const int32_t* code_slots, int n_prn, int64_t st
     }
     std::vector<long long> host(4 * (size_t)n_prn);
     SDR_HIP(hipMemcpyAsync(host.data(), e->pcps_res.ptr, res_bytes, hipMemcpyDeviceToHost, e->stream));
+    std::vector<DeepDetectPeak> host_peaks(det ? (size_t)n_prn * sdr::kDetectMaxPeaks : 0);
+    std::vector<sdr_detect_noise> host_noise(det ? (size_t)n_prn : 0);
+    if (det) {
+        SDR_HIP(hipMemcpyAsync(host_peaks.data(), ws.peaks, host_peaks.size() * sizeof(DeepDetectPeak), hipMemcpyDeviceToHost,
+                               e->stream));
+        SDR_HIP(hipMemcpyAsync(host_noise.data(), ws.noise, host_noise.size() * sizeof(sdr_detect_noise), hipMemcpyDeviceToHost,
+                               e->stream));
+    }
     if (corr_map)
         SDR_HIP(hipMemcpyAsync(corr_map, e->pcps_map.ptr, (size_t)n_prn * G * row_bytes, hipMemcpyDeviceToHost, e->stream));
     SDR_HIP(hipStreamSynchronize(e->stream));
+    for (int i = 0; det && i < n_prn; ++i) {
+        noise[i] = host_noise[(size_t)i];
+        const double sigma = std::sqrt(noise[i].variance);
+        for (int k = 0; k < det->n_peaks; ++k) {
+            const DeepDetectPeak& h = host_peaks[(size_t)i * sdr::kDetectMaxPeaks + k];
+            sdr_detect_peak& o = peaks[(size_t)i * det->n_peaks + k];
+            o.group = h.row < 0 ? -1 : h.row / nbins;
+            o.reserved = 0;
+            o.bin = h.row < 0 ? 0 : h.row % nbins;
+            o.code = h.code;
+            const int64_t end = (o.code + sdr_acq_deep_shift(cfg, (int)o.bin, K)) % N;
+            o.code_end = h.row < 0 ? 0 : (end < 0 ? end + N : end);
+            o.value = h.value;
+            o.z = (o.value - noise[i].mean) / sigma;
+        }
+    }
     for (int i = 0; i < n_prn; ++i) {
         sdr_deep_result& r = results[i];
         const long long row = host[(size_t)i];
@@ -1911,6 +1955,18 @@ int sdr_acq_deep(sdr_engine* e, const int32_t* code_slots, int n_prn, int64_t st
         r.peak_code_end = end < 0 ? end + N : end;
     }
     return SDR_OK;
+}
+
+int sdr_acq_deep(sdr_engine* e, const int32_t* code_slots, int n_prn, int64_t start_sample, const sdr_deep_cfg* cfg,
+                 sdr_deep_result* results, double* corr_map) {
+    return acq_deep_impl(e, code_slots, n_prn, start_sample, cfg, results, corr_map, nullptr, nullptr, nullptr);
+}
+
+int sdr_acq_deep_detect(sdr_engine* e, const int32_t* code_slots, int n_prn, int64_t start_sample, const sdr_deep_cfg* cfg,
+                        const sdr_detect_cfg* det, sdr_deep_result* results, sdr_detect_peak* peaks, sdr_detect_noise* noise,
+                        double* corr_map) {
+    if (!det) return sdr_fail(SDR_ERR_INVALID, "NULL detection settings");
+    return acq_deep_impl(e, code_slots, n_prn, start_sample, cfg, results, corr_map, det, peaks, noise);
 }
 
 }  // extern "C"

@@ -54,6 +54,51 @@ def deep_code_end(peak_bin, peak_code, dopplerRange, dopplerStep, samplesPerCode
                                         peak_bin, nonCoherentIntegration)) % int(samplesPerCode)
 
 
+def deep_detect(M, n_peaks, excl_code, excl_bins):
+    """The statement of sdr_acq_deep_detect's figures for one PRN's map M[G][B][N] (include/sydr_amd.h):
+    -> (peaks, noise).  peaks: n_peaks dicts(group, bin, code, value, z) -- peak k is the first maximum, in row-major
+    (g, b, n) order, outside the zones |b - b_j| <= excl_bins, dist(n, n_j) <= excl_code (every g) of the peaks j < k;
+    group = -1, value = 0.0 where no cell is left.  noise: dict(n_cells, mean, variance) of the cells whose code column lies
+    further than excl_code (circularly) from every reported peak's, in all bins and groups: two passes, population variance.
+    z = (value - mean) / sqrt(variance) in fp64, in this order."""
+    M = np.asarray(M, dtype=np.float64)
+    if M.ndim != 3:
+        raise ValueError("deep_detect takes one PRN's map [groups][bins][samplesPerCode]")
+    G, B, N = M.shape
+    n_peaks, excl_code, excl_bins = int(n_peaks), int(excl_code), int(excl_bins)
+    if not 1 <= n_peaks <= 8:
+        raise ValueError(f"n_peaks = {n_peaks} outside 1..8")
+    if excl_code < 0 or excl_bins < 0:
+        raise ValueError("negative exclusion window")
+    if n_peaks * (2 * excl_code + 1) >= N:
+        raise ValueError(f"{n_peaks} peaks x (2 x {excl_code} + 1) excluded columns leave no noise cell of {N}")
+    n = np.arange(N)
+    b = np.arange(B)
+    free = np.ones((B, N), dtype=bool)          # outside every zone so far (the same for every group)
+    columns = np.ones(N, dtype=bool)            # code columns clear of every reported peak
+    peaks = []
+    for _ in range(n_peaks):
+        if not free.any():
+            peaks.append(dict(group=-1, bin=0, code=0, value=0.0))
+            continue
+        masked = np.where(free[None, :, :], M, -np.inf)
+        g_k, b_k, n_k = (int(v) for v in np.unravel_index(np.argmax(masked), M.shape))
+        peaks.append(dict(group=g_k, bin=b_k, code=n_k, value=float(M[g_k, b_k, n_k])))
+        d = np.abs(n - n_k)
+        near = np.minimum(d, N - d) <= excl_code
+        free &= ~((np.abs(b - b_k) <= excl_bins)[:, None] & near[None, :])
+        columns &= ~near
+    cells = M[:, :, columns].ravel()
+    n_cells = int(cells.size)
+    mean = float(np.sum(cells)) / n_cells
+    dev = cells - mean
+    variance = float(np.sum(dev * dev)) / n_cells
+    for p in peaks:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            p["z"] = float((np.float64(p["value"]) - mean) / np.sqrt(np.float64(variance)))
+    return peaks, dict(n_cells=n_cells, mean=mean, variance=variance)
+
+
 def _chips_of_spectrum(codeFFT, samplingFrequency):
     """The chips behind codeFFT = conj(fft(UpsampleCode(code))) (gnsssignal.py:53: sample k holds chip trunc(k*ts/tc))."""
     up = np.rint(np.real(np.fft.ifft(np.conj(np.asarray(codeFFT, dtype=np.complex128)))))
@@ -62,14 +107,12 @@ def _chips_of_spectrum(codeFFT, samplingFrequency):
     return up[first].astype(np.int8)
 
 
-def DeepSearch(rfData, interFrequency, samplingFrequency, code, dopplerRange, dopplerStep, samplesPerCode,
-               coherentIntegration=1, nonCoherentIntegration=1, groups=1, carrierFrequencyRF=0.0):
-    """Correlation map [groups][bins][samplesPerCode] of the statement above, on the GPU.  `code`: the chips (+-1), or
-    codeFFT = conj(fft(UpsampleCode(code))) of length samplesPerCode as PCPS takes it (the chips are read back from it)."""
+def _stage(rfData, samplingFrequency, code, samplesPerCode, coherentIntegration, nonCoherentIntegration, who):
+    """The window in a cf64 ring from sample 0 and the chips in slot 3 of the process's engine."""
     rf = np.squeeze(np.asarray(rfData, dtype=np.complex128))
     need = int(samplesPerCode) * int(coherentIntegration) * int(nonCoherentIntegration)
     if rf.size < need:
-        raise ValueError(f"DeepSearch needs {need} samples, got {rf.size}")
+        raise ValueError(f"{who} needs {need} samples, got {rf.size}")
     code = np.asarray(code)
     chips = _chips_of_spectrum(code, samplingFrequency) if np.iscomplexobj(code) else code.astype(np.int8)
     eng = get_engine()
@@ -80,6 +123,29 @@ def DeepSearch(rfData, interFrequency, samplingFrequency, code, dopplerRange, do
     if eng.iq_fmt != FMT_CF64 or eng.iq_capacity < cap:
         eng.iq_alloc(cap, FMT_CF64)
     eng.iq_upload(rf[:need], 0)
+    return eng
+
+
+def DeepSearch(rfData, interFrequency, samplingFrequency, code, dopplerRange, dopplerStep, samplesPerCode,
+               coherentIntegration=1, nonCoherentIntegration=1, groups=1, carrierFrequencyRF=0.0):
+    """Correlation map [groups][bins][samplesPerCode] of the statement above, on the GPU.  `code`: the chips (+-1), or
+    codeFFT = conj(fft(UpsampleCode(code))) of length samplesPerCode as PCPS takes it (the chips are read back from it)."""
+    eng = _stage(rfData, samplingFrequency, code, samplesPerCode, coherentIntegration, nonCoherentIntegration, "DeepSearch")
     _, cmap = eng.acq_deep([3], 0, samplingFrequency, interFrequency, dopplerRange, dopplerStep, coherentIntegration,
                            nonCoherentIntegration, groups, carrierFrequencyRF, want_map=True)
     return cmap[0]
+
+
+def DeepDetect(rfData, interFrequency, samplingFrequency, code, dopplerRange, dopplerStep, samplesPerCode,
+               coherentIntegration=1, nonCoherentIntegration=1, groups=1, carrierFrequencyRF=0.0, n_peaks=1, excl_code=0,
+               excl_bins=0, want_map=False):
+    """`deep_detect`'s (peaks, noise) of DeepSearch's map, made on the GPU where the map lies (sdr_acq_deep_detect); the
+    peaks carry `code_end` too.  With want_map -> (peaks, noise, map [groups][bins][samplesPerCode])."""
+    eng = _stage(rfData, samplingFrequency, code, samplesPerCode, coherentIntegration, nonCoherentIntegration, "DeepDetect")
+    _, peaks, noise, cmap = eng.acq_deep_detect([3], 0, samplingFrequency, interFrequency, dopplerRange, dopplerStep,
+                                                coherentIntegration, nonCoherentIntegration, groups, carrierFrequencyRF,
+                                                n_peaks, excl_code, excl_bins, want_map=want_map)
+    out = ([dict(group=int(p["group"]), bin=int(p["bin"]), code=int(p["code"]), code_end=int(p["code_end"]),
+                 value=float(p["value"]), z=float(p["z"])) for p in peaks[0]],
+           dict(n_cells=int(noise[0]["n_cells"]), mean=float(noise[0]["mean"]), variance=float(noise[0]["variance"])))
+    return out + (cmap[0],) if want_map else out

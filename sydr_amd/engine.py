@@ -793,6 +793,29 @@ class Engine:
                                      ptr(cmap) if want_map else None))
         return res, cmap
 
+    def acq_deep_detect(self, code_slots, start_sample, fs, if_hz, doppler_range, doppler_step, coh, noncoh, groups=1,
+                        carrier_rf_hz=0.0, n_peaks=1, excl_code=0, excl_bins=0, want_map=False):
+        """The deep search with detection statistics made on the resident maps (sdr_acq_deep_detect): the `n_peaks`
+        strongest peaks that lie outside each other's zones (`excl_code` samples circularly, `excl_bins` bins) and the
+        count, mean and variance of the cells whose code column is clear of every peak.
+        -> (results as `acq_deep`, peaks: DETECT_PEAK_DTYPE[n][n_peaks] -- bin, code, code_end, group, value, z --,
+        noise: DETECT_NOISE_DTYPE[n] -- n_cells, mean, variance --, map or None)."""
+        slots = np.ascontiguousarray(code_slots, dtype=np.int32)
+        n = len(slots)
+        cfg = _lib.DeepCfg(float(fs), float(if_hz), float(doppler_range), float(doppler_step), float(carrier_rf_hz),
+                           int(coh), int(noncoh), int(groups), 0)
+        det = _lib.DetectCfg(int(n_peaks), int(excl_code), int(excl_bins), 0)
+        res = np.zeros(n, dtype=_lib.DEEP_RESULT_DTYPE)
+        peaks = np.zeros((n, max(0, min(int(n_peaks), 8))), dtype=_lib.DETECT_PEAK_DTYPE)
+        noise = np.zeros(n, dtype=_lib.DETECT_NOISE_DTYPE)
+        cmap = None
+        if want_map:
+            nbins = max(0, self._lib.sdr_pcps_bins(float(doppler_range), float(doppler_step)))
+            cmap = np.empty((n, max(0, int(groups)), nbins, int(round(fs * 1023 / 1.023e6))), dtype=np.float64)
+        check(self._lib.sdr_acq_deep_detect(self._h, ptr(slots), n, int(start_sample), C.byref(cfg), C.byref(det), ptr(res),
+                                            ptr(peaks), ptr(noise), ptr(cmap) if want_map else None))
+        return res, peaks, noise, cmap
+
     def two_peak_compare_ss(self, cmap: np.ndarray):
         cmap = np.ascontiguousarray(cmap, dtype=np.float64)
         pb, pc, pr = C.c_int64(0), C.c_int64(0), C.c_double(0)
