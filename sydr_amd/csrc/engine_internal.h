@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/sydr_amd.h"
+#include "pcps_fused_work.h"
 
 // Thread-local error text behind sdr_last_error().
 void sdr_set_error(const char* fmt, ...);
@@ -173,8 +174,8 @@ struct sdr_engine {
     bool pcps_no_spec_cache = false; // "pcps_no_spectra_cache": conj(fft(code)) recomputed by every search, as the reference does (kaplan:184-185)
     bool pcps_fused = true;          // map-free search at N = 125 x 200 of a round of 256 transforms or more: one workgroup per (PRN, bin) transform (pcps_fused.h); "pcps_fused" = 0: the two-kernel sweeps
     DevBuf pcps_work;                // its work list (transform numbers in processing order)
-    int pcps_work_prn = 0, pcps_work_bins = 0, pcps_work_block = 0;   // ... and the grid / block shape it was made for
-    int pcps_work_first[9] = {0};
+    fusedwork::WorkKey pcps_work_key;   // ... what it was made for (pcps_fused_work.h: everything the list is a function of)
+    int pcps_work_first[9] = {0};       // ... and the XCDs' shares of it
     DevBuf pcps_theta;               // its two per-PRN bound arrays (pcps_fused.h Args::theta), the PRN count they are for, the one in use
     int pcps_theta_prn = 0, pcps_theta_flip = 0;
 

@@ -57,7 +57,7 @@ constexpr int kTab = 240;                     // w125^e (e <= 96) during the col
 constexpr size_t kLdsBytes = (size_t)(2 * kBuf + kTab) * sizeof(double2);
 static_assert(kLdsBytes == 160 * 1024, "the whole LDS of a CU");
 constexpr int kRecordsPerTransform = kWaves;
-constexpr int kSlotsPerXcd = 32;
+constexpr int kSlotsPerXcd = fusedwork::kSlotsPerXcd;
 
 // exp(-2 pi i k / n) for the transforms' internal twiddles: literals (a wave-uniform table read costs scalar registers the
 // kernel does not have; the compiler materialises a literal where it is used)
@@ -97,13 +97,9 @@ __device__ __forceinline__ double2 ldb(const Operand& o, unsigned voff, unsigned
     return *reinterpret_cast<const double2*>((o.base + soff) + voff);
 }
 
-// One unit of work of a persistent workgroup: a whole (PRN, bin) transform, or -- for the transforms left over when the
-// search is not a whole number of rounds of 256 -- ONE of a transform's five rounds: the column stage then computes that
-// round's fifth of its outputs only (all operands are still read), so that the tail of the launch is a fifth of a round
-// on 5 x as many compute units.  `record`: where its kRecordsPerTransform records go (PRN-major for the peak kernel).
-struct WorkItem {
-    int prn, bin, round, record;
-};
+// One unit of work of a persistent workgroup, the list of them and the slots per XCD: pcps_fused_work.h (host arithmetic,
+// checked on its own)
+using fusedwork::WorkItem;
 
 struct Args {
     const double2* spec;       // [nbins][N] forward spectra of the Doppler-mixed block
@@ -751,63 +747,6 @@ __global__ __launch_bounds__(kThreads) void ifft_second_kernel(const SecondArgs 
             __hip_atomic_store(&s.done[prn], s.done_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // ... before this word
         }
     }
-}
-
-// Processing order and record slots of a search over bins [0, nbins) x n_prn PRNs.  The first `bins_whole` bins are done
-// as whole transforms: blocks of 4 bins x 8 PRNs (32 transforms = one round of an XCD's 32 workgroups, so that the
-// operands an XCD has in flight mostly sit in its L2), dealt to the XCDs in contiguous eighths; the transforms of the
-// remaining bins are cut into their five rounds, dealt out behind the whole ones (a workgroup's last, short unit).
-// Record slots are PRN-major: PRN p owns slots [p * per_prn, (p + 1) * per_prn), per_prn = bins_whole + 5 (nbins - bins_whole).
-inline int make_work_list(int n_prn, int nbins, int bins_whole, std::vector<WorkItem>& order, int first[9], int pieces = 5,
-                          int block_bins = 4) {
-    // block_bins: bins of a block of 32 whole transforms (x 32 / block_bins PRNs).  4 x 8 shares 4 spectra + 8 code spectra;
-    // with SHARED spectra (pcps.hip: a handful of class arrays serve every bin, and stay in the L2s) 16 x 2 shares the classes
-    // + 2 code spectra, 32 x 1 the classes + 1: half the operand arrays an XCD has in flight, or fewer.
-    const int block_prns = kSlotsPerXcd / block_bins;
-    // pieces: 5 = one unit per round; 3 = rounds {0, 1}, {2, 3}, {4} (N = 50 000: the operand stage of a unit costs what four
-    // rounds do, and 64 left-over transforms x 3 fit ONE wave of workgroups where x 5 need a wave and a quarter)
-    const int per_prn = bins_whole + pieces * (nbins - bins_whole);
-    std::vector<WorkItem> whole, parts;
-    for (int b0 = 0; b0 < bins_whole; b0 += block_bins)
-        for (int p0 = 0; p0 < n_prn; p0 += block_prns)
-            for (int b = b0; b < b0 + block_bins && b < bins_whole; ++b)
-                for (int p = p0; p < p0 + block_prns && p < n_prn; ++p) whole.push_back({p, b, -1, p * per_prn + b});
-    for (int b = bins_whole; b < nbins; ++b)
-        for (int p = 0; p < n_prn; ++p)
-            for (int u = 0; u < pieces; ++u) {
-                const int rounds = pieces == 5 ? (u | 15 << 4) : (u == 2 ? (4 | 15 << 4) : (2 * u | (2 * u + 1) << 4));
-                parts.push_back({p, b, rounds, p * per_prn + bins_whole + pieces * (b - bins_whole) + u});
-            }
-    // XCD x: its eighth of the short units, then its eighth of the whole transforms (its workgroups walk the list in steps
-    // of 32)
-    order.clear();
-    const int nw = (int)whole.size(), np = (int)parts.size();
-    first[0] = 0;
-    // The short units go FIRST (round 5): three workgroups in four start with one and run the rest of the launch ~3/4 of a
-    // unit out of step with the others -- the operand stages of an XCD's 32 workgroups no longer all fall into the same
-    // moments -- and no workgroup is left holding a short unit while the others have finished.  Measured, one box, ms of
-    // kernels per 32-PRN call: N = 50 000 0.532 -> 0.511, N = 25 000 0.235 -> 0.228 (gpurun_out/r05_partsfirst.txt).
-    constexpr bool parts_first = true;
-    for (int x = 0; x < 8; ++x) {
-        const int p_lo = (int)(((long long)np * x) / 8), p_hi = (int)(((long long)np * (x + 1)) / 8);
-        const int w_lo = (int)(((long long)nw * x) / 8), w_hi = (int)(((long long)nw * (x + 1)) / 8);
-        if (parts_first) {
-            for (int i = p_lo; i < p_hi; ++i) order.push_back(parts[i]);
-            // the XCD's 32 workgroups walk the list 32 items at a time, and the whole transforms come in blocks of 32 that share
-            // their operand arrays: the step the short units leave incomplete is filled with the LAST whole transforms, so that
-            // every later step is one block again (with the blocks straddling two steps the launch fetched 1.34 instead of
-            // 0.87 GB through the fabric at N = 50 000)
-            int pad = (kSlotsPerXcd - (p_hi - p_lo) % kSlotsPerXcd) % kSlotsPerXcd;
-            if (pad > w_hi - w_lo) pad = w_hi - w_lo;
-            for (int i = w_hi - pad; i < w_hi; ++i) order.push_back(whole[i]);
-            for (int i = w_lo; i < w_hi - pad; ++i) order.push_back(whole[i]);
-        } else {
-            for (int i = w_lo; i < w_hi; ++i) order.push_back(whole[i]);
-            for (int i = p_lo; i < p_hi; ++i) order.push_back(parts[i]);
-        }
-        first[x + 1] = (int)order.size();
-    }
-    return per_prn;
 }
 
 }  // namespace fused25k

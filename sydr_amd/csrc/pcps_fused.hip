@@ -11,28 +11,14 @@ namespace {
 #include "pcps_fused.h"
 #include "pcps_fused10k.h"
 static_assert(fused25k::kRecordsPerTransform == SDR_PCPS_FUSED_RECORDS, "records per transform");
+static_assert(fusedwork::kRecordsPerUnit == SDR_PCPS_FUSED_RECORDS, "records per unit");
 static_assert(sizeof(fused10k::UnitRecord) == SDR_PCPS_FUSED10K_RECORD_BYTES, "unit record");
 }  // namespace
-
-// How the fused sweep cuts a search of n_prn x nbins transforms: whole transforms for the bins that fill whole rounds of
-// its 256 workgroups, single rounds for the rest (returns the records per PRN the sweep leaves).
-static int fused_plan(int n_prn, int nbins, int* bins_whole, int pieces) {
-    const int rounds = (n_prn * nbins) / 256;
-    int bw = rounds > 0 ? (256 * rounds) / n_prn : 0;
-    if (bw > nbins) bw = nbins;
-    // (more than a round's worth left over -- few PRNs, many bins -- : cutting buys nothing, whole transforms throughout)
-    if (n_prn * (nbins - bw) > 256) bw = nbins;
-    *bins_whole = bw;
-    return bw + pieces * (nbins - bw);
-}
-// units a left-over transform is cut into: its five rounds at N = 25 000; rounds {0, 1}, {2, 3}, {4} at N = 50 000
-static int fused_pieces(int terms) { return terms == 2 ? 3 : 5; }
 
 // (terms: 1 at N = 25 000; 2 at N = 50 000, where a unit is one parity of a (PRN, bin) transform and the plan sees
 // 2 nbins virtual bins)
 int sdr_pcps_fused_records_per_prn(int n_prn, int nbins, int terms) {
-    int bw;
-    return fused_plan(n_prn, terms * nbins, &bw, fused_pieces(terms)) * SDR_PCPS_FUSED_RECORDS;
+    return fusedwork::fused_records_per_prn(n_prn, nbins, terms);
 }
 
 // C: [n_prn][N] code spectra at N = 25 000; [n_prn][2][N] at N = 50 000 -- the spectrum and its image with the odd half's
@@ -41,22 +27,19 @@ int sdr_pcps_fused_sweep(sdr_engine* e, const void* F, const void* spec_off, con
                          void* partials) {
     if (N != fused25k::N && N != 2 * fused25k::N) return sdr_fail(SDR_ERR_UNSUPPORTED, "fused PCPS sweep: N = %d", N);
     const int terms = N / fused25k::N;
-    const int vbins = terms * nbins;
-    // (shared spectra: see make_work_list.  Measured, ms of kernels per 32-PRN x 41-bin call with blocks of 4 / 8 / 16 / 32 bins:
-    // N = 25 000 0.2165 / 0.2116 / 0.2118 / 0.2144, N = 50 000 0.4834 / 0.4790 / 0.4705 / 0.4665 -- gpurun_out/r05_block_bins.txt)
-    const int block_bins = spec_off ? (terms == 2 ? 32 : 16) : 4;
-    if (e->pcps_work_prn != n_prn || e->pcps_work_bins != vbins || e->pcps_work_block != block_bins) {
+    // the device's work list is the one of `key` or is made now: the key holds everything the list is a function of
+    const fusedwork::WorkKey key = fusedwork::fused_work_key(n_prn, nbins, terms, spec_off != nullptr);
+    if (e->pcps_work_key != key) {
         std::vector<fused25k::WorkItem> order;
-        int bins_whole;
-        fused_plan(n_prn, vbins, &bins_whole, fused_pieces(terms));
-        fused25k::make_work_list(n_prn, vbins, bins_whole, order, e->pcps_work_first, fused_pieces(terms), block_bins);
+        int first[9];
+        fusedwork::make_work_list(key, order, first);
+        e->pcps_work_key = fusedwork::WorkKey();   // (valid again only once the new list is on the device, below)
         if (int rc = sdr_devbuf_reserve(e, &e->pcps_work, order.size() * sizeof(fused25k::WorkItem))) return rc;
         // (pageable source, tiny: the copy is complete when the stream has been waited for)
         SDR_HIP(hipMemcpyAsync(e->pcps_work.ptr, order.data(), order.size() * sizeof(fused25k::WorkItem), hipMemcpyHostToDevice, e->stream));
         SDR_HIP(hipStreamSynchronize(e->stream));
-        e->pcps_work_prn = n_prn;
-        e->pcps_work_bins = vbins;
-        e->pcps_work_block = block_bins;
+        for (int x = 0; x < 9; ++x) e->pcps_work_first[x] = first[x];
+        e->pcps_work_key = key;
     }
     fused25k::Args a = {};
     a.spec = (const double2*)F;
