@@ -28,22 +28,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kBinTile = 16;   // bins per workgroup: 256 B written per sample column against <= 16*C B read (cf64 ring)
 
-template <int FMT>
-__device__ __forceinline__ double2 ring_sample(const void* ring, int64_t pos) {
-    if (FMT == SDR_FMT_CI8) {
-        const char2 v = static_cast<const char2*>(ring)[pos];      // (sign-flipped bytes: correlator.h kCi8Flip)
-        return make_double2((double)(int8_t)(v.x ^ 0x80), (double)(int8_t)(v.y ^ 0x80));
-    } else if (FMT == SDR_FMT_CI16) {
-        const short2 v = static_cast<const short2*>(ring)[pos];
-        return make_double2((double)v.x, (double)v.y);
-    } else if (FMT == SDR_FMT_CF32) {
-        const float2 v = static_cast<const float2*>(ring)[pos];
-        return make_double2((double)v.x, (double)v.y);
-    } else {
-        return static_cast<const double2*>(ring)[pos];
-    }
-}
-
 // CT: the compiled-in bound of the period loop (the lane's samples stay in registers), C <= CT periods are live.
 template <int FMT, int CT>
 __global__ __launch_bounds__(kThreads) void deep_fold_kernel(const void* __restrict__ ring, int64_t capacity, int64_t first,
@@ -59,7 +43,7 @@ __global__ __launch_bounds__(kThreads) void deep_fold_kernel(const void* __restr
         pp[c] = 0.0;
         if (c < C) {
             const int64_t m = (int64_t)c * N + n;              // index into phasePoints: the carrier restarts with the block
-            x[c] = ring_sample<FMT>(ring, (first + m) % capacity);
+            x[c] = sdr::ring_read<FMT>(ring, (first + m) % capacity);
             pp[c] = (double)(m * 2) * M_PI;                    // acquisition.py:33: ((m*2)*pi)/fs
             pp[c] = pp[c] / fs;
         }
@@ -120,12 +104,7 @@ int sdr_deep_fold(sdr_engine* e, int64_t first, int N, int coh, int nbins, doubl
     if (coh < 1 || coh > 20 || N < 1 || nbins < 1 || first < 0 || !F) return sdr_fail(SDR_ERR_INVALID, "bad fold request");
     ProfScope ps(e, "deep_fold");
     double2* f = (double2*)F;
-    switch (e->iq_fmt) {
-        case SDR_FMT_CI8: launch_fold<SDR_FMT_CI8>(e, first, N, coh, nbins, fs, if_hz, bin_start, bin_delta, f); break;
-        case SDR_FMT_CI16: launch_fold<SDR_FMT_CI16>(e, first, N, coh, nbins, fs, if_hz, bin_start, bin_delta, f); break;
-        case SDR_FMT_CF32: launch_fold<SDR_FMT_CF32>(e, first, N, coh, nbins, fs, if_hz, bin_start, bin_delta, f); break;
-        default: launch_fold<SDR_FMT_CF64>(e, first, N, coh, nbins, fs, if_hz, bin_start, bin_delta, f); break;
-    }
+    sdr::with_fmt(e->iq_fmt, [&](auto fmt) { launch_fold<decltype(fmt)::value>(e, first, N, coh, nbins, fs, if_hz, bin_start, bin_delta, f); });
     SDR_HIP(hipGetLastError());
     return SDR_OK;
 }

@@ -50,17 +50,6 @@ struct CancelArgs {
     unsigned long long* stats;       // [2]: samples changed, components clipped
 };
 
-template <int FMT>
-struct Fmt;
-template <>
-struct Fmt<SDR_FMT_CI8> { static constexpr int S = 8; };
-template <>
-struct Fmt<SDR_FMT_CI16> { static constexpr int S = 4; };
-template <>
-struct Fmt<SDR_FMT_CF32> { static constexpr int S = 2; };
-template <>
-struct Fmt<SDR_FMT_CF64> { static constexpr int S = 1; };
-
 // sample j of a granule's four words, widened
 template <int FMT>
 __device__ __forceinline__ void sample_get(const uint32_t (&w)[4], int j, double& xr, double& xi) {
@@ -80,7 +69,7 @@ __device__ __forceinline__ void sample_get(const uint32_t (&w)[4], int j, double
     }
 }
 
-// sdr_ddc_push's rule for an integer ring: round to nearest even, clip to the symmetric rails
+// ring_format.h clip_rint, counting the components that the rails change
 __device__ __forceinline__ int quantise(double v, double lim, unsigned& clipped) {
     const double r = rint(v);
     clipped += fabs(r) > lim ? 1u : 0u;
@@ -91,12 +80,14 @@ __device__ __forceinline__ int quantise(double v, double lim, unsigned& clipped)
 template <int FMT>
 __device__ __forceinline__ void sample_put(uint32_t (&w)[4], int j, double yr, double yi, unsigned& clipped) {
     if (FMT == SDR_FMT_CI8) {
-        const unsigned re = (unsigned)quantise(yr, 127.0, clipped) & 0xffu, im = (unsigned)quantise(yi, 127.0, clipped) & 0xffu;
-        const unsigned h = (re | (im << 8)) ^ 0x8080u;
+        constexpr double lim = ring_rail(SDR_FMT_CI8);
+        const unsigned re = (unsigned)quantise(yr, lim, clipped) & 0xffu, im = (unsigned)quantise(yi, lim, clipped) & 0xffu;
+        const unsigned h = (re | (im << 8)) ^ (kCi8Flip & 0xffffu);
         const int sh = 16 * (j & 1);
         w[j >> 1] = (w[j >> 1] & ~(0xffffu << sh)) | (h << sh);
     } else if (FMT == SDR_FMT_CI16) {
-        const unsigned re = (unsigned)quantise(yr, 32767.0, clipped) & 0xffffu, im = (unsigned)quantise(yi, 32767.0, clipped) & 0xffffu;
+        constexpr double lim = ring_rail(SDR_FMT_CI16);
+        const unsigned re = (unsigned)quantise(yr, lim, clipped) & 0xffffu, im = (unsigned)quantise(yi, lim, clipped) & 0xffffu;
         w[j] = re | (im << 16);
     } else if (FMT == SDR_FMT_CF32) {
         w[2 * j] = __float_as_uint((float)yr);
@@ -118,7 +109,7 @@ __device__ __forceinline__ void sample_store(void* dst, int64_t pos, const uint3
 
 template <int FMT>
 __global__ __launch_bounds__(kThreads) void cancel_kernel(const CancelArgs a) {
-    constexpr int S = Fmt<FMT>::S;
+    constexpr int S = ring_granule_samples(FMT);
     __shared__ int first[SDR_CANCEL_MAX_CHANNELS];   // per channel: the first epoch that reaches into this tile
     __shared__ unsigned red[2][kThreads / 64];
     const int tid = threadIdx.x;
@@ -279,7 +270,7 @@ int sdr_iq_cancel(sdr_engine* e, const sdr_epl_item* items, const double* amps, 
     a.count = (const int32_t*)((char*)e->cancel_ws.ptr + b_items);
     a.stats = (unsigned long long*)((char*)e->cancel_ws.ptr + b_items + b_count);
     a.n_ch = n_ch, a.n_epochs = n_epochs, a.codes = e->codes, a.code_stride = e->code_stride, a.in_place = in_place ? 1 : 0, a.fs = fs;
-    const int spg = (int)(16 / sdr_fmt_bytes(e->iq_fmt));
+    const int spg = ring_granule_samples(e->iq_fmt);
     a.win = probe_window(base, W, cap, spg);
     const int64_t tiles = (a.win.total + kThreads - 1) / kThreads;
     if (tiles > 0x7fffffff) return sdr_fail(SDR_ERR_UNSUPPORTED, "a window of %lld samples needs more tiles than one launch has", (long long)W);
@@ -298,12 +289,9 @@ int sdr_iq_cancel(sdr_engine* e, const sdr_epl_item* items, const double* amps, 
         {
             ProfScope ps(e, "cancel_kernel");
             if (dst == e) sdr_iq_mark_written(e, dbase, W);
-            switch (e->iq_fmt) {
-                case SDR_FMT_CI8: hipLaunchKernelGGL(cancel_kernel<SDR_FMT_CI8>, dim3((unsigned)tiles), dim3(kThreads), 0, e->stream, a); break;
-                case SDR_FMT_CI16: hipLaunchKernelGGL(cancel_kernel<SDR_FMT_CI16>, dim3((unsigned)tiles), dim3(kThreads), 0, e->stream, a); break;
-                case SDR_FMT_CF32: hipLaunchKernelGGL(cancel_kernel<SDR_FMT_CF32>, dim3((unsigned)tiles), dim3(kThreads), 0, e->stream, a); break;
-                default: hipLaunchKernelGGL(cancel_kernel<SDR_FMT_CF64>, dim3((unsigned)tiles), dim3(kThreads), 0, e->stream, a); break;
-            }
+            with_fmt(e->iq_fmt, [&](auto fmt) {
+                hipLaunchKernelGGL(cancel_kernel<decltype(fmt)::value>, dim3((unsigned)tiles), dim3(kThreads), 0, e->stream, a);
+            });
             SDR_HIP(hipGetLastError());
         }
     }

@@ -157,9 +157,9 @@ __global__ __launch_bounds__(256) void synth_kernel(T* __restrict__ ring, int64_
         im += r * sn;
     }
     int64_t slot = n % capacity;
-    if constexpr (sizeof(T) == 1) {     // (a ci8 ring holds its bytes with the sign bit flipped: correlator.h kCi8Flip)
-        ring[2 * slot] = (T)(quantise<T>(re) ^ (T)0x80);
-        ring[2 * slot + 1] = (T)(quantise<T>(im) ^ (T)0x80);
+    if constexpr (sizeof(T) == 1) {     // (a ci8 ring holds its bytes with the sign bit flipped: ring_format.h kCi8Flip)
+        ring[2 * slot] = (T)(quantise<T>(re) ^ (T)sdr::kCi8Flip);
+        ring[2 * slot + 1] = (T)(quantise<T>(im) ^ (T)sdr::kCi8Flip);
     } else {
         ring[2 * slot] = quantise<T>(re);
         ring[2 * slot + 1] = quantise<T>(im);

@@ -103,7 +103,7 @@ __global__ __launch_bounds__(kThreads) void corr_profile_kernel(const void* __re
                 // Unaligned on purpose: an epoch starts at any sample, so these 16-byte loads are aligned to the sample size
                 // only (2 B for ci8).  gfx950's global path serves them (correlator.h single_load relies on the same: "16-byte
                 // loads from any 2-byte aligned address"); aligning the lanes to the ring instead would need a head pass through
-                // load_one in every segment and a prefix array that starts inside a lane's 16 samples.
+                // ring_read in every segment and a prefix array that starts inside a lane's 16 samples.
                 if (pos + kPerLane <= capacity) {   // (what lies behind the epoch's end is still inside the ring)
                     Raw8<FMT> raw[2];
                     raw[0].load(ring, pos);
@@ -121,9 +121,8 @@ __global__ __launch_bounds__(kThreads) void corr_profile_kernel(const void* __re
                         wr[j] = wi[j] = 0.0;
                         if (j < v) {
                             const int64_t pj = pos + j >= capacity ? pos + j - capacity : pos + j;
-                            double ar, ai;
-                            load_one<FMT>(ring, pj, ar, ai);
-                            wipe(j, ar, ai);
+                            const double2 x = ring_read<FMT>(ring, pj);
+                            wipe(j, x.x, x.y);
                         }
                     }
                 }
@@ -284,13 +283,7 @@ int sdr_corr_profile(sdr_engine* e, const sdr_epl_item* items, int n_items, doub
     CorrItemDev* d_items = (CorrItemDev*)e->corr_ws.ptr;
     double2* d_out = (double2*)((char*)e->corr_ws.ptr + b_items);
 
-    const void* kernel = nullptr;
-    switch (e->iq_fmt) {
-        case SDR_FMT_CI8: kernel = kernel_of<SDR_FMT_CI8>(per_sample); break;
-        case SDR_FMT_CI16: kernel = kernel_of<SDR_FMT_CI16>(per_sample); break;
-        case SDR_FMT_CF32: kernel = kernel_of<SDR_FMT_CF32>(per_sample); break;
-        default: kernel = kernel_of<SDR_FMT_CF64>(per_sample); break;
-    }
+    const void* kernel = sdr::with_fmt(e->iq_fmt, [&](auto fmt) { return kernel_of<decltype(fmt)::value>(per_sample); });
     const size_t shmem = kFixedLds + round16((size_t)max_len);
     // (above the 64 KB a kernel gets unasked: raised once per kernel of this engine, and again only for a longer code)
     size_t& lds_allowed = e->corr_lds_allowed[(e->iq_fmt & 3) * 2 + (per_sample ? 1 : 0)];

@@ -44,15 +44,8 @@ __device__ __forceinline__ double uniform(double x) {
     return __hiloint2double(hi, lo);
 }
 
-// A ci8 ring holds its samples with the sign bit of every byte flipped (u = x + 128 as an unsigned byte: "offset binary") --
-// the form the straight-line correlators build their doubles from with one v_perm_b32 per component (correlator_chip.h
-// biased_sample).  Round 6: that IS the ring, not an image beside it -- the engine flips where samples enter (uploads, the
-// ingest kernels, the synthesiser) and flips back where they leave (sdr_iq_download); every other reader takes the bits back
-// with one exclusive or per dword of two samples, here.
-constexpr uint32_t kCi8Flip = 0x80808080u;
-__device__ __forceinline__ int ci8_native(int w) { return w ^ (int)kCi8Flip; }
-
-// Load 8 consecutive ring samples starting at aligned position `pos` and widen to fp64.
+// Load 8 consecutive ring samples starting at aligned position `pos` and widen to fp64 (a ci8 ring's bytes are sign-flipped:
+// ring_format.h kCi8Flip).
 template <int FMT>
 struct Loader;
 
@@ -138,28 +131,6 @@ __host__ __device__ __forceinline__ double carrier_step(double carrier_hz, doubl
     return w / fs;
 }
 
-// One ring sample, widened to fp64 (edge samples only).
-template <int FMT>
-__device__ __forceinline__ void load_one(const void* ring, int64_t pos, double& xr, double& xi) {
-    if (FMT == SDR_FMT_CI8) {
-        const char2 v = static_cast<const char2*>(ring)[pos];
-        xr = (double)(int8_t)(v.x ^ 0x80);
-        xi = (double)(int8_t)(v.y ^ 0x80);
-    } else if (FMT == SDR_FMT_CI16) {
-        const short2 v = static_cast<const short2*>(ring)[pos];
-        xr = (double)v.x;
-        xi = (double)v.y;
-    } else if (FMT == SDR_FMT_CF32) {
-        const float2 v = static_cast<const float2*>(ring)[pos];
-        xr = (double)v.x;
-        xi = (double)v.y;
-    } else {
-        const double2 v = static_cast<const double2*>(ring)[pos];
-        xr = v.x;
-        xi = v.y;
-    }
-}
-
 // The few samples of an epoch that do not fill a whole aligned group -- [0, head_end) and
 // [tail_start, n), at most 2*(group-1) of them -- are correlated one per lane with the plain
 // per-sample form of the reference arithmetic, in a single pass of the first wave.  (Routing them
@@ -175,8 +146,8 @@ __device__ __forceinline__ void edge_samples(const void* __restrict__ ring, int6
     // base >= 0: the ring position of the epoch's first sample, from a caller whose epoch does not wrap (a 64-bit
     // modulo is ~60 instructions)
     int64_t pos = base >= 0 ? base + i : (ep.start_sample + i) % capacity;
-    double xr, xi;
-    load_one<FMT>(ring, pos, xr, xi);
+    const double2 x = ring_read<FMT>(ring, pos);
+    const double xr = x.x, xi = x.y;
     double sn, cs;
     sincos_reduced(__builtin_fma(-(double)i, dphi, ep.rem_carrier), &sn, &cs);
     const double zr = __builtin_fma(-xi, sn, xr * cs);

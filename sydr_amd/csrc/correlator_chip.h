@@ -82,7 +82,7 @@ __device__ __forceinline__ int wave_min_i32(int x) {
 }
 
 // int8 -> fp64 in ONE instruction, with a known offset.  v_perm_b32 drops a sample byte (sign bit flipped: u = x + 128;
-// a ci8 ring holds its bytes that way, correlator.h kCi8Flip)
+// a ci8 ring holds its bytes that way, ring_format.h kCi8Flip)
 // into bits 8..15 of the high word 0x40B0_0000 of a double whose low word is zero: that double is 4096 + u = 4224 + x,
 // exactly.  The straight-line kernels mix THESE into their running sums (against 2 instructions for
 // v_bfe_i32 + v_cvt_f64_i32: the conversion was half of the 8-instruction floor per sample) and take the offset's share
@@ -848,7 +848,7 @@ __device__ __forceinline__ bool correlate_epoch_chip(const void* __restrict__ ri
                 // block's fraction, taken HERE: a flag made when the block was prepared is a lane mask in a scalar register pair
                 // for the length of a block, two blocks in flight, beside the 52 scalar registers of the rotations -- which then
                 // spill through v_readlane.  A block that went through the exact re-evaluation brings its flags as integers.
-                constexpr uint32_t kNoSample = 0x80808080u;
+                constexpr uint32_t kNoSample = kCi8Flip;   // (two samples of 0 + 0j as the ring holds them)
                 constexpr int kWordS = (kHalf - 1) >> 1, kWordM = KM >> 1;
                 bool dnf = false, swf = false;
                 if constexpr (kWalk) {

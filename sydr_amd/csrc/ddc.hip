@@ -113,24 +113,6 @@ __device__ __forceinline__ double2 ddc_mixed_input(const Filter& filter, const L
     return make_double2(xr * c + xi * s, xi * c - xr * s);
 }
 
-// An output into the ring (or the mitigator's work buffer) in its format, a ci8 ring's bytes sign-flipped.
-__device__ __forceinline__ void ddc_store(void* __restrict__ ring, int out_fmt, int64_t pos, double ar, double ai) {
-    switch (out_fmt) {
-        case SDR_FMT_CI8: {
-            const int re = (int)ddc_clip_rint(ar, 127.0), im = (int)ddc_clip_rint(ai, 127.0);
-            ((uint16_t*)ring)[pos] = (uint16_t)((((unsigned)re & 0xffu) | (((unsigned)im & 0xffu) << 8)) ^ 0x8080u);
-            break;
-        }
-        case SDR_FMT_CI16: {
-            const int re = (int)ddc_clip_rint(ar, 32767.0), im = (int)ddc_clip_rint(ai, 32767.0);
-            ((uint32_t*)ring)[pos] = ((unsigned)re & 0xffffu) | (((unsigned)im & 0xffffu) << 16);
-            break;
-        }
-        case SDR_FMT_CF32: ((float2*)ring)[pos] = make_float2((float)ar, (float)ai); break;
-        default: ((double2*)ring)[pos] = make_double2(ar, ai); break;
-    }
-}
-
 // THE converter kernel, over (filter, loader).  One workgroup per tile of outputs.  Phase 1: the tile's inputs, each loaded and
 // mixed once, into LDS as fp64 complex.  Phase 2: a lane per output, the filter's tap loop, the store.  With a mitigator attached
 // `ring` is its linear cf64 work buffer.
@@ -146,7 +128,7 @@ __device__ __forceinline__ void ddc_convert_body(double2* z, const void* __restr
     __syncthreads();
     for (int o = threadIdx.x; o < t.count; o += kDdcThreads) {
         const double2 a = filter.output(t, o, z, taps, gain);
-        ddc_store(ring, out_fmt, ddc_ring_pos(ring_offset, t.i0 + o, capacity), a.x, a.y);
+        ring_write(ring, out_fmt, ddc_ring_pos(ring_offset, t.i0 + o, capacity), a.x, a.y);   // (the ring, or the mitigator's work buffer)
     }
 }
 

@@ -205,8 +205,6 @@ inline void ddc_with_loader(const sdr_ddc* d, F&& f) {
     }
 }
 
-__device__ __forceinline__ double ddc_clip_rint(double v, double lim) { return fmin(fmax(rint(v), -lim), lim); }
-
 inline int ddc_check(sdr_engine* e, const sdr_ddc* d) {
     if (!d) return sdr_fail(SDR_ERR_INVALID, "converter is NULL");
     if (d->engine != e) return sdr_fail(SDR_ERR_INVALID, "the converter belongs to another engine");

@@ -121,9 +121,8 @@ __global__ __launch_bounds__(kThreads) void ddm_segments_kernel(const void* __re
                         wr[j] = wi[j] = 0.0;
                         if (j < v) {
                             const int64_t pj = pos + j >= capacity ? pos + j - capacity : pos + j;
-                            double ar, ai;
-                            load_one<FMT>(ring, pj, ar, ai);
-                            wipe(j, ar, ai);
+                            const double2 x = ring_read<FMT>(ring, pj);
+                            wipe(j, x.x, x.y);
                         }
                     }
                 }
@@ -411,13 +410,7 @@ int sdr_ddm(sdr_engine* e, const sdr_epl_item* items, int n_items, const sdr_ddm
     double* d_map = (double*)(ws + b_items + b_z);
     sdr_ddm_result* d_res = (sdr_ddm_result*)(ws + b_items + b_z + b_map);
 
-    const void* kernel = nullptr;
-    switch (e->iq_fmt) {
-        case SDR_FMT_CI8: kernel = kernel_of<SDR_FMT_CI8>(per_sample); break;
-        case SDR_FMT_CI16: kernel = kernel_of<SDR_FMT_CI16>(per_sample); break;
-        case SDR_FMT_CF32: kernel = kernel_of<SDR_FMT_CF32>(per_sample); break;
-        default: kernel = kernel_of<SDR_FMT_CF64>(per_sample); break;
-    }
+    const void* kernel = sdr::with_fmt(e->iq_fmt, [&](auto fmt) { return kernel_of<decltype(fmt)::value>(per_sample); });
     const size_t shmem = kFixedLds + round16((size_t)max_len);
     // (above the 64 KB a kernel gets unasked: raised once per kernel of this engine, and again only for a longer code)
     size_t& lds_allowed = e->ddm_lds_allowed[(e->iq_fmt & 3) * 2 + (per_sample ? 1 : 0)];

@@ -157,7 +157,7 @@ int sdr_iq_order_reader(sdr_engine* e, StreamCtx* ctx) {
     return SDR_OK;
 }
 
-// A ci8 ring holds its samples with the sign bit of every byte flipped (correlator.h kCi8Flip): bytes [lo, hi) of the ring,
+// A ci8 ring holds its samples with the sign bit of every byte flipped (ring_format.h kCi8Flip): bytes [lo, hi) of the ring,
 // just copied in as the host has them, flipped in place -- whole 16-byte granules inside the range, byte by byte at its ends.
 __global__ __launch_bounds__(256) void flip_range_kernel(uint4* __restrict__ ring, size_t lo, size_t hi) {
     const size_t g0 = lo / 16, g1 = (hi + 15) / 16;
@@ -166,11 +166,11 @@ __global__ __launch_bounds__(256) void flip_range_kernel(uint4* __restrict__ rin
         uint4 v = ring[g];
         const size_t b = g * 16;
         if (b >= lo && b + 16 <= hi) {
-            v.x ^= 0x80808080u, v.y ^= 0x80808080u, v.z ^= 0x80808080u, v.w ^= 0x80808080u;
+            v.x ^= sdr::kCi8Flip, v.y ^= sdr::kCi8Flip, v.z ^= sdr::kCi8Flip, v.w ^= sdr::kCi8Flip;
         } else {
             uint32_t w[4] = {v.x, v.y, v.z, v.w};
             for (int i = 0; i < 16; ++i)
-                if (b + (size_t)i >= lo && b + (size_t)i < hi) w[i >> 2] ^= 0x80u << (8 * (i & 3));
+                if (b + (size_t)i >= lo && b + (size_t)i < hi) w[i >> 2] ^= (sdr::kCi8Flip & 0xffu) << (8 * (i & 3));
             v.x = w[0], v.y = w[1], v.z = w[2], v.w = w[3];
         }
         ring[g] = v;
@@ -190,8 +190,6 @@ __global__ __launch_bounds__(256) void ingest_kernel(const uint4* __restrict__ s
         ring[d] = v;
     }
 }
-
-static inline uint32_t ring_flip_mask(const sdr_engine* e) { return e->iq_fmt == SDR_FMT_CI8 ? 0x80808080u : 0u; }
 
 
 // The calling thread onto the CPUs next to the engine's GPU (its PCI function's local_cpulist in sysfs).  A receiver tick
@@ -507,7 +505,7 @@ int sdr_iq_alloc(sdr_engine* e, int64_t capacity_samples, int fmt) {
         return sdr_fail(SDR_ERR_NOMEM, "hipMalloc(%zu) for the IQ ring failed: %s", bytes,
                         hipGetErrorString(err));
     }
-    SDR_HIP(hipMemsetAsync(e->iq, fmt == SDR_FMT_CI8 ? 0x80 : 0, bytes, e->stream));     // (zero samples: ci8 bytes are kept sign-flipped)
+    SDR_HIP(hipMemsetAsync(e->iq, sdr::ring_fill_byte(fmt), bytes, e->stream));     // (zero samples: ci8 bytes are kept sign-flipped)
     e->iq_capacity = capacity_samples;
     e->iq_fmt = fmt;
     return SDR_OK;
@@ -526,7 +524,8 @@ static int iq_copy(sdr_engine* e, void* host, int64_t n, int64_t off, bool uploa
     int64_t first = n < e->iq_capacity - off ? n : e->iq_capacity - off;
     char* dev = (char*)e->iq;
     char* h = (char*)host;
-    const bool ci8 = e->iq_fmt == SDR_FMT_CI8;
+    const uint32_t mask = sdr::ring_flip_mask(e->iq_fmt);
+    const bool ci8 = mask != 0;
     auto flip = [&](size_t lo, size_t hi) {      // (ci8: the bytes just copied in, into the ring's sign-flipped form)
         const size_t n16 = (hi + 15) / 16 - lo / 16;
         const unsigned blocks = (unsigned)(n16 / 256 / 4 + 1 < 8192 ? n16 / 256 / 4 + 1 : 8192);
@@ -557,10 +556,10 @@ static int iq_copy(sdr_engine* e, void* host, int64_t n, int64_t off, bool uploa
         for (; i + 8 <= nb; i += 8) {
             uint64_t w;
             memcpy(&w, b + i, 8);
-            w ^= 0x8080808080808080ull;
+            w ^= (uint64_t)mask << 32 | mask;
             memcpy(b + i, &w, 8);
         }
-        for (; i < nb; ++i) b[i] ^= 0x80;
+        for (; i < nb; ++i) b[i] ^= (unsigned char)mask;
     }
     return SDR_OK;
 }
@@ -616,7 +615,7 @@ int sdr_iq_flush_server_slab(sdr_engine* e) {
     const char* stage = (const char*)e->srv_slab_src;
     const size_t n16 = bytes / 16;
     const unsigned blocks = (unsigned)((n16 + 255) / 256 < 64 ? (n16 + 255) / 256 : 64);
-    hipLaunchKernelGGL(ingest_kernel, dim3(blocks), dim3(256), 0, e->stream, (const uint4*)stage, (uint4*)e->iq, n16, off_b / 16, cap_b / 16, ring_flip_mask(e));
+    hipLaunchKernelGGL(ingest_kernel, dim3(blocks), dim3(256), 0, e->stream, (const uint4*)stage, (uint4*)e->iq, n16, off_b / 16, cap_b / 16, sdr::ring_flip_mask(e->iq_fmt));
     SDR_HIP(hipGetLastError());
     if (half >= 0) {      // (a staging half: busy until the kernel has read it; the caller's own block is the caller's to keep)
         if (!e->slab_done[half]) SDR_HIP(hipEventCreateWithFlags(&e->slab_done[half], hipEventDisableTiming));
@@ -697,7 +696,7 @@ int sdr_iq_upload_async(sdr_engine* e, const void* iq, int64_t n_samples, int64_
             }
             const size_t n16 = bytes / 16;
             const unsigned blocks = (unsigned)((n16 + 255) / 256 < 64 ? (n16 + 255) / 256 : 64);
-            hipLaunchKernelGGL(ingest_kernel, dim3(blocks), dim3(256), 0, e->stream, (const uint4*)iq, (uint4*)e->iq, n16, off_b / 16, cap_b / 16, ring_flip_mask(e));
+            hipLaunchKernelGGL(ingest_kernel, dim3(blocks), dim3(256), 0, e->stream, (const uint4*)iq, (uint4*)e->iq, n16, off_b / 16, cap_b / 16, sdr::ring_flip_mask(e->iq_fmt));
             SDR_HIP(hipGetLastError());
             e->inplace_slab_in_flight = true;      // (sdr_bank_tick_mirrored_end waits for it where nothing else would)
             return SDR_OK;
@@ -731,7 +730,7 @@ int sdr_iq_upload_async(sdr_engine* e, const void* iq, int64_t n_samples, int64_
             const size_t n16 = bytes / 16;
             const unsigned blocks = (unsigned)((n16 + 255) / 256 < 64 ? (n16 + 255) / 256 : 64);
             hipLaunchKernelGGL(ingest_kernel, dim3(blocks), dim3(256), 0, e->stream, (const uint4*)stage, (uint4*)e->iq, n16,
-                               off_b / 16, cap_b / 16, ring_flip_mask(e));
+                               off_b / 16, cap_b / 16, sdr::ring_flip_mask(e->iq_fmt));
             SDR_HIP(hipGetLastError());
             SDR_HIP(hipEventRecord(e->slab_done[half], e->stream));
             e->slab_busy[half] = true;

@@ -13,6 +13,7 @@
 
 #include "../../include/sydr_amd.h"
 #include "pcps_fused_work.h"
+#include "ring_format.h"
 
 // Thread-local error text behind sdr_last_error().
 void sdr_set_error(const char* fmt, ...);
@@ -233,16 +234,6 @@ int sdr_slab_half_acquire(sdr_engine* e, size_t bytes, int* half, char** stage);
 void sdr_iq_mark_written(sdr_engine* e, int64_t ring_offset, int64_t n_samples);
 // A launch on ctx's stream that reads the ring: behind every ring write queued on the engine's own stream so far.
 int sdr_iq_order_reader(sdr_engine* e, StreamCtx* ctx);
-
-static inline size_t sdr_fmt_bytes(int fmt) {
-    switch (fmt) {
-        case SDR_FMT_CI8: return 2;
-        case SDR_FMT_CI16: return 4;
-        case SDR_FMT_CF32: return 8;
-        case SDR_FMT_CF64: return 16;
-    }
-    return 0;
-}
 
 // RAII bracket: records hipEvents around a launch when profiling is on.
 struct ProfScope {

@@ -839,7 +839,7 @@ int sdr_epl_plan_run_range_on(sdr_engine* e, sdr_epl_plan* p, int64_t first, int
                         (long long)(first + count), p->n_items);
     if (p->doubled)
         if (int rc = ensure_doubled_luts(e, ctx->stream)) return rc;   // (a slot may have been re-staged since the plan was made)
-    // (the straight-line kernels build their doubles from sign-flipped bytes: a ci8 ring holds them that way -- correlator.h kCi8Flip)
+    // (the straight-line kernels build their doubles from sign-flipped bytes: a ci8 ring holds them that way -- ring_format.h kCi8Flip)
     if (int rc = sdr_iq_order_reader(e, ctx)) return rc;      // (behind the uploads queued on the engine's stream so far)
     const sdr_epl_item* items = p->d_items + first;
     double* out = p->d_out + (size_t)first * 2 * p->n_taps;
@@ -855,13 +855,10 @@ int sdr_epl_plan_run_range_on(sdr_engine* e, sdr_epl_plan* p, int64_t first, int
             const size_t shmem = 8 * sizeof(uint32_t) + (size_t)((p->lut_words + 3) & ~3) * sizeof(uint32_t);
             ops->launch(st, shmem, e->iq, e->iq_capacity, items, n, e->luts, p->lut_words, e->lut_stride, p->d_spacing, p->fs, out, setups, xcd_run);
         } else {
-            int rc;
-            switch (e->iq_fmt) {
-                case SDR_FMT_CI8: rc = launch_fmt<SDR_FMT_CI8>(e, st, items, n, p->d_spacing, p->fs, p->n_taps, p->lut_words, p->wide, p->group_stride, p->doubled, out, setups, xcd_run); break;
-                case SDR_FMT_CI16: rc = launch_fmt<SDR_FMT_CI16>(e, st, items, n, p->d_spacing, p->fs, p->n_taps, p->lut_words, p->wide, p->group_stride, p->doubled, out, setups, xcd_run); break;
-                case SDR_FMT_CF32: rc = launch_fmt<SDR_FMT_CF32>(e, st, items, n, p->d_spacing, p->fs, p->n_taps, p->lut_words, p->wide, p->group_stride, p->doubled, out, setups, xcd_run); break;
-                default: rc = launch_fmt<SDR_FMT_CF64>(e, st, items, n, p->d_spacing, p->fs, p->n_taps, p->lut_words, p->wide, p->group_stride, p->doubled, out, setups, xcd_run); break;
-            }
+            const int rc = with_fmt(e->iq_fmt, [&](auto fmt) {
+                return launch_fmt<decltype(fmt)::value>(e, st, items, n, p->d_spacing, p->fs, p->n_taps, p->lut_words, p->wide, p->group_stride,
+                                                        p->doubled, out, setups, xcd_run);
+            });
             if (rc) return rc;
         }
     }

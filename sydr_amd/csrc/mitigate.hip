@@ -44,26 +44,6 @@ namespace {
 
 constexpr int kCounterHead = 2;
 
-__device__ __forceinline__ double mit_clip_rint(double v, double lim) { return fmin(fmax(rint(v), -lim), lim); }
-
-// The ring's formats exactly as ddc_kernel stores them (a ci8 ring's bytes sign-flipped).
-__device__ __forceinline__ void mit_store(void* __restrict__ ring, int out_fmt, int64_t pos, double ar, double ai) {
-    switch (out_fmt) {
-        case SDR_FMT_CI8: {
-            const int re = (int)mit_clip_rint(ar, 127.0), im = (int)mit_clip_rint(ai, 127.0);
-            ((uint16_t*)ring)[pos] = (uint16_t)((((unsigned)re & 0xffu) | (((unsigned)im & 0xffu) << 8)) ^ 0x8080u);
-            break;
-        }
-        case SDR_FMT_CI16: {
-            const int re = (int)mit_clip_rint(ar, 32767.0), im = (int)mit_clip_rint(ai, 32767.0);
-            ((uint32_t*)ring)[pos] = ((unsigned)re & 0xffffu) | (((unsigned)im & 0xffffu) << 16);
-            break;
-        }
-        case SDR_FMT_CF32: ((float2*)ring)[pos] = make_float2((float)ar, (float)ai); break;
-        default: ((double2*)ring)[pos] = make_double2(ar, ai); break;
-    }
-}
-
 __device__ __forceinline__ int wave_add_int(int v) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
@@ -185,7 +165,7 @@ __global__ __launch_bounds__(kMitThreads) void mit_combine_kernel(const double2*
         }
     }
     const int64_t pos = ring_offset + i;
-    mit_store(ring, out_fmt, pos >= capacity ? pos - capacity : pos, yr, yi);
+    ring_write(ring, out_fmt, pos >= capacity ? pos - capacity : pos, yr, yi);
 }
 
 // b grows to `bytes`, its first `keep` bytes kept (the state when a push is longer than any before it).

@@ -168,22 +168,6 @@ struct Butterfly<8, INV> {
     }
 };
 
-template <int FMT>
-__device__ __forceinline__ double2 ring_sample(const void* ring, int64_t pos) {
-    if (FMT == SDR_FMT_CI8) {
-        const char2 v = static_cast<const char2*>(ring)[pos];      // (sign-flipped bytes: correlator.h kCi8Flip)
-        return make_double2((double)(int8_t)(v.x ^ 0x80), (double)(int8_t)(v.y ^ 0x80));
-    } else if (FMT == SDR_FMT_CI16) {
-        const short2 v = static_cast<const short2*>(ring)[pos];
-        return make_double2((double)v.x, (double)v.y);
-    } else if (FMT == SDR_FMT_CF32) {
-        const float2 v = static_cast<const float2*>(ring)[pos];
-        return make_double2((double)v.x, (double)v.y);
-    } else {
-        return static_cast<const double2*>(ring)[pos];
-    }
-}
-
 template <int LOAD, int FMT, bool INV>
 __device__ __forceinline__ double2 load_elem(const PassArgs& a, int batch, int idx) {
     if (LOAD == LOAD_PLAIN) {
@@ -195,7 +179,7 @@ __device__ __forceinline__ double2 load_elem(const PassArgs& a, int batch, int i
         const int blk = a.iq_blocks > 0 ? batch / a.iq_blocks : 0;
         batch -= blk * a.iq_blocks;
         int64_t pos = (a.first_sample + (int64_t)blk * a.N + idx) % a.capacity;
-        double2 x = ring_sample<FMT>(a.ring, pos);
+        double2 x = sdr::ring_read<FMT>(a.ring, pos);
         double bin = a.bin_start + (double)batch * a.bin_delta;
         double freq = a.if_hz - bin;
         int64_t m = a.carrier_offset + idx;
@@ -1754,13 +1738,7 @@ static int pcps_impl(sdr_engine* e, const int32_t* code_slots, const double* cod
     {
         // (one event pair around every kernel of the search: its in-stream time; while it records, the search stays on one stream)
         ProfScope whole(e, "call_pcps");
-        auto search = [&](auto fmt) { return pcps_search<decltype(fmt)::value>(e, p, c); };
-        switch (e->iq_fmt) {
-            case SDR_FMT_CI8: rc = search(std::integral_constant<int, SDR_FMT_CI8>{}); break;
-            case SDR_FMT_CI16: rc = search(std::integral_constant<int, SDR_FMT_CI16>{}); break;
-            case SDR_FMT_CF32: rc = search(std::integral_constant<int, SDR_FMT_CF32>{}); break;
-            default: rc = search(std::integral_constant<int, SDR_FMT_CF64>{}); break;
-        }
+        rc = sdr::with_fmt(e->iq_fmt, [&](auto fmt) { return pcps_search<decltype(fmt)::value>(e, p, c); });
     }
     if (rc) {
         // a search that stopped half way: what the code-spectra buffer holds is unknown, and a sweep may still be
@@ -2003,7 +1981,7 @@ __global__ __launch_bounds__(kThreads) void ss_chipsum_kernel(const void* __rest
             const int u = (int)trunc(v);
             if (u < m) continue;
             if (u > m) break;
-            const double2 x = ring_sample<FMT>(ring, (first_sample + n) % capacity);
+            const double2 x = sdr::ring_read<FMT>(ring, (first_sample + n) % capacity);
             double pp = (double)((int64_t)n * 2) * M_PI;
             pp = pp / fs;
             double s, c;
@@ -2159,12 +2137,7 @@ int sdr_serial_search(sdr_engine* e, const int32_t* code_slots, int n_prn, int64
         const int64_t first = start_sample + (int64_t)k * N;
         {
             ProfScope ps(e, "ss_chipsum");
-            switch (e->iq_fmt) {
-                case SDR_FMT_CI8: ss_launch_chipsum<SDR_FMT_CI8>(e, first, N, L, fs, bin_start, bin_delta, nbins, A); break;
-                case SDR_FMT_CI16: ss_launch_chipsum<SDR_FMT_CI16>(e, first, N, L, fs, bin_start, bin_delta, nbins, A); break;
-                case SDR_FMT_CF32: ss_launch_chipsum<SDR_FMT_CF32>(e, first, N, L, fs, bin_start, bin_delta, nbins, A); break;
-                default: ss_launch_chipsum<SDR_FMT_CF64>(e, first, N, L, fs, bin_start, bin_delta, nbins, A); break;
-            }
+            sdr::with_fmt(e->iq_fmt, [&](auto fmt) { ss_launch_chipsum<decltype(fmt)::value>(e, first, N, L, fs, bin_start, bin_delta, nbins, A); });
         }
         {
             ProfScope ps(e, "ss_correlate");

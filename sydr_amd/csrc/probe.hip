@@ -70,19 +70,19 @@ template <int FMT>
 struct IntFmt;
 template <>
 struct IntFmt<SDR_FMT_CI8> {
-    static constexpr int kSpg = 8, kLo = -128, kHi = 127;
+    static constexpr int kSpg = ring_granule_samples(SDR_FMT_CI8), kLo = -128, kHi = 127;
     typedef int wide;
     static __device__ __forceinline__ void get(const uint4& v, int j, int& xi, int& xq) {
         const unsigned w = (j >> 1) == 0 ? v.x : (j >> 1) == 1 ? v.y : (j >> 1) == 2 ? v.z : v.w;
         const unsigned h = (j & 1) ? w >> 16 : w;
-        xi = (int)(h & 0xffu) - 128;   // (the ring's bytes are u = x + 128)
-        xq = (int)((h >> 8) & 0xffu) - 128;
+        xi = (int)(h & 0xffu) - ring_fill_byte(SDR_FMT_CI8);   // (the ring's bytes are u = x + 128)
+        xq = (int)((h >> 8) & 0xffu) - ring_fill_byte(SDR_FMT_CI8);
     }
     static __device__ __forceinline__ int bin(int x, int) { return x + 128; }   // the stored byte IS the bin
 };
 template <>
 struct IntFmt<SDR_FMT_CI16> {
-    static constexpr int kSpg = 4, kLo = -32768, kHi = 32767;
+    static constexpr int kSpg = ring_granule_samples(SDR_FMT_CI16), kLo = -32768, kHi = 32767;
     typedef long long wide;
     static __device__ __forceinline__ void get(const uint4& v, int j, int& xi, int& xq) {
         const int w = (int)(j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w);
@@ -223,7 +223,7 @@ __global__ __launch_bounds__(kThreads) void probe_moments_int_kernel(const uint4
 template <int FMT>
 __global__ __launch_bounds__(kThreads) void probe_moments_float_kernel(const uint4* __restrict__ ring, ProbeWindow W,
                                                                         ProbeDev* __restrict__ dev, double* __restrict__ slab) {
-    constexpr int kSpg = FMT == SDR_FMT_CF32 ? 2 : 1;
+    constexpr int kSpg = ring_granule_samples(FMT);
     extern __shared__ __attribute__((aligned(16))) char probe_lds[];
     double* scratch = reinterpret_cast<double*>(probe_lds);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -320,11 +320,10 @@ __global__ __launch_bounds__(kThreads) void probe_psd_kernel(const void* __restr
     bool bad = false;
     for (int64_t s = blockIdx.x; s < n_seg; s += gridDim.x) {
         for (int j = tid; j < nfft; j += kThreads) {
-            double xr, xi;
-            load_one<FMT>(ring, probe_segment_sample(base, capacity, s, nfft, j), xr, xi);
-            bad |= !(finite64(xr) && finite64(xi));
+            const double2 v = ring_read<FMT>(ring, probe_segment_sample(base, capacity, s, nfft, j));
+            bad |= !(finite64(v.x) && finite64(v.y));
             const double w = win[j];
-            x[j] = make_double2(w * xr, w * xi);
+            x[j] = make_double2(w * v.x, w * v.y);
         }
         __syncthreads();
         fft_lds_forward<kThreads>(x, nfft, tw, tid);   // X[k] ends at position bitrev(k)
@@ -403,7 +402,7 @@ int sdr_iq_probe(sdr_engine* e, int64_t start_sample, int64_t n_samples, int his
         return sdr_fail(SDR_ERR_RANGE, "a window of %lld samples, ring holds %lld", (long long)n_samples, (long long)e->iq_capacity);
 
     const int64_t base = start_sample % e->iq_capacity;
-    const int spg = (int)(16 / sdr_fmt_bytes(fmt));
+    const int spg = sdr::ring_granule_samples(fmt);
     const ProbeWindow W = probe_window(base, n_samples, e->iq_capacity, spg);
     // (with a histogram fewer, longer-lived workgroups: each flushes up to 512 bins)
     const int64_t want = (W.total + kThreads * 4 - 1) / (kThreads * 4);
@@ -456,13 +455,7 @@ int sdr_iq_probe(sdr_engine* e, int64_t start_sample, int64_t n_samples, int his
         }
         if (psd) {
             ProfScope ps(e, "probe_psd_kernel");
-            const void* kernel = nullptr;
-            switch (fmt) {
-                case SDR_FMT_CI8: kernel = (const void*)probe_psd_kernel<SDR_FMT_CI8>; break;
-                case SDR_FMT_CI16: kernel = (const void*)probe_psd_kernel<SDR_FMT_CI16>; break;
-                case SDR_FMT_CF32: kernel = (const void*)probe_psd_kernel<SDR_FMT_CF32>; break;
-                default: kernel = (const void*)probe_psd_kernel<SDR_FMT_CF64>; break;
-            }
+            const void* kernel = sdr::with_fmt(fmt, [](auto f) { return (const void*)probe_psd_kernel<decltype(f)::value>; });
             const void* ring = e->iq;
             int64_t capacity = e->iq_capacity, b = base, ns = n_seg;
             const double2* tw = (const double2*)e->probe_tab.ptr;

@@ -237,16 +237,10 @@ int sdr_acq_refine(sdr_engine* e, const sdr_refine_item* items, int n_items, dou
             ProfScope ps(e, "refine_segments");
             const dim3 grid((unsigned)(n_items * M * S)), block(64);
             const size_t shmem = (size_t)((max_words + 3) & ~3) * sizeof(uint32_t);
-            auto launch = [&](auto kernel) {
-                hipLaunchKernelGGL(kernel, grid, block, shmem, e->stream, (const void*)e->iq, e->iq_capacity, d_items, M, S, e->luts,
-                                   e->lut_stride, fs, d_z);
-            };
-            switch (e->iq_fmt) {
-                case SDR_FMT_CI8: launch(refine_segments_kernel<SDR_FMT_CI8>); break;
-                case SDR_FMT_CI16: launch(refine_segments_kernel<SDR_FMT_CI16>); break;
-                case SDR_FMT_CF32: launch(refine_segments_kernel<SDR_FMT_CF32>); break;
-                default: launch(refine_segments_kernel<SDR_FMT_CF64>); break;
-            }
+            with_fmt(e->iq_fmt, [&](auto fmt) {
+                hipLaunchKernelGGL(refine_segments_kernel<decltype(fmt)::value>, grid, block, shmem, e->stream, (const void*)e->iq,
+                                   e->iq_capacity, d_items, M, S, e->luts, e->lut_stride, fs, d_z);
+            });
             SDR_HIP(hipGetLastError());
         }
         {

@@ -94,7 +94,7 @@ int launch_track(sdr_engine* e, StreamCtx* ctx, const TrackRun& r, int* parts_us
         if (take_slab && phase == 3) {
             const size_t sb = sdr_fmt_bytes(e->iq_fmt);
             srv_arg.ring16 = (uint4*)e->iq;
-            srv_arg.ring_flip = e->iq_fmt == SDR_FMT_CI8 ? sdr::kCi8Flip : 0u;
+            srv_arg.ring_flip = sdr::ring_flip_mask(e->iq_fmt);
             srv_arg.ring_n16 = (unsigned long long)((size_t)e->iq_capacity * sb / 16);
             srv_arg.ingest_src16 = (unsigned long long)((uintptr_t)e->srv_slab_src / 16);
             srv_arg.ingest_n16 = (unsigned long long)((size_t)e->srv_slab_n * sb / 16);
@@ -128,12 +128,7 @@ int launch_track(sdr_engine* e, StreamCtx* ctx, const TrackRun& r, int* parts_us
                 else launch(track_kernel<F, 512, 2, 3>);
             }
         };
-        switch (e->iq_fmt) {
-            case SDR_FMT_CI8: by_shape(std::integral_constant<int, SDR_FMT_CI8>{}); break;
-            case SDR_FMT_CI16: by_shape(std::integral_constant<int, SDR_FMT_CI16>{}); break;
-            case SDR_FMT_CF32: by_shape(std::integral_constant<int, SDR_FMT_CF32>{}); break;
-            default: by_shape(std::integral_constant<int, SDR_FMT_CF64>{}); break;
-        }
+        sdr::with_fmt(e->iq_fmt, by_shape);
         return err;
     };
 
@@ -862,7 +857,7 @@ static int tick_server_start(sdr_engine* e, sdr_bank* b, const int32_t* channels
     a.dev = (TickServerDev*)s->dev.ptr;
     a.go = (unsigned*)dp;
     a.ring16 = (uint4*)e->iq;
-    a.ring_flip = e->iq_fmt == SDR_FMT_CI8 ? sdr::kCi8Flip : 0u;
+    a.ring_flip = sdr::ring_flip_mask(e->iq_fmt);
     a.ring_n16 = (unsigned long long)((size_t)e->iq_capacity * sdr_fmt_bytes(e->iq_fmt) / 16);
     a.rec_out = (sdr_track_epoch*)(dp + go_bytes);
     int32_t* d_map = (int32_t*)(dp + go_bytes + (size_t)n * sizeof(sdr_track_epoch));

@@ -20,10 +20,5 @@ hipError_t sdr_track_dense_launch(int fmt, int n_taps, int n_ch, size_t shmem, h
         constexpr int F = decltype(fmt_c)::value;
         return n_taps == 5 ? launch(track_kernel<F, 256, 3, 5>) : launch(track_kernel<F, 256, 3, 3>);
     };
-    switch (fmt) {
-        case SDR_FMT_CI8: return by_taps(std::integral_constant<int, SDR_FMT_CI8>{});
-        case SDR_FMT_CI16: return by_taps(std::integral_constant<int, SDR_FMT_CI16>{});
-        case SDR_FMT_CF32: return by_taps(std::integral_constant<int, SDR_FMT_CF32>{});
-        default: return by_taps(std::integral_constant<int, SDR_FMT_CF64>{});
-    }
+    return sdr::with_fmt(fmt, by_taps);
 }

@@ -104,7 +104,7 @@ struct TickServer {
     unsigned* go;                  // device [n_ch * kGoStride]: channel c's release word (the request its cluster may work on; kServerStop: leave)
     uint4* ring16;
     unsigned long long ring_n16;
-    unsigned ring_flip;            // what a slab's dwords are xor-ed with on their way into the ring (ci8: every sign bit, correlator.h kCi8Flip)
+    unsigned ring_flip;            // what a slab's dwords are xor-ed with on their way into the ring (ring_format.h ring_flip_mask)
     sdr_track_epoch* rec_out;      // device [n_ch]: where the roles write the epoch's record
     // page-locked, written by the channels themselves: the answer (state, record, 1 ran / 0 not ready / -1 stopped), then -- behind a
     // system-wide release -- the number of the request it answers

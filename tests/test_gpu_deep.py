@@ -11,7 +11,7 @@ import deep_cases as dc
 from oracle import sydr_oracle as orc
 from sydr_amd import _lib
 from sydr_amd.engine import FMT_CI8
-from test_gpu_pcps import MAP_RTOL
+from test_gpu_pcps import ALL_FMTS, FORMAT_GRID, MAP_RTOL, bits_per_ring_format
 from test_host_layer import KAPLAN_INI, channel_config, rf_signal
 
 pytestmark = pytest.mark.gpu
@@ -101,6 +101,17 @@ def test_two_calls_return_the_same_bits(engine):
     res3, none = _deep(engine, c, 2, rf=1e6, want_map=False)
     assert none is None and map1.tobytes() == map2.tobytes()
     assert res1.tobytes() == res2.tobytes() == res3.tobytes()
+
+
+def test_same_bits_from_every_ring_format(engine):
+    """C = 2, K = 2, G = 1: the fold kernel's load is the only code that knows the ring's format."""
+    def run(start):
+        res, cmap = engine.acq_deep(np.arange(2), start, 4e6, 0.0, *FORMAT_GRID, 2, 2, 1, 0.0, want_map=True)
+        assert cmap.shape == (2, 1, 5, 4000) and [int(r["peak_bin"]) for r in res] == [1, 4]
+        return res, cmap
+    bits = bits_per_ring_format(engine, 4, run)
+    for fmt in ALL_FMTS[1:]:
+        assert bits[fmt] == bits[FMT_CI8], f"ring format {fmt}"
 
 
 def test_long_window_keeps_its_peak(engine):

@@ -1,11 +1,13 @@
 """GPU parity: PCPS acquisition + two-peak comparison vs golden vectors captured from the
 reference (peak indices bit-exact, map values / ratio to 1e-9 relative) and vs the oracle."""
+import functools
+
 import numpy as np
 import pytest
 
 from conftest import load_golden
 from oracle import sydr_oracle as orc
-from sydr_amd.engine import FMT_CF64, FMT_CI8
+from sydr_amd.engine import FMT_CF32, FMT_CF64, FMT_CI16, FMT_CI8
 
 pytestmark = pytest.mark.gpu
 
@@ -74,6 +76,52 @@ def test_pcps_full_map_vs_oracle_with_ring_offset(engine):
         peak, ratio = orc.two_peak_compare(ref, n, 4)
         assert [int(pb[k]), int(pc[k])] == peak
         assert pr[k] == pytest.approx(ratio, rel=1e-9)
+
+
+ALL_FMTS = (FMT_CI8, FMT_CI16, FMT_CF32, FMT_CF64)
+FORMAT_PRNS = (14, 2)
+FORMAT_GRID = (1000.0, 500.0)       # +-1000 Hz by 500 Hz: 5 bins
+
+
+@functools.lru_cache(maxsize=None)
+def _format_recording():
+    sats = [dict(prn=14, doppler=500.0, code_phase=512.3, phase=0.2, amp=7.0),
+            dict(prn=2, doppler=-1000.0, code_phase=100.6, phase=1.1, amp=6.0)]
+    raw = orc.synth_iq(4e6, 4 * 4000, sats, 20.0, 20260007)
+    raw.setflags(write=False)
+    return raw
+
+
+def bits_per_ring_format(engine, periods, run):
+    """The same int8-valued recording -- `periods` code periods at 4 MHz, N = 4000, PRNs 14 and 2 -- in a ring of exactly that
+    many samples of each of the four formats (iq_upload converts to the ring's element type), starting mid-ring so that every
+    read wraps: run(start) -> arrays, -> {format: their bytes}.  Small integers widen to the same doubles from every format
+    and everything behind the load is the same fp64 code (contraction off), so the bytes must be equal, not close."""
+    n = 4000 * periods
+    raw = _format_recording()[:2 * n]
+    start = n - 1896
+    ring = np.empty(2 * n, dtype=np.int8)
+    lin = np.arange(start, start + n) % n
+    ring[2 * lin] = raw[0::2]
+    ring[2 * lin + 1] = raw[1::2]
+    out = {}
+    for fmt in ALL_FMTS:
+        _stage(engine, ring, FORMAT_PRNS, fmt=fmt, capacity=n)
+        out[fmt] = b"".join(np.ascontiguousarray(a).tobytes() for a in run(start))
+    return out
+
+
+def test_pcps_same_bits_from_every_ring_format(engine):
+    """coh = 1, noncoh = 2 with the full map, and the indices of the map-free call."""
+    def run(start):
+        pb, pc, pr, cmap = engine.pcps([0, 1], start, 4e6, 0.0, *FORMAT_GRID, 1, 2, want_map=True)
+        assert cmap.shape == (2, 5, 4000) and [int(b) for b in pb] == [1, 4]     # (satellites at +500 and -1000 Hz)
+        pb2, pc2, _, none = engine.pcps([0, 1], start, 4e6, 0.0, *FORMAT_GRID, 1, 2)
+        assert none is None
+        return pb, pc, pr, cmap, pb2, pc2
+    bits = bits_per_ring_format(engine, 2, run)
+    for fmt in ALL_FMTS[1:]:
+        assert bits[fmt] == bits[FMT_CI8], f"ring format {fmt}"
 
 
 def test_pcps_complex128_ring(engine):

@@ -6,6 +6,7 @@ import pytest
 from conftest import load_golden
 from oracle import sydr_oracle as orc
 from sydr_amd.engine import FMT_CI8
+from test_gpu_pcps import ALL_FMTS, FORMAT_GRID, bits_per_ring_format
 
 pytestmark = pytest.mark.gpu
 
@@ -32,6 +33,16 @@ def test_serial_search_golden(engine):
     rf = orc.iq_to_complex(g["iq"])[:n].reshape(1, -1)
     ref = orc.serial_search(rf, orc.gold_code(5), rng_hz, step, fs, n)
     np.testing.assert_allclose(cmap[1], ref, rtol=0, atol=1e-9 * ref.max())
+
+
+def test_serial_search_same_bits_from_every_ring_format(engine):
+    def run(start):
+        pb, pc, pr, cmap = engine.serial_search([0, 1], start, 4e6, *FORMAT_GRID, noncoh=1, want_map=True)
+        assert cmap.shape == (2, 5, 1023) and [int(b) for b in pb] == [1, 4]
+        return pb, pc, pr, cmap
+    bits = bits_per_ring_format(engine, 1, run)
+    for fmt in ALL_FMTS[1:]:
+        assert bits[fmt] == bits[FMT_CI8], f"ring format {fmt}"
 
 
 def test_two_peak_compare_ss_edge_cases(engine):

@@ -1,8 +1,9 @@
 """the host halves that parse untrusted input or are shared with the device run clean under the address and
 undefined-behaviour sanitizers -- `make -C sydr_amd/csrc check-sanitize` (CPU only; the GPU pool refuses sanitizer runs):
 the per-item check and per-item setups of sdr_epl_plan_create fed 600 000 hostile items (tests/csrc/fuzz_items.hip), the
-chip-geometry dump of test_plan_geometry.py, the exact-division identity of test_div_by_constant.py and the choice and
-decoding of an E/P/L plan's variant word (tests/csrc/epl_variant_dump.hip: grid, decode, rows)."""
+chip-geometry dump of test_plan_geometry.py, the exact-division identity of test_div_by_constant.py, the choice and
+decoding of an E/P/L plan's variant word (tests/csrc/epl_variant_dump.hip: grid, decode, rows) and the ring's sample formats
+read, written and dispatched (tests/csrc/ring_format_check.hip)."""
 import os
 import shutil
 import subprocess
