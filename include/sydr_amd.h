@@ -996,6 +996,47 @@ int sdr_ddc_stap_weights(sdr_engine* e, sdr_ddc* d, const double* w);
 /* C = [T][K][K][2]; waits for the stream */
 int sdr_ddc_stap_covariance(sdr_engine* e, sdr_ddc* d, double* C, int64_t* n, int clear);
 
+/* ------------------------------------------------- beams: several weight sets over one push, each into its own ring
+ * An array or space-time converter decodes one recording; sdr_ddc_beam_attach gives it further weight sets -- a beam per
+ * satellite, or the K element streams side by side -- without a second push: the push stages its bytes once (one copy command,
+ * as ever), and every beam decodes them from HBM.  Beam 0 is the converter as it is: engine e, the weights of
+ * sdr_ddc_array_weights / sdr_ddc_stap_weights.  Beam b >= 1 has a weight set of its own, of the converter's shape ([K][2], or
+ * [T][K][2] of a space-time converter), and its output goes into the ring of `target`, another engine on the same device.
+ * The definition needs no new arithmetic.  Take an independent converter on `target`, made with the same constructor arguments
+ * and the weights w_b, given the same pushes at the same ring_offset and the same weight changes at the same input indices:
+ * beam b's ring holds, byte for byte, what that converter writes -- in every ring format (a beam's ring has its own, any of the
+ * four), whatever the cut into pushes.  The NumPy form is sydr_amd/signal/array.py `statement` / sydr_amd/signal/stap.py
+ * `Statement` applied once per beam (`beams_statement` there).  What follows from it: every push writes the same number of
+ * outputs at the same ring_offset of every beam's ring, and nothing else; sdr_ddc_beam_weights takes effect with the first
+ * input of the next push (it is ordered on e's stream behind the pushes queued so far, which keep the weights they were queued
+ * with); sdr_ddc_reset zeroes every beam's history of combined inputs and keeps every beam's weights; the raw tail of a
+ * space-time converter holds elements, not beams, and is shared; the covariance pass (SDR_DDC_ARRAY_MEASURE) is unchanged, once
+ * per push over the raw elements.
+ * Attaching and clearing are allowed only while the converter has seen no input since creation or reset (SDR_ERR_STATE
+ * otherwise, as for sdr_ddc_mitigate).  A mitigator and attached beams exclude each other: the mitigator's state is per stream
+ * and a converter has one, so whichever of sdr_ddc_mitigate(cfg != NULL) and sdr_ddc_beam_attach comes second is refused with
+ * SDR_ERR_UNSUPPORTED.  SDR_ERR_INVALID: NULL arguments (`beam`, the result, may be NULL), a converter that is neither an array
+ * nor a space-time converter, a target on another device, without a ring, with a ring of another capacity than e's, target == e,
+ * a target attached twice, more than SDR_DDC_MAX_BEAMS - 1 attached beams, a non-finite weight, a beam outside 1 .. count - 1.
+ * A refused call changes nothing.
+ * A push does for every target what it does for e: a resident tick server leaves, a slab parked for the next tick goes into the
+ * ring first, and SDR_ERR_RANGE is checked before anything is queued; a target whose ring has been released or re-allocated at
+ * another capacity since the attachment makes the push fail with SDR_ERR_STATE.  sdr_ddc_push_queue stays asynchronous: before
+ * the beams' kernels write, e's stream waits for an event recorded on each target's stream (what the target queued on its ring
+ * comes first); behind them each target's stream waits for an event recorded on e's stream, and the target's other streams order
+ * themselves as they do behind its own uploads.  sdr_ddc_push returns once every beam's ring holds the push.
+ * Destroying a target engine while it is attached is the caller's error: sdr_ddc_beams_clear or sdr_ddc_destroy release the
+ * attachments first.  Scopes: the attached beams' one launch per push is "ddc_beam_kernel" / "resample_beam_kernel", their
+ * histories are written inside "ddc_history_kernel"; "call_ddc_push" brackets everything.  A converter without attached beams
+ * makes exactly the launches, and writes exactly the bytes, it always made. */
+#define SDR_DDC_MAX_BEAMS 16            /* the converter's own stream included */
+/* w: [K][2] (array converter) or [T][K][2] (space-time converter); *beam (nullable) = the new beam's index, 1 .. */
+int sdr_ddc_beam_attach(sdr_engine* e, sdr_ddc* d, sdr_engine* target, const double* w, int* beam);
+/* beam in 1 .. count - 1; from the next push on; ordered on the stream */
+int sdr_ddc_beam_weights(sdr_engine* e, sdr_ddc* d, int beam, const double* w);
+int sdr_ddc_beam_count(const sdr_ddc* d);          /* 1 + attached beams */
+int sdr_ddc_beams_clear(sdr_engine* e, sdr_ddc* d);
+
 /* ------------------------------------------------- pulse blanking and narrow-band excision in front of the ring
  * An opt-in stage of a converter, between the filter's fp64 output v and the ring's format: a threshold blanker against pulsed
  * interference (DME, radar, a switching supply) and a frequency-domain excisor with windowed overlap-add against carrier-wave

@@ -319,6 +319,10 @@ _PROTOTYPES = {
                                       C.POINTER(_VP)]),
     "sdr_ddc_stap_weights": (C.c_int, [_VP, _VP, C.POINTER(C.c_double)]),
     "sdr_ddc_stap_covariance": (C.c_int, [_VP, _VP, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),
+    "sdr_ddc_beam_attach": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "sdr_ddc_beam_weights": (C.c_int, [_VP, _VP, C.c_int, C.POINTER(C.c_double)]),
+    "sdr_ddc_beam_count": (C.c_int, [_VP]),
+    "sdr_ddc_beams_clear": (C.c_int, [_VP, _VP]),
     "sdr_ddc_destroy": (None, [_VP, _VP]),
     "sdr_ddc_reset": (C.c_int, [_VP, _VP]),
     "sdr_ddc_push": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),

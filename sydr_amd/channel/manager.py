@@ -502,6 +502,27 @@ class ChannelManager:
         block, _ = self._raw_input(block)
         self.engine.ddc_push(self._ddc, block, offset)
 
+    # ------------------------------------------------------------------ beams of a multi-antenna recording (channel/beams.py)
+    def addBeam(self, weights, output_bits=None, engine=None):
+        """One more weight set over the same recording (sdr_ddc_beam_attach): `weights` in the converter's shape -- [K], or [T][K]
+        with `array_taps` --, its stream into the ring of a further engine on this device (`engine`, or one made here), 8- or
+        16-bit samples (None: this manager's).  Valid before the first addNewRFData on a manager whose front end is an array or
+        space-time converter without mitigation keys.  -> the FOLLOWER, a manager over that ring: used like any manager, fed by
+        this one's addNewRFData (its own raises), without read-ahead.  Adaptive training stays this manager's and governs its own
+        stream, beam 0.  Without a call of this, nothing in the manager changes."""
+        from .beams import add_beam
+        return add_beam(self, weights, output_bits, engine)
+
+    def beams(self):
+        """The followers, beam 1 first."""
+        return list(getattr(self, "_beams", ()))
+
+    def setBeamWeights(self, beam: int, weights):
+        """The weights of beam `beam` >= 1 from the next slab on (sdr_ddc_beam_weights; ordered behind the slabs queued so far)."""
+        if not 1 <= int(beam) <= len(self.beams()):
+            raise ValueError(f"beam {beam} outside 1..{len(self.beams())}")
+        self.engine.ddc_beam_weights(self._ddc, int(beam), weights)
+
     def _guard_unread(self, count: int):
         """Refuse to overwrite samples a tracking channel has not consumed yet (the reference would silently wrap:
         circularbuffer.py:54-82 -- and then track garbage)."""
@@ -600,6 +621,9 @@ class ChannelManager:
         if self._ddc is not None:
             self.engine.ddc_destroy(self._ddc)
             self._ddc = None
+        if getattr(self, "_beams", None):
+            from .beams import close_beams
+            close_beams(self)
         if self._ahead is not None and self._ahead["bank"] is self.bank:
             self.bank.device.step_end()                       # (a block queued ahead: let it finish before the bank goes)
         self._ahead = None

@@ -9,6 +9,9 @@
 // the polyphase one of a rational resampler (L > 1; "resample_kernel", resample.hip says what it computes); the loader
 // (ddc_handle.h) is picked from the converter's kind in one place: the four raw formats, an input layout, an antenna array
 // (ddc_array.hip) or a space-time array (ddc_stap.hip).
+// An array or space-time converter with BEAMS attached (sdr_ddc_beam_attach, ddc_beams.hip) runs the same two kernel bodies
+// once more with the beam as the grid's second dimension: the staged bytes are decoded again from HBM per beam, combined with
+// the beam's weights, and written into the beam's target ring.
 // A converter with a mitigator attached (sdr_ddc_mitigate: pulse blanker, narrow-band excisor -- mitigate.hip) has the same
 // kernel write its outputs as cf64 into the mitigator's work buffer in place of the ring; without one a push makes the
 // launches it always made.
@@ -36,6 +39,7 @@ struct DdcFir {
     int tile;
     typedef DdcTile Tile;
     static constexpr const char* kScope = "ddc_kernel";
+    static constexpr const char* kBeamScope = "ddc_beam_kernel";
     static int check(const sdr_ddc* d, int64_t n_in, int64_t cap) {
         if (n_in / d->D > cap) return sdr_fail(SDR_ERR_RANGE, "%lld inputs make more outputs than the ring of %lld samples holds", (long long)n_in, (long long)cap);
         return SDR_OK;
@@ -68,6 +72,7 @@ struct DdcPolyphase {
     int tile;
     typedef RsTile Tile;
     static constexpr const char* kScope = "resample_kernel";
+    static constexpr const char* kBeamScope = "resample_beam_kernel";
     static int check(const sdr_ddc* d, int64_t n_in, int64_t) {
         if (!rs_in_range(d->n_seen, n_in, d->L))
             return sdr_fail(SDR_ERR_RANGE, "%lld inputs behind %lld take the up-sampled index past 2^62", (long long)n_in, (long long)d->n_seen);
@@ -140,6 +145,17 @@ __global__ __launch_bounds__(kDdcThreads) void ddc_convert_kernel(const void* __
     ddc_convert_body((double2*)ddc_smem, in, hist, taps, ring, filter, load, out_fmt, fcw, gain, ring_offset, capacity);
 }
 
+// The attached beams of a push in one launch: workgroup (x, b) is tile x of beam b + 1 -- the body above with that beam's weights
+// (a row of the table in device memory), history, ring and ring format.
+template <class Filter, class Load>
+__global__ __launch_bounds__(kDdcThreads) void ddc_beam_kernel(const void* __restrict__ in, const double* __restrict__ taps, Filter filter, Load load,
+                                                               DdcBeamDst dst, uint64_t fcw, double gain, int64_t ring_offset, int64_t capacity) {
+    extern __shared__ __attribute__((aligned(16))) char ddc_smem[];
+    const int b = blockIdx.y;
+    ddc_convert_body((double2*)ddc_smem, in, (const void*)dst.hist[b], taps, dst.ring[b], filter, load.beam(b), dst.fmt[b], fcw, gain, ring_offset,
+                     capacity);
+}
+
 // THE history kernel, over the loader: the history after a push is its last Tp - 1 inputs as the loader keeps them.  One
 // workgroup; every lane reads its element (out of the block, or -- a push shorter than Tp - 1 -- further up the old history)
 // before any lane writes; a loader with a raw tail brings that up to date the same way.
@@ -164,6 +180,12 @@ __global__ __launch_bounds__(kDdcMaxTaps) void ddc_history_kernel(const void* __
     ddc_history_body(in, hist, n_in, Tp, load);
 }
 
+// ... and the attached beams' histories: workgroup (0, b) is beam b + 1.
+template <class Load>
+__global__ __launch_bounds__(kDdcMaxTaps) void ddc_beam_history_kernel(const void* __restrict__ in, DdcBeamDst dst, int64_t n_in, int Tp, Load load) {
+    ddc_history_body(in, dst.hist[blockIdx.y], n_in, Tp, load.beam(blockIdx.y));
+}
+
 // The bytes a push of n_in >= 0 inputs copies to the staging buffer; of a converter with a layout SDR_ERR_INVALID when they are
 // not whole (nothing has changed then).
 static int ddc_push_bytes(const sdr_ddc* d, int64_t n_in, size_t* bytes) {
@@ -186,6 +208,9 @@ static int ddc_push_impl(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in
     if (n_in < 0) return sdr_fail(SDR_ERR_INVALID, "negative input count");
     if (!in && n_in > 0) return sdr_fail(SDR_ERR_INVALID, "host pointer is NULL");
     const int64_t cap = e->iq_capacity;
+    for (const DdcBeam& b : d->beams)
+        if (!b.target->iq || b.target->iq_capacity != cap)
+            return sdr_fail(SDR_ERR_STATE, "an attached beam's ring is gone or no longer holds the %lld samples of the converter's", (long long)cap);
     if (off < 0 || off >= cap) return sdr_fail(SDR_ERR_RANGE, "ring offset %lld outside the ring of %lld samples", (long long)off, (long long)cap);
     if (int rc = Filter::check(d, n_in, cap)) return rc;
     const Filter filter(d, n_in);
@@ -210,6 +235,10 @@ static int ddc_push_impl(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in
     }
     SDR_HIP(hipMemcpyAsync(e->ddc_stage.ptr, in, bytes, hipMemcpyHostToDevice, e->stream));
     const void* staged = (const void*)e->ddc_stage.ptr;
+    const unsigned n_beams = (unsigned)d->beams.size();
+    DdcBeamDst beam_dst = {};
+    for (unsigned b = 0; b < n_beams; ++b)
+        beam_dst.ring[b] = d->beams[b].target->iq, beam_dst.hist[b] = d->beams[b].hist, beam_dst.fmt[b] = d->beams[b].target->iq_fmt;
     if (n > 0) {
         sdr_iq_mark_written(e, off, n);
         ProfScope ps(e, Filter::kScope);
@@ -221,9 +250,35 @@ static int ddc_push_impl(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in
     }
     if (d->mit && n > 0)
         if (int rc = mit_push_finish(e, d->mit, m_first, n, off)) return rc;
+    if (n_beams && n > 0) {
+        // every beam's ring behind what its engine has queued on it, the beams' kernels, and the targets' streams behind those
+        for (const DdcBeam& b : d->beams) {
+            SDR_HIP(hipEventRecord(b.ready, b.target->stream));
+            SDR_HIP(hipStreamWaitEvent(e->stream, b.ready, 0));
+        }
+        {
+            ProfScope ps(e, Filter::kBeamScope);
+            ddc_with_beam_loader(d, [&](auto load) {
+                hipLaunchKernelGGL((ddc_beam_kernel<Filter, decltype(load)>), dim3((unsigned)filter.tiles(), n_beams), dim3(kDdcThreads),
+                                   filter.lds_inputs() * sizeof(double2), e->stream, staged, (const double*)d->taps, filter, load, beam_dst, d->fcw, d->gain,
+                                   off, cap);
+            });
+        }
+        SDR_HIP(hipEventRecord(d->beams_done, e->stream));
+        for (const DdcBeam& b : d->beams) {
+            SDR_HIP(hipStreamWaitEvent(b.target->stream, d->beams_done, 0));
+            sdr_iq_mark_written(b.target, off, n);
+        }
+    }
     ddc_cov_launch(e, d, n_in);
     if (d->Tp > 1 || (d->kind == kDdcKindStap && d->stap.T > 1)) {     // (a space-time converter's raw tail too)
         ProfScope ps(e, "ddc_history_kernel");
+        // (the beams' histories first: their last inputs reach into the raw tail as it was before this push)
+        if (n_beams && d->Tp > 1)
+            ddc_with_beam_loader(d, [&](auto load) {
+                hipLaunchKernelGGL((ddc_beam_history_kernel<decltype(load)>), dim3(1, n_beams), dim3(kDdcMaxTaps), 0, e->stream, staged, beam_dst, n_in, d->Tp,
+                                   load);
+            });
         ddc_with_loader(d, [&](auto load) {
             hipLaunchKernelGGL((ddc_history_kernel<decltype(load)>), dim3(1), dim3(kDdcMaxTaps), 0, e->stream, staged, d->hist, n_in, d->Tp, load);
         });
@@ -237,6 +292,9 @@ static int ddc_push_impl(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in
 static int ddc_push_any(sdr_engine* e, sdr_ddc* d, const void* in, int64_t n_in, int64_t off, int64_t* n_out, bool wait) {
     if (int rc = sdr_set_device(e)) return rc;
     if (int rc = ddc_check(e, d)) return rc;
+    // (what the push does for its own engine it does for every beam's: a resident tick server leaves, a parked slab goes into the ring)
+    for (const DdcBeam& b : d->beams)
+        if (int rc = sdr_set_device(b.target)) return rc;
     return d->L == 1 ? ddc_push_impl<DdcFir>(e, d, in, n_in, off, n_out, wait) : ddc_push_impl<DdcPolyphase>(e, d, in, n_in, off, n_out, wait);
 }
 
@@ -252,6 +310,7 @@ static void ddc_free(sdr_ddc* d) {
     if (d->cov) (void)hipFree(d->cov);
     if (d->cov_slab.ptr) (void)hipFree(d->cov_slab.ptr);
     if (d->tail) (void)hipFree(d->tail);
+    ddc_beams_release(d);
     mit_destroy(nullptr, d->mit);
     delete d;
 }
@@ -374,6 +433,7 @@ int sdr_ddc_reset(sdr_engine* e, sdr_ddc* d) {
     SDR_HIP(hipMemsetAsync(d->hist, 0, ddc_hist_bytes(d), e->stream));
     if (d->cov) SDR_HIP(hipMemsetAsync(d->cov, 0, ddc_cov_bytes(d), e->stream));     // (the weights stay)
     if (d->tail) SDR_HIP(hipMemsetAsync(d->tail, 0, ddc_stap_tail_bytes(d->stap.T, d->array.K), e->stream));
+    for (const DdcBeam& b : d->beams) SDR_HIP(hipMemsetAsync(b.hist, 0, ddc_hist_bytes(d), e->stream));     // (every beam's weights stay)
     d->cov_n = 0;
     if (d->mit)
         if (int rc = mit_reset(e, d->mit)) return rc;
@@ -403,6 +463,8 @@ int sdr_ddc_mitigate(sdr_engine* e, sdr_ddc* d, const sdr_mit_cfg* cfg) {
     if (int rc = sdr_set_device(e)) return rc;
     if (int rc = ddc_check(e, d)) return rc;
     if (d->n_seen != 0) return sdr_fail(SDR_ERR_STATE, "the converter has seen %lld inputs since its creation or reset", (long long)d->n_seen);
+    if (cfg && !d->beams.empty())
+        return sdr_fail(SDR_ERR_UNSUPPORTED, "the converter has beams attached: a mitigator's state is per stream, and there is one mitigator");
     Mitigator* fresh = nullptr;
     if (cfg)
         if (int rc = mit_create(e, cfg, &fresh)) return rc;

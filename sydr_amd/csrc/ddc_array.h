@@ -138,8 +138,23 @@ SDR_DDC_HD inline void ddc_array_accumulate(double wr, double wi, double sr, dou
     *re = r, *im = i;
 }
 
-// Input j of the converter: x_j = sum_a conj(w_a) s_a over the frame's K elements.
-SDR_DDC_HD inline void ddc_array_load(const void* __restrict__ p, int64_t j, const DdcLayout& l, const DdcArray& arr, double* re, double* im) {
+// Where a combine takes its weights from: the array's own, a kernel argument by value (the converter's own stream) ...
+struct DdcArrayOwnWeights {
+    const DdcArray& arr;
+    SDR_DDC_HD double re(int a) const { return arr.w[a][0]; }
+    SDR_DDC_HD double im(int a) const { return arr.w[a][1]; }
+};
+// ... or a row [kDdcArrayMax][2] of a table in device memory (an attached beam's: ddc_handle.h), read by wave-uniform loads.
+struct DdcArrayTableWeights {
+    const double* __restrict__ w;
+    SDR_DDC_HD double re(int a) const { return w[2 * a]; }
+    SDR_DDC_HD double im(int a) const { return w[2 * a + 1]; }
+};
+
+// Input j of the converter: x_j = sum_a conj(w_a) s_a over the frame's K elements, the weights from `w`.
+template <class Weights>
+SDR_DDC_HD inline void ddc_array_combine(const void* __restrict__ p, int64_t j, const DdcLayout& l, const DdcArray& arr, const Weights& w, double* re,
+                                         double* im) {
     const DdcFrame fr = ddc_array_frame(p, j, l);
     double r = 0.0, i = 0.0;
     // (unrolled with constant element indices: on the device lanes and weights then stay kernel arguments in scalar registers;
@@ -149,9 +164,12 @@ SDR_DDC_HD inline void ddc_array_load(const void* __restrict__ p, int64_t j, con
         if (a >= arr.K) break;
         double sr, si;
         ddc_array_element(p, j, l, fr, arr.lanes[a], &sr, &si);
-        ddc_array_accumulate(arr.w[a][0], arr.w[a][1], sr, si, &r, &i);
+        ddc_array_accumulate(w.re(a), w.im(a), sr, si, &r, &i);
     }
     *re = r, *im = i;
+}
+SDR_DDC_HD inline void ddc_array_load(const void* __restrict__ p, int64_t j, const DdcLayout& l, const DdcArray& arr, double* re, double* im) {
+    ddc_array_combine(p, j, l, arr, DdcArrayOwnWeights{arr}, re, im);
 }
 
 // The history: combined inputs as (re, im) doubles.

@@ -19,6 +19,23 @@ enum DdcKind {
     kDdcKindStap            // sdr_ddc_create_stap (array.w is not read): T taps per element, `tail` the raw tail (ddc_stap.h)
 };
 
+// An attached BEAM (sdr_ddc_beam_attach): a further weight set of an array or space-time converter whose stream goes into the
+// ring of `target`.  Its weights are row (beam - 1) of sdr_ddc::beam_w, its history the converter's own kind of history.
+constexpr int kDdcMaxBeams = SDR_DDC_MAX_BEAMS;
+constexpr int kDdcBeamWeightRow = sdr::kDdcStapMaxTaps * sdr::kDdcArrayMax * 2;     // doubles: DdcStap::w's layout; an array's w in front
+struct DdcBeam {
+    sdr_engine* target = nullptr;
+    void* hist = nullptr;             // device [max(Tp-1, 1)] combined inputs, cf64
+    hipEvent_t ready = nullptr;       // recorded on the target's stream in front of a push: what it queued on its ring comes first
+};
+
+// The attached beams' destinations as their kernels take them, by value: entry b is beam b + 1.
+struct DdcBeamDst {
+    void* ring[kDdcMaxBeams - 1];
+    void* hist[kDdcMaxBeams - 1];
+    int fmt[kDdcMaxBeams - 1];
+};
+
 struct sdr_ddc {
     sdr_engine* engine = nullptr;
     DdcKind kind = kDdcKindFormat;
@@ -42,6 +59,9 @@ struct sdr_ddc {
     DevBuf cov_slab;
     sdr::DdcStap stap = {};
     double* tail = nullptr;      // device: the last stap.T - 1 decoded frames
+    std::vector<DdcBeam> beams;  // beam 1 .. (beam 0 is the converter's own stream)
+    double* beam_w = nullptr;    // device [kDdcMaxBeams - 1][kDdcBeamWeightRow], written on the engine's stream (ddc_beam_set_kernel)
+    hipEvent_t beams_done = nullptr;   // recorded on the engine's stream behind the beams' kernels: the targets' streams wait for it
 };
 
 // Bytes of the covariance slots of a measuring converter.
@@ -194,6 +214,67 @@ struct DdcStapLoad {
     }
 };
 
+// ... or those two with the weights of attached beam `b + 1`, a row of the table in device memory in place of the argument's
+// own: the same statements on the same operands (ddc_array_combine, ddc_stap_load_table).  The raw tail is read, never kept: it
+// holds elements, not beams, and the converter's own history launch brings it up to date behind the beams'.
+struct DdcArrayBeamLoad {
+    sdr::DdcLayout lay;
+    sdr::DdcArray arr;
+    const double* w;
+    typedef double2 Kept;
+    static constexpr bool kTail = false;
+    __device__ __forceinline__ DdcArrayBeamLoad beam(int b) const {
+        DdcArrayBeamLoad r = *this;
+        r.w = w + (size_t)b * kDdcBeamWeightRow;
+        return r;
+    }
+    __device__ __forceinline__ void block(const void* __restrict__ p, int64_t i, double* re, double* im) const {
+        sdr::ddc_array_combine(p, i, lay, arr, sdr::DdcArrayTableWeights{w}, re, im);
+    }
+    __device__ __forceinline__ void history(const void* __restrict__ p, int64_t i, double* re, double* im) const { sdr::ddc_array_history_load(p, i, re, im); }
+    __device__ __forceinline__ Kept kept_block(const void* p, int64_t i) const {
+        Kept v;
+        block(p, i, &v.x, &v.y);
+        return v;
+    }
+    __device__ __forceinline__ Kept kept_history(const void* p, int64_t i) const {
+        Kept v;
+        history(p, i, &v.x, &v.y);
+        return v;
+    }
+    __device__ __forceinline__ void keep(void* hist, int i, Kept v) const { sdr::ddc_array_history_store(hist, i, v.x, v.y); }
+};
+
+struct DdcStapBeamLoad {
+    sdr::DdcLayout lay;
+    sdr::DdcArray arr;
+    int T;
+    const double* tail;
+    const double* w;
+    typedef double2 Kept;
+    static constexpr bool kTail = false;
+    __device__ __forceinline__ DdcStapBeamLoad beam(int b) const {
+        DdcStapBeamLoad r = *this;
+        r.w = w + (size_t)b * kDdcBeamWeightRow;
+        return r;
+    }
+    __device__ __forceinline__ void block(const void* __restrict__ p, int64_t i, double* re, double* im) const {
+        sdr::ddc_stap_load_table(p, tail, i, lay, arr, T, w, re, im);
+    }
+    __device__ __forceinline__ void history(const void* __restrict__ p, int64_t i, double* re, double* im) const { sdr::ddc_array_history_load(p, i, re, im); }
+    __device__ __forceinline__ Kept kept_block(const void* p, int64_t i) const {
+        Kept v;
+        block(p, i, &v.x, &v.y);
+        return v;
+    }
+    __device__ __forceinline__ Kept kept_history(const void* p, int64_t i) const {
+        Kept v;
+        history(p, i, &v.x, &v.y);
+        return v;
+    }
+    __device__ __forceinline__ void keep(void* hist, int i, Kept v) const { sdr::ddc_array_history_store(hist, i, v.x, v.y); }
+};
+
 // The one place where a converter's kind becomes its loader: f(load) with the loader as the kernels take it, by value.
 template <class F>
 inline void ddc_with_loader(const sdr_ddc* d, F&& f) {
@@ -203,6 +284,13 @@ inline void ddc_with_loader(const sdr_ddc* d, F&& f) {
         case kDdcKindLayout: return f(DdcLayoutLoad{d->layout});
         default: return f(DdcFormatLoad{d->in_fmt});
     }
+}
+
+// ... and its beams' loader (d->kind >= kDdcKindArray).
+template <class F>
+inline void ddc_with_beam_loader(const sdr_ddc* d, F&& f) {
+    if (d->kind == kDdcKindStap) return f(DdcStapBeamLoad{d->layout, d->array, d->stap.T, d->tail, d->beam_w});
+    return f(DdcArrayBeamLoad{d->layout, d->array, d->beam_w});
 }
 
 inline int ddc_check(sdr_engine* e, const sdr_ddc* d) {
@@ -217,5 +305,8 @@ namespace sdr {
 // kDdcKindLayout on, `array` from kDdcKindArray on, stap_taps and stap_w ([stap_taps][K][2]) of kDdcKindStap, unread otherwise.
 int ddc_create(sdr_engine* e, DdcKind kind, const sdr_ddc_cfg* cfg, int L, const sdr_ddc_layout* layout, const sdr_ddc_array* array, int stap_taps,
                const double* stap_w, sdr_ddc** out);
+
+// ddc_beams.hip: every attachment of d released -- histories, events, the weight table (the caller has waited for the stream).
+void ddc_beams_release(sdr_ddc* d);
 
 }  // namespace sdr

@@ -98,6 +98,41 @@ SDR_DDC_HD inline void ddc_stap_load(const void* __restrict__ p, const double* _
     *re = r, *im = i;
 }
 
+// The same input with the T taps' weights out of a row [kDdcStapMaxTaps][kDdcArrayMax][2] of a table in device memory (an attached
+// beam's: ddc_handle.h), DdcStap::w's own layout, read by wave-uniform loads: ddc_stap_load's statements on the same operands in
+// the same order.  Kept apart from it: routed through one template the by-value form compiles to other code than it always had
+// (17 063 instructions against 15 434 in the converter's kernel).
+SDR_DDC_HD inline void ddc_stap_load_table(const void* __restrict__ p, const double* __restrict__ tail, int64_t j, const DdcLayout& l,
+                                           const DdcArray& arr, int T, const double* __restrict__ w, double* re, double* im) {
+    double r = 0.0, i = 0.0;
+#pragma unroll
+    for (int t = 0; t < kDdcStapMaxTaps; ++t) {
+        if (t >= T) break;
+        const int64_t f = j - t;
+        const double* wt = w + 2 * (t * kDdcArrayMax);
+        if (f >= 0) {
+            const DdcFrame fr = ddc_array_frame(p, f, l);
+#pragma unroll
+            for (int a = 0; a < kDdcArrayMax; ++a) {
+                if (a >= arr.K) break;
+                double sr, si;
+                ddc_array_element(p, f, l, fr, arr.lanes[a], &sr, &si);
+                ddc_array_accumulate(wt[2 * a], wt[2 * a + 1], sr, si, &r, &i);
+            }
+        } else {
+            const int slot = T - 1 + (int)f;
+#pragma unroll
+            for (int a = 0; a < kDdcArrayMax; ++a) {
+                if (a >= arr.K) break;
+                double sr, si;
+                ddc_stap_tail_load(tail, slot, arr.K, a, &sr, &si);
+                ddc_array_accumulate(wt[2 * a], wt[2 * a + 1], sr, si, &r, &i);
+            }
+        }
+    }
+    *re = r, *im = i;
+}
+
 // lanes[a] by selects (a run-time index into the by-value array would copy it to scratch memory).
 SDR_DDC_HD inline int ddc_stap_lane(const DdcArray& arr, int a) {
     int lane = arr.lanes[0];

@@ -494,6 +494,39 @@ class Engine:
         check(self._lib.sdr_ddc_stap_covariance(self._h, ddc.handle, out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n), int(bool(clear))))
         return out[..., 0] + 1j * out[..., 1], n.value
 
+    def _beam_weights(self, ddc, weights):
+        """A beam's weights in the converter's shape, [K] or [T][K], as the C-ABI's doubles."""
+        if ddc.n_taps:
+            from .signal.stap import as_weights
+            w = as_weights(weights, ddc.n_taps, ddc.n_elements or 1)
+        else:
+            from .signal.array import as_weights
+            w = as_weights(weights, ddc.n_elements or 1)
+        return np.ascontiguousarray(np.stack([w.real, w.imag], axis=-1))
+
+    def ddc_beam_attach(self, ddc, target_engine, weights) -> int:
+        """A further beam of an array or space-time converter: `weights` in the converter's shape, the output into
+        target_engine's ring (sdr_ddc_beam_attach; only before the converter's first input or after a reset) -> its index, 1 .."""
+        flat, beam = self._beam_weights(ddc, weights), C.c_int(0)
+        check(self._lib.sdr_ddc_beam_attach(self._h, ddc.handle, target_engine._h, flat.ctypes.data_as(C.POINTER(C.c_double)), C.byref(beam)))
+        return beam.value
+
+    def ddc_beam_weights(self, ddc, beam: int, weights):
+        """The weights of attached beam `beam` >= 1 from the next push on (sdr_ddc_beam_weights; ordered on the stream)."""
+        flat = self._beam_weights(ddc, weights)
+        check(self._lib.sdr_ddc_beam_weights(self._h, ddc.handle, int(beam), flat.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def ddc_beam_count(self, ddc) -> int:
+        """1 + the attached beams (sdr_ddc_beam_count)."""
+        n = self._lib.sdr_ddc_beam_count(ddc.handle)
+        if n < 0:
+            check(int(n))
+        return int(n)
+
+    def ddc_beams_clear(self, ddc):
+        """Release every attached beam (sdr_ddc_beams_clear; only before the converter's first input or after a reset)."""
+        check(self._lib.sdr_ddc_beams_clear(self._h, ddc.handle))
+
     def ddc_push(self, ddc, raw: np.ndarray, ring_offset: int = 0) -> int:
         """Raw inputs (real: one integer each; complex: interleaved I,Q; a converter with a layout: the recording's bytes, whole
         frames, uint8 for packed fields and the field's type otherwise) through the converter into the ring at ring_offset

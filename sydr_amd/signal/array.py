@@ -41,8 +41,16 @@ Rl = R/n + loading * trace(R/n)/K * I:
 
     power_inversion:  w = Rl^-1 e_ref / (e_ref^H Rl^-1 e_ref)       (unit response of the reference element, least output power)
     mvdr:             w = Rl^-1 a / (a^H Rl^-1 a)                   (unit response towards the steering vector a)
+
+BEAMS (sdr_ddc_beam_attach).  A converter with beams forms several weight sets over one push, beam b >= 1 into the ring of an
+engine of its own.  There is no second formulation: beam b's ring holds what `statement` gives a converter of the same
+configuration with the weights w_b, the same pushes and the same weight changes at the same input indices --
+`beams_statement` is `statement` once per weight set.  `element_weights` are the K unit vectors (the element streams side by
+side) and `wiener_weights` the weights R^-1 p of a signal whose per-element prompts p were measured behind them.
 """
 from __future__ import annotations
+
+import dataclasses
 
 import numpy as np
 
@@ -275,3 +283,38 @@ def statement(cfg: dc.DownConverterConfig, pushes, ring_fmt=None, state: Stateme
         parts.append(st.push(raw))
     v = np.concatenate(parts) if parts else np.zeros(0, dtype=np.complex128)
     return v if ring_fmt is None else dc.quantise(v, ring_fmt)
+
+
+def with_weights(cfg: dc.DownConverterConfig, weights) -> dc.DownConverterConfig:
+    """`cfg` with its array's weights replaced: the configuration of the independent converter a beam is defined by."""
+    return dataclasses.replace(cfg, array=ArrayGeometry(cfg.array.lanes, weights, cfg.array.measure))
+
+
+def beams_statement(cfg: dc.DownConverterConfig, weight_sets, pushes, ring_fmts=None, weights_at=None, _statement=None, _with=None):
+    """What every beam's ring holds: `statement` per weight set, in its own words -> a list, beam 0 first.  weight_sets[b]: beam
+    b's weights at creation / attachment; ring_fmts (optional): one ring format per beam; weights_at: {push index: {beam:
+    weights}} set before that push."""
+    one, replaced = _statement or statement, _with or with_weights
+    out = []
+    for b, w in enumerate(weight_sets):
+        changes = {k: per_beam[b] for k, per_beam in (weights_at or {}).items() if b in per_beam}
+        out.append(one(replaced(cfg, w), pushes, None if ring_fmts is None else ring_fmts[b], weights_at=changes))
+    return out
+
+
+def element_weights(K: int) -> np.ndarray:
+    """The K unit vectors [K][K]: beam a of them is element a's own stream."""
+    return np.stack([unit_weights(K, a) for a in range(K)])
+
+
+def wiener_weights(R, p, loading: float = DEFAULT_LOADING) -> np.ndarray:
+    """w = (R + loading tr(R)/K I)^-1 p: R the covariance of the elements (any common scale), p the per-element prompts of a
+    tracked signal, p_a = sum_j s_a[j] conj(replica[j]) -- the cross-correlation of the elements with the wanted signal.  The
+    beam w^H s then has the largest ratio of signal to interference plus noise a linear combination of the elements can have."""
+    R = np.asarray(R, dtype=np.complex128)
+    K = R.shape[0]
+    if R.shape != (K, K) or not MIN_ELEMENTS <= K <= MAX_ELEMENTS:
+        raise ValueError("R is K x K, K in 2..8")
+    if not loading >= 0.0:
+        raise ValueError("loading is not negative")
+    return np.linalg.solve(R + loading * (np.trace(R).real / K) * np.eye(K), as_weights(p, K))

@@ -49,8 +49,13 @@ With Rl = R + loading * trace(R)/(K T) * I -- `array.py`'s loading rule on the l
 
 The output is then the reference element (the steered beam) delayed by reference_tap input samples; sdr_ddc_delay does not know
 of it, the host layer adds it.
+
+BEAMS (sdr_ddc_beam_attach): as in `array.py` -- beam b's ring is `statement` of the same configuration with the weights w_b
+[T][K]; `beams_statement` is that, once per weight set.  The raw tail holds elements and is the same for every beam.
 """
 from __future__ import annotations
+
+import dataclasses
 
 import numpy as np
 
@@ -280,3 +285,28 @@ def statement(cfg: dc.DownConverterConfig, pushes, ring_fmt=None, state: Stateme
         parts.append(st.push(raw))
     v = np.concatenate(parts) if parts else np.zeros(0, dtype=np.complex128)
     return v if ring_fmt is None else dc.quantise(v, ring_fmt)
+
+
+def with_weights(cfg: dc.DownConverterConfig, weights) -> dc.DownConverterConfig:
+    """`cfg` with its space-time weights replaced: the configuration of the independent converter a beam is defined by."""
+    return dataclasses.replace(cfg, array=SpaceTimeGeometry(cfg.array.lanes, cfg.array.taps, weights, cfg.array.measure))
+
+
+def beams_statement(cfg: dc.DownConverterConfig, weight_sets, pushes, ring_fmts=None, weights_at=None):
+    """`array.beams_statement` with this file's `statement`: one list entry per weight set [T][K], beam 0 first."""
+    return ar.beams_statement(cfg, weight_sets, pushes, ring_fmts, weights_at, _statement=statement, _with=with_weights)
+
+
+def element_weights(T: int, K: int, t0: int = 0) -> np.ndarray:
+    """The K unit vectors at tap t0, [K][T][K]: beam a of them is element a's own stream, delayed by t0 inputs."""
+    return np.stack([unit_weights(T, K, a, t0) for a in range(K)])
+
+
+def wiener_weights(C, n, p, reference_tap=None, loading: float = DEFAULT_LOADING) -> np.ndarray:
+    """w [T][K] = Rl^-1 c, Rl the loaded space-time covariance of the lags C of n inputs and c the per-element prompts p of a
+    tracked signal at reference_tap, zero elsewhere (`array.wiener_weights` on the stacked vector)."""
+    C = np.asarray(C)
+    T, K = C.shape[0], C.shape[1]
+    c = np.zeros((T, K), dtype=np.complex128)
+    c[_reference_tap(T, reference_tap)] = ar.as_weights(p, K)
+    return np.linalg.solve(_loaded(C, n, loading), c.reshape(-1)).reshape(T, K)
