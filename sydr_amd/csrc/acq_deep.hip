@@ -121,11 +121,9 @@ int sdr_deep_shift_acc(sdr_engine* e, const double* mag, double* map, const int3
 
 extern "C" int64_t sdr_acq_deep_shift(const sdr_deep_cfg* cfg, int bin, int64_t block) {
     if (!cfg || !(cfg->carrier_rf_hz > 0.0) || bin < 0 || block < 0) return 0;
-    // np.arange(-R, R+1, S): element k = start + k*delta with delta = (start+step) - start (sdr_pcps's grid)
-    const double bin_start = -cfg->doppler_range;
-    const double bin_delta = (bin_start + cfg->doppler_step) - bin_start;
-    const double d = bin_start + (double)bin * bin_delta;
-    const int64_t N = (int64_t)std::nearbyint(cfg->fs * 1023.0 / 1.023e6);
+    // the search's own grid and samples per code (acq_request.h)
+    const double d = sdr::acq_bin(cfg->doppler_range, cfg->doppler_step, bin);
+    const int64_t N = (int64_t)sdr::acq_samples_per_code(cfg->fs);
     const double t = (double)(block * (int64_t)cfg->coh * N);
     return (int64_t)std::nearbyint(d * t / cfg->carrier_rf_hz);
 }

@@ -29,7 +29,7 @@ constexpr int kThreads = kDetectThreads;
 constexpr int kWaves = kThreads / 64;
 
 __device__ __forceinline__ Best better(Best a, Best b) {
-    // larger value wins; on ties the smaller flat index (pcps.hip)
+    // larger value wins; on ties the smaller flat index (pcps_peak.h)
     if (b.v > a.v || (b.v == a.v && b.i < a.i)) return b;
     return a;
 }

@@ -12,7 +12,9 @@
 #include <vector>
 
 #include "../../include/sydr_amd.h"
+#include "acq_request.h"
 #include "pcps_fused_work.h"
+#include "pcps_plan.h"   // SDR_PCPS_FUSED_RECORDS, SDR_PCPS_FUSED10K_RECORD_BYTES
 #include "ring_format.h"
 
 // Thread-local error text behind sdr_last_error().
@@ -110,7 +112,7 @@ struct sdr_engine {
     DevBuf pcps_fwd, pcps_a, pcps_b, pcps_code, pcps_tw, pcps_map, pcps_csum, pcps_part, pcps_res;
     DevBuf pcps_code2;            // N = 50 000, fused search: [prn][parity][N] -- the spectra and their image with the odd half's twiddle (pcps_fused.h)
     bool pcps_code2_ok = false;   // ... made from what pcps_code holds now
-    DevBuf pcps_spec_off;         // shared spectra: every bin's element offset into the padded class spectra (pcps.hip)
+    DevBuf pcps_spec_off;         // shared spectra: every bin's element offset into the padded class spectra (pcps_plan.h, pcps.hip upload_spec_offsets)
     std::vector<int64_t> pcps_spec_off_key;
     bool pcps_no_shared_spectra = false;   // "pcps_no_shared_spectra": one forward transform per bin, as before round 5
     DevBuf pcps_tickets;          // one word per PRN: the second sweep's last workgroup of a PRN divides the two peaks (pcps_fused.h)
@@ -211,6 +213,18 @@ struct sdr_engine {
     DevBuf cancel_ws;             // [items][counts][the two counters]
 };
 
+// What acq_request.h's check needs of the engine and of an acquisition call (slots == nullptr: the caller hands in code
+// spectra; the caller then sets n_code).
+inline sdr::AcqRequest sdr_acq_request(const sdr_engine* e, const int32_t* slots, int n_prn, int64_t start_sample, double fs,
+                                       double doppler_range, double doppler_step, int64_t blocks) {
+    sdr::AcqRequest r;
+    r.ring = e->iq != nullptr, r.capacity = e->iq_capacity;
+    r.slots_allocated = e->codes != nullptr, r.n_slots = e->n_slots, r.code_len = e->code_len_host.data();
+    r.slots = slots, r.n_prn = n_prn, r.start = start_sample;
+    r.fs = fs, r.doppler_range = doppler_range, r.doppler_step = doppler_step, r.blocks = blocks;
+    return r;
+}
+
 int sdr_devbuf_reserve(sdr_engine* e, DevBuf* b, size_t bytes);
 // Same for a buffer only ever used on `stream` (waits for that stream alone before a re-allocation).
 int sdr_devbuf_reserve_on(sdr_engine* e, hipStream_t stream, DevBuf* b, size_t bytes);
@@ -255,17 +269,15 @@ const void* sdr_epl_straight_kernel(int nt, int km, int ks, int ki);
 // pcps_fused.hip: every (PRN, bin) inverse transform of a map-free search at N = 25 000 in one launch; leaves
 // SDR_PCPS_FUSED_RECORDS (value, index) records per transform in `partials` ([transform][record], 16 bytes each).
 // N = 50 000 (terms = 2): a unit is one parity of a transform -- twice the records -- and C is the [prn][parity][N] image.
-#define SDR_PCPS_FUSED_RECORDS 8
-// spec_off (nullable): element offset of every bin's spectrum inside F (shared spectra: pcps.hip); else bin b is at b * N.
+// spec_off (nullable): element offset of every bin's spectrum inside F (shared spectra: pcps_plan.h); else bin b is at b * N.
 int sdr_pcps_fused_sweep(sdr_engine* e, const void* F, const void* spec_off, const void* C, const void* tw, int n_prn, int nbins, int N,
                          void* partials);
-// records per PRN that sweep leaves (PRN-major: [prn][records]); a search that is not a whole number of rounds of its 256
-// workgroups has its last transforms cut into five units of SDR_PCPS_FUSED_RECORDS records each
-int sdr_pcps_fused_records_per_prn(int n_prn, int nbins, int terms);
+// records per PRN that sweep leaves (PRN-major: [prn][records]): fusedwork::fused_records_per_prn (terms: 1 at N = 25 000; 2 at
+// N = 50 000, where a unit is one parity of a (PRN, bin) transform and the plan sees 2 nbins virtual bins) -- a search that is
+// not a whole number of rounds of its 256 workgroups has its last transforms cut into units of SDR_PCPS_FUSED_RECORDS records each
 // pcps_fused10k.h: a search at N = 10 000 that wants indices and ratio only (coh = 1, any number of non-coherent blocks): one
 // workgroup per (PRN, bin) keeps the transform in its LDS and the non-coherent sum in registers; F_all = [noncoh][nbins][N]
 // forward spectra, records = n_prn * nbins * SDR_PCPS_FUSED10K_RECORD_BYTES bytes of scratch; the results go to out_*.
-#define SDR_PCPS_FUSED10K_RECORD_BYTES 32
 // (spec_off / blk_stride: shared spectra, as above; nullptr / nbins * N: one spectrum per bin)
 // done (nullable): one page-locked word per PRN, raised to done_seq behind the PRN's results
 int sdr_pcps_fused10k_search(sdr_engine* e, const void* F_all, const void* spec_off, long long blk_stride, const void* C, const void* tw, int n_prn,

@@ -1,4 +1,4 @@
-// Pieces shared by the PCPS translation units (pcps.hip and pcps_fused.hip): the (value, index) record of the map-free
+// Pieces shared by the PCPS translation units (pcps.hip, serial_search.hip and pcps_fused.hip): the (value, index) record of the map-free
 // search, complex helpers, the wave-wide maximum and the radix-5 codelet of the register-resident transforms.
 #pragma once
 

@@ -1,6 +1,6 @@
 // Register-resident four-step kernels for the inverse transforms of the map-free PCPS search at N = 25 000 = 125 x 200
-// (25 MHz, 1 ms: BASELINE configs[1]) -- included by pcps.hip, which keeps the general mixed-radix kernels for every
-// other length and for the stages that are not 1312 transforms per call.
+// (25 MHz, 1 ms: BASELINE configs[1]) -- included by pcps.hip; pcps_fft.h keeps the general mixed-radix kernels for every
+// other length and for the stages that are not 1312 transforms per call, and dispatches to run / run_cols below.
 //
 // The general kernels give every thread ONE radix-R butterfly per pass and go through LDS (read R, write R, a barrier)
 // for each of the three passes of a sub-transform: at 125 x 200 they execute ~140 vector instructions and ~11 LDS
@@ -24,19 +24,23 @@
 // running (|.|/N, first index) maximum with per-wave 16-byte records instead of the map on the way out.
 #pragma once
 
+#include "pcps_fft.h"        // PassArgs, Butterfly
+#include "pcps_codelets.h"   // Best, wave_best, the radix-5 codelet
+#include "pcps_plan.h"       // the geometry the planner counts this kernel pair's records with
+
+namespace {
 namespace fast25k {
 
-constexpr int N1 = 125, N2 = 200, N = 25000;
+using pcps::fast25k::N1;
+using pcps::fast25k::N2;
+using pcps::fast25k::N;
 constexpr int kColT = 25;            // columns per workgroup: 125 of 128 threads hold 25 points each
 constexpr int kColThreads = 128;
-#ifndef SDR_PCPS_FAST_ROWT
-#define SDR_PCPS_FAST_ROWT 12
-#endif
-constexpr int kRowT = SDR_PCPS_FAST_ROWT;                 // rows per workgroup: 120 of 128 threads hold 20 points each
-constexpr int kRowThreads = (10 * kRowT + 63) / 64 * 64;
+using pcps::fast25k::kRowT;          // rows per workgroup: 120 of 128 threads hold 20 points each
+using pcps::fast25k::kRowThreads;
 constexpr int kRowPitch = 10 * kRowT + 1;                 // 16-byte slots per exchanged register (odd: ten-strided reads hit sixteen different slots)
-constexpr int kRowTiles = (N1 + kRowT - 1) / kRowT;
-constexpr int kRecordsPerTransform = kRowTiles * (kRowThreads / 64);
+using pcps::fast25k::kRowTiles;
+using pcps::fast25k::kRecordsPerTransform;
 
 // 25-point inverse transform of v[m], m = m1 + 5 m2: result A[kA + 5 kB] in v[5 kA + kB].
 __device__ __forceinline__ void idft25(double2* v, const double2* __restrict__ tw) {
@@ -305,3 +309,4 @@ inline void run(sdr_engine* e, PassArgs a, int batch, double2* Z, hipStream_t st
 }
 
 }  // namespace fast25k
+}  // namespace

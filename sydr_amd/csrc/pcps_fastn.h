@@ -6,22 +6,26 @@
 //      N = 10 000 (10 MHz) =  50 x 200      columns: 25 x 2
 //      N = 50 000 (50 MHz) = 250 x 200      columns: 25 x 10
 // (N = 25 000 keeps its own, tuned kernels.)  Same fused stages: spectrum x code spectrum on the way in with the XCD-aware
-// mapping, running (|.|/N, first index) maximum with per-wave records on the way out.  Included by pcps.hip after pcps_fast.h.
+// mapping, running (|.|/N, first index) maximum with per-wave records on the way out.  Included by pcps.hip; pcps_fft.h dispatches
+// to run / run_rows below.
 #pragma once
 
+#include "pcps_fast.h"       // the row geometry and the 25 MHz kernels' codelets; with it PassArgs, Butterfly, Best, wave_best
+#include "pcps_plan.h"       // the lengths served and the records a transform leaves: the planner's
+
+namespace {
 namespace fastn {
 
 using fast25k::cmulf;
 using fast25k::cmul_conj;
 using fast25k::ibf5;
 
-constexpr int N2 = 200;
+using pcps::fastn::N2;
 constexpr int kThreadsN = 128;
-constexpr int kRowT = fast25k::kRowT;
-constexpr int kRowThreads = fast25k::kRowThreads;
+using pcps::fastn::kRowT;
+using pcps::fastn::kRowThreads;
 constexpr int kRowPitch = fast25k::kRowPitch;
-constexpr int row_tiles(int n1) { return (n1 + kRowT - 1) / kRowT; }
-constexpr int records_per_transform(int n1) { return row_tiles(n1) * (kRowThreads / 64); }
+using pcps::fastn::row_tiles;
 
 // 25-point inverse transform of v[m], m = m1 + 5 m2: result A[kA + 5 kB] in v[5 kA + kB]  (tw = w_N^k table)
 template <int N>
@@ -337,8 +341,7 @@ inline void run_n(PassArgs a, int batch, double2* Z, hipStream_t stream) {
     run_rows<N1, STORE>(a, batch, Z, stream);
 }
 
-inline bool handles(int N) { return N == 4000 || N == 10000 || N == 50000; }
-inline int records(int N) { return records_per_transform(N / N2); }
+// (pcps::fastn::handles: N = 4 000, 10 000, 50 000)
 template <int STORE>
 inline void run(int N, PassArgs a, int batch, double2* Z, hipStream_t stream) {
     if (N == 4000) run_n<20, 1, 100, STORE>(a, batch, Z, stream);
@@ -347,3 +350,4 @@ inline void run(int N, PassArgs a, int batch, double2* Z, hipStream_t stream) {
 }
 
 }  // namespace fastn
+}  // namespace

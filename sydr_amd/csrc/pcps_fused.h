@@ -104,7 +104,7 @@ using fusedwork::WorkItem;
 struct Args {
     const double2* spec;       // [nbins][N] forward spectra of the Doppler-mixed block
     // Doppler bins whose frequencies differ by a whole number of transform bins (250 Hz steps over 1 ms: every fourth) have
-    // the SAME spectrum, circularly shifted (pcps.hip: shared spectra): when given, bin b's spectrum starts spec_off[b]
+    // the SAME spectrum, circularly shifted (pcps_plan.h: shared spectra): when given, bin b's spectrum starts spec_off[b]
     // elements into `spec` -- a row of its class with the shift taken out of a halo in front of it.
     const long long* spec_off;
     const double2* code_spec;  // [n_prn][N]

@@ -15,12 +15,6 @@ static_assert(fusedwork::kRecordsPerUnit == SDR_PCPS_FUSED_RECORDS, "records per
 static_assert(sizeof(fused10k::UnitRecord) == SDR_PCPS_FUSED10K_RECORD_BYTES, "unit record");
 }  // namespace
 
-// (terms: 1 at N = 25 000; 2 at N = 50 000, where a unit is one parity of a (PRN, bin) transform and the plan sees
-// 2 nbins virtual bins)
-int sdr_pcps_fused_records_per_prn(int n_prn, int nbins, int terms) {
-    return fusedwork::fused_records_per_prn(n_prn, nbins, terms);
-}
-
 // C: [n_prn][N] code spectra at N = 25 000; [n_prn][2][N] at N = 50 000 -- the spectrum and its image with the odd half's
 // twiddle folded in (pcps.hip code_parity_kernel).
 int sdr_pcps_fused_sweep(sdr_engine* e, const void* F, const void* spec_off, const void* C, const void* tw, int n_prn, int nbins, int N,

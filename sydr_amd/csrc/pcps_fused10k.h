@@ -48,7 +48,7 @@ struct UnitRecord {        // what a (PRN, bin) unit leaves: its row's first max
 
 struct Args {
     const double2* spec;       // [noncoh][nbins][N] forward spectra of the Doppler-mixed blocks
-    // shared spectra (pcps.hip): a block is blk_stride elements long, bin b's spectrum starts spec_off[b] elements into it
+    // shared spectra (pcps_plan.h): a block is blk_stride elements long, bin b's spectrum starts spec_off[b] elements into it
     // (spec_off == nullptr: b * N, blk_stride = nbins * N)
     const long long* spec_off;
     long long blk_stride;

@@ -36,7 +36,7 @@ inline int fused_plan(int n_prn, int nbins, int* bins_whole, int pieces) {
     return bw + pieces * (nbins - bw);
 }
 
-// records per PRN the sweep leaves (sdr_pcps_fused_records_per_prn: what the second sweep reads a PRN's records with)
+// records per PRN the sweep leaves (pcps_plan.h records_per_prn: what the second sweep reads a PRN's records with)
 inline int fused_records_per_prn(int n_prn, int nbins, int terms) {
     int bw;
     return fused_plan(n_prn, terms * nbins, &bw, fused_pieces(terms)) * kRecordsPerUnit;
@@ -75,7 +75,7 @@ inline WorkKey fused_work_key(int n_prn, int nbins, int terms, bool shared_spect
 inline int make_work_list(int n_prn, int nbins, int bins_whole, std::vector<WorkItem>& order, int first[9], int pieces,
                           int block_bins) {
     // block_bins: bins of a block of 32 whole transforms (x 32 / block_bins PRNs).  4 x 8 shares 4 spectra + 8 code spectra;
-    // with SHARED spectra (pcps.hip: a handful of class arrays serve every bin, and stay in the L2s) 16 x 2 shares the classes
+    // with SHARED spectra (pcps_plan.h: a handful of class arrays serve every bin, and stay in the L2s) 16 x 2 shares the classes
     // + 2 code spectra, 32 x 1 the classes + 1: half the operand arrays an XCD has in flight, or fewer.
     const int block_prns = kSlotsPerXcd / block_bins;
     // pieces: 5 = one unit per round; 3 = rounds {0, 1}, {2, 3}, {4} (N = 50 000: the operand stage of a unit costs what four

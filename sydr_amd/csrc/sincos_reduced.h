@@ -1,5 +1,5 @@
 // fp64 sin/cos of a phase of up to ~1e6 rad, shared by the correlators (correlator.h) and the acquisition's carrier
-// wipe-off (pcps.hip).
+// wipe-off (pcps_fft.h).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -14,7 +14,7 @@
 
 namespace sdr {
 
-constexpr int kXcds = 8;   // XCDs of the device: the `& 7` / `>> 3` of the PCPS workgroup mappings (pcps.hip, pcps_fast.h, pcps_fused.h)
+constexpr int kXcds = 8;   // XCDs of the device: the `& 7` / `>> 3` of the PCPS workgroup mappings (pcps_fft.h, pcps_fast.h, pcps_fused.h)
 
 // b: linear workgroup id, n: workgroups of the launch, R: run length (0: linear order).  The partial last tile keeps the
 // linear order.  One division by a run-time value, the rest shifts and selects -- no branch: in a kernel the loads of its

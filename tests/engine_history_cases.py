@@ -246,7 +246,7 @@ SCENE_NAMES = tuple(_BUILDERS)
 
 # ------------------------------------------------------------------------------------------------------------ PCPS
 def classes(fs, nbins, step):
-    """P of plan_shared_spectra (pcps.hip): the smallest P <= 64 with 2 P <= bins whose P steps are a whole number q of
+    """P of plan_shared_spectra (pcps_plan.h): the smallest P <= 64 with 2 P <= bins whose P steps are a whole number q of
     transform bins (and q * ((bins - 1) / P) <= 4096), or 0: every bin its own forward transform."""
     N = orc.samples_per_code(fs)
     for P in range(1, 65):

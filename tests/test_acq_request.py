@@ -1,0 +1,43 @@
+"""What an acquisition request means (sydr_amd/csrc/acq_request.h) through tests/csrc/acq_request_check.hip, host only: the
+half-even samples per code, the status of every request that is wrong in one way -- per flavour of the check: the FFT
+searches and SerialSearch differ above 65535 bins or PRNs and on the code lengths -- and the grid length against NumPy's own
+len(np.arange(-R, R + 1, S)) for the pairs of test_doppler_grid_length_host_helper and a few thousand random ones (`make
+check-sanitize` runs the same program under the address and undefined-behaviour sanitizers)."""
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+
+
+@pytest.fixture(scope="module")
+def check(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("acq_request") / "acq_request_check")
+    subprocess.run([HIPCC, "-O1", "-std=c++17", "--cuda-host-only", "-ffp-contract=off", "-o", exe,
+                    os.path.join(REPO, "tests", "csrc", "acq_request_check.hip")], check=True, capture_output=True, timeout=300)
+    return exe
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+def test_single_faults_and_rounding(check):
+    out = subprocess.run([check], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and out.stdout.startswith("ok "), out.stdout[-2000:] + out.stderr[-2000:]
+    assert int(out.stdout.split()[1]) >= 3 * 25
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+def test_grid_length_is_numpys(check):
+    pairs = [(5000.0, 250.0), (5000.0, 100.0), (5000.0, 300.0), (7000.0, 125.0), (10.0, 3.0)]
+    rng = np.random.default_rng(20261020)
+    pairs += [(float(r), float(s)) for r, s in zip(rng.uniform(0.0, 20000.0, 3000), rng.uniform(0.5, 2000.0, 3000))]
+    # whole steps that divide 2 R + 1 or miss it by one: the ceil's own edge
+    pairs += [(float(r), float(s)) for r in range(0, 60) for s in (1.0, 2.0, 3.0, 7.0, 0.25)]
+    text = "".join("%s %s\n" % (r.hex(), s.hex()) for r, s in pairs)
+    out = subprocess.run([check, "grid"], input=text, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0
+    got = [int(x) for x in out.stdout.split()]
+    assert got == [len(np.arange(-r, r + 1, s)) for r, s in pairs]

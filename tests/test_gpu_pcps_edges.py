@@ -1,7 +1,7 @@
 """GPU parity at the edges of the map-free acquisition routes: the crafted streams of tests/pcps_edge_cases.py (every bin
 of the Doppler grid a winning row over the rotations; first and second peaks on the row's ends and on the boundary columns
 of the two-peak exclusion window) through ROUTE_FUSED (25 and 50 MHz), ROUTE_FUSED10K, ROUTE_SWEEPS and ROUTE_MAP
-(pcps.hip: plan_pcps) -- indices equal to the oracle's, ratios within 1e-9 relative, and each call against the same call
+(pcps_plan.h: plan_pcps) -- indices equal to the oracle's, ratios within 1e-9 relative, and each call against the same call
 taken off its route (general kernels, two-kernel sweeps, the map written): equal indices, ratios to rounding.
 tests/test_pcps_edge_cases.py shows on the CPU that every one-column change of the window rule moves some ratio of every
 stream by more than 1e-3."""
@@ -208,3 +208,56 @@ def test_fused_sweep_from_a_start_above_64(engine):
     assert _fills_a_fused_round(case)
     _stage(engine, case, start=4321)
     _on_and_off_route(engine, case, "fused 25 MHz, start 4321", 4321)
+
+
+@pytest.mark.gpu
+def test_acquisition_entry_points_refuse_alike(engine):
+    """sdr_pcps, sdr_acq_deep and sdr_serial_search derive what a request means and check it through one header
+    (sydr_amd/csrc/acq_request.h): a request wrong in one way gets the same status from all three -- the statuses each has always
+    answered -- nothing reaches the device (no profiling scope records), and a good search afterwards returns the bytes it
+    returned before.  4 MHz (N = 4000), a ring of 8000 samples, two slots of which one is staged."""
+    from sydr_amd import _lib
+    from sydr_amd.engine import Engine
+    INVALID, RANGE, STATE = -1, -5, -6
+    fs = 4e6
+
+    def searches(e, slots=(0,), start=0, step=250.0, blocks=1):
+        return (lambda: e.pcps(slots, start, fs, 0.0, 5000.0, step, 1, blocks),
+                lambda: e.acq_deep(slots, start, fs, 0.0, 5000.0, step, 1, blocks),
+                lambda: e.serial_search(slots, start, fs, 5000.0, step, blocks))
+
+    def refused(e, status, word="", **request):
+        for search in searches(e, **request):
+            with pytest.raises(_lib.SdrError) as err:
+                search()
+            assert err.value.status == status and word in str(err.value), (request, str(err.value))
+
+    def good(e):
+        pcps, deep, serial = (search() for search in searches(e, blocks=2))
+        return b"".join(np.asarray(a).tobytes() for a in (*pcps[:3], deep[0], *serial[:3]))
+
+    engine.iq_alloc(8000, FMT_CI8)
+    engine.code_slots(2)
+    engine.load_gps_code(0, 9)
+    engine.iq_synth([dict(prn=9, doppler=1250.0, code_phase=311.4, phase=0.3, amp=8.0)], fs, 12.0, 5, 0, 8000)
+    before = good(engine)
+    engine.prof_enable(True)
+    engine.prof_reset()
+    try:
+        refused(engine, INVALID, "not staged", slots=(1,))          # a slot that is not staged
+        refused(engine, INVALID, step=0.0)                          # no grid
+        refused(engine, RANGE, start=-1)
+        refused(engine, RANGE, blocks=3)                            # one block more than the ring holds
+        refused(engine, INVALID, slots=())                          # n_prn = 0
+        assert engine.prof_read("")[1] == 0                         # no kernel, no scope: nothing reached the device
+    finally:
+        engine.prof_enable(False)
+        engine.prof_reset()
+    assert good(engine) == before
+    fresh = Engine(0)
+    try:
+        refused(fresh, STATE, "ring")
+        fresh.iq_alloc(8000, FMT_CI8)
+        refused(fresh, STATE, "slots")
+    finally:
+        fresh.close()

@@ -3,7 +3,8 @@ undefined-behaviour sanitizers -- `make -C sydr_amd/csrc check-sanitize` (CPU on
 the per-item check and per-item setups of sdr_epl_plan_create fed 600 000 hostile items (tests/csrc/fuzz_items.hip), the
 chip-geometry dump of test_plan_geometry.py, the exact-division identity of test_div_by_constant.py, the choice and
 decoding of an E/P/L plan's variant word (tests/csrc/epl_variant_dump.hip: grid, decode, rows) and the ring's sample formats
-read, written and dispatched (tests/csrc/ring_format_check.hip)."""
+read, written and dispatched (tests/csrc/ring_format_check.hip), the planner of an acquisition search
+(tests/csrc/pcps_plan_check.hip) and the one check of an acquisition request (tests/csrc/acq_request_check.hip)."""
 import os
 import shutil
 import subprocess
