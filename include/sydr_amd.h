@@ -39,7 +39,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define SDR_ABI_VERSION 5   /* 5 (still): + sdr_acq_deep_detect, sdr_detect_cfg / _peak / _noise (additive); 5 (still): + sdr_iq_cancel, sdr_cancel_stats (additive); 5 (still): + sdr_acq_deep, sdr_acq_deep_shift (additive); 5 (still): + sdr_ddc_cfg, sdr_ddc_create / _destroy / _reset / _push / _push_queue / _out_count (additive); 5 (still): + sdr_iq_probe (additive); 5 (still): + sdr_corr_profile, option "corr_profile_per_sample" (additive); 5 (still): + sdr_iq_packing, sdr_iq_packed_bytes, sdr_iq_upload_packed / _begin / _queue (additive); 5 (still): + sdr_acq_refine, sdr_acq_refine_bins (additive); 5: + sdr_bank_tick_mirrored_begin / _end, sdr_iq_upload_queue, sdr_host_alloc / _free, options "tick_server" + sdr_tick_server_stats, "bind_thread_to_device" (additive); 4: + sdr_build_id, sdr_epl_plan_create_dev, sdr_bank_tick_mirrored, sdr_iq_upload_begin, sdr_block_schedule, sdr_bank_step_begin / _end (additive) */
+#define SDR_ABI_VERSION 5   /* 5 (still): + sdr_pcps_signal, sdr_acq_signal (additive); 5 (still): + sdr_acq_deep_detect, sdr_detect_cfg / _peak / _noise (additive); 5 (still): + sdr_iq_cancel, sdr_cancel_stats (additive); 5 (still): + sdr_acq_deep, sdr_acq_deep_shift (additive); 5 (still): + sdr_ddc_cfg, sdr_ddc_create / _destroy / _reset / _push / _push_queue / _out_count (additive); 5 (still): + sdr_iq_probe (additive); 5 (still): + sdr_corr_profile, option "corr_profile_per_sample" (additive); 5 (still): + sdr_iq_packing, sdr_iq_packed_bytes, sdr_iq_upload_packed / _begin / _queue (additive); 5 (still): + sdr_acq_refine, sdr_acq_refine_bins (additive); 5: + sdr_bank_tick_mirrored_begin / _end, sdr_iq_upload_queue, sdr_host_alloc / _free, options "tick_server" + sdr_tick_server_stats, "bind_thread_to_device" (additive); 4: + sdr_build_id, sdr_epl_plan_create_dev, sdr_bank_tick_mirrored, sdr_iq_upload_begin, sdr_block_schedule, sdr_bank_step_begin / _end (additive) */
 
 typedef struct sdr_engine sdr_engine;
 
@@ -237,6 +237,40 @@ int sdr_pcps_bins(double doppler_range, double doppler_step);
 int sdr_two_peak_compare(sdr_engine* e, const double* corr_map, int n_bins, int n_code,
                          int samples_per_chip, int64_t* peak_bin, int64_t* peak_code,
                          double* peak_ratio);
+
+/* The same search for any staged code: chip rate, code period and a zero-padded (linear) correlation (no counterpart in the
+ * reference, whose acquisition is GPS L1 C/A's; the NumPy statement is dsp.signalsearch.pcps_signal_statement).  All slots of
+ * a call hold codes of one length L; s0 = start_sample.
+ *   N = nearbyint(fs * L / chip_rate_hz) (half-even), T = N * (1 + pad); *n_code_out = N
+ *   r_p[k] = c_p[min(trunc((ts*k)/tc), L-1)], ts = 1/fs, tc = 1/chip_rate_hz, k < N  (UpsampleCode with the chip rate a parameter)
+ *   codeFFT_p = conj(fft(r_p followed by T - N zeros)),  bins = arange(-doppler_range, doppler_range+1, doppler_step)
+ * pad = 0: sdr_pcps's map with this N and this replica (circular correlation over one code period).
+ * pad = 1 (coh must be 1): for block j < noncoh and n < 2N
+ *   y[n] = x[s0 + j*N + n] * exp(-1j*(if_hz - bins[b])*(n*2*pi/fs))      (blocks advance by N and read 2N samples)
+ *   map[p][b][n] = sum_j | ifft( fft(y) * codeFFT_p )[n] |,  n < N only
+ * -- the linear correlation of two periods of signal with one period of code: a data sign that flips at a code boundary
+ * inside the window (a symbol as long as the code: E1-B/C, L5, L1C, B1C) no longer splits the peak over the Doppler bins.  The
+ * window is (noncoh + 1) * N samples (coh * noncoh * N with pad = 0); it may cross the ring's end where sdr_pcps's may.
+ * peak_bin / peak_code: the first maximum in row-major order; peak_ratio: sdr_two_peak_compare's on map[p] with
+ * samples_per_chip = excl_samples, or nearbyint(fs / chip_rate_hz) when that is 0.  A sub-carrier needs no field: BOC(1,1) is
+ * searched as its half-chip code at twice the chip rate (how the correlators track it), excl_samples covering the side
+ * peaks.  Sums are added in a fixed order: two identical calls return identical bits; {1.023e6, 0, 0} on 1023-chip slots is
+ * sdr_pcps, bit for bit.  corr_map (nullable): [n_prn][bins][N].
+ * SDR_ERR_INVALID: NULL sig, chip rate not finite or not positive, pad outside 0..1, negative excl_samples, non-zero
+ * reserved, pad = 1 with coh != 1, slots of different lengths, 2*excl_samples + 1 >= N, and every cause sdr_pcps names;
+ * SDR_ERR_UNSUPPORTED: T outside 2 .. 2^24; SDR_ERR_RANGE: a window longer than the ring.  A refused call changes nothing.
+ * Profiler scope "call_pcps_signal" around the call's kernels; the inner scopes are sdr_pcps's. */
+typedef struct sdr_acq_signal {
+    double  chip_rate_hz;   /* > 0, finite: chips per second of the staged codes                       */
+    int32_t pad;            /* 0: circular over one code period (sdr_pcps's model)
+                               1: linear correlation, code zero-padded to two periods                  */
+    int32_t excl_samples;   /* second-peak exclusion half-width; 0 = nearbyint(fs / chip_rate_hz)      */
+    int32_t reserved[2];    /* 0 */
+} sdr_acq_signal;
+int sdr_pcps_signal(sdr_engine* e, const sdr_acq_signal* sig, const int32_t* code_slots, int n_prn,
+                    int64_t start_sample, double fs, double if_hz, double doppler_range, double doppler_step,
+                    int coh, int noncoh, int64_t* peak_bin, int64_t* peak_code, double* peak_ratio,
+                    double* corr_map /* nullable [n_prn][bins][N] */, int* n_bins_out, int* n_code_out);
 
 /* SerialSearch acquisition (sydr/dsp/acquisition.py:119-155; plugin sydr/channel/channel_l1ca_kaplan_ss.py):
  *   map[prn][b][k] = sum over `noncoh` successive code periods of

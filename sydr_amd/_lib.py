@@ -98,6 +98,11 @@ DETECT_PEAK_DTYPE = np.dtype([("bin", np.int64), ("code", np.int64), ("code_end"
 DETECT_NOISE_DTYPE = np.dtype([("n_cells", np.int64), ("mean", np.float64), ("variance", np.float64)], align=True)
 
 
+class AcqSignal(C.Structure):
+    """sdr_acq_signal (include/sydr_amd.h): chip rate, padding and exclusion half-width of sdr_pcps_signal's search."""
+    _fields_ = [("chip_rate_hz", C.c_double), ("pad", C.c_int32), ("excl_samples", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 class CancelStats(C.Structure):
     """sdr_cancel_stats (include/sydr_amd.h): what sdr_iq_cancel wrote, changed and clipped."""
     _fields_ = [("samples_written", C.c_int64), ("samples_changed", C.c_int64), ("clipped_components", C.c_int64)]
@@ -269,6 +274,8 @@ _PROTOTYPES = {
                            C.c_int, C.c_int, _VP, _VP, _VP, _VP, C.POINTER(C.c_int)]),
     "sdr_pcps_spectra": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int64, C.c_double, C.c_double, C.c_double,
                                    C.c_double, C.c_int, C.c_int, _VP, _VP, _VP, _VP, C.POINTER(C.c_int)]),
+    "sdr_pcps_signal": (C.c_int, [_VP, C.POINTER(AcqSignal), _VP, C.c_int, C.c_int64, C.c_double, C.c_double, C.c_double,
+                                  C.c_double, C.c_int, C.c_int, _VP, _VP, _VP, _VP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "sdr_pcps_bins": (C.c_int, [C.c_double, C.c_double]),
     "sdr_two_peak_compare": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64),
                                        C.POINTER(C.c_int64), C.POINTER(C.c_double)]),

@@ -90,7 +90,7 @@ struct sdr_engine {
     std::vector<int32_t> code_len_host;
     std::vector<int64_t> code_stamp;      // per slot: value of code_stamp_counter when the slot was last staged
     int64_t code_stamp_counter = 0;
-    std::vector<int64_t> pcps_spec_key;   // what pcps_code currently holds: [N, fs bits, (slot, stamp) ...]
+    std::vector<int64_t> pcps_spec_key;   // what pcps_code currently holds: [T, samples per code, fs bits, chip-rate bits, generation, (slot, stamp) ...]
     int n_slots = 0;
     int code_stride = 0;
     // per slot: the replica as the kernels want it in LDS -- uint32 high words of +-1.0 with the periodic

@@ -15,7 +15,8 @@
 // match NumPy's bit for bit, and a 1e-7 relative error could reorder near-ties.
 //
 // This file: the code spectra, the forward transforms, the four routes of a search (pcps_plan.h chooses), the deep search's
-// driver and the entry points.  The transforms are pcps_fft.h's, the peak kernels pcps_peak.h's, what a request means
+// driver and the entry points (sdr_pcps_signal: the same search by chip rate and code period, circular or zero-padded over two
+// periods -- pcps_impl).  The transforms are pcps_fft.h's, the peak kernels pcps_peak.h's, what a request means
 // acq_request.h's; SerialSearch is serial_search.hip.  docs/notes/pcps_layout.md has the map.
 #include "engine_internal.h"
 #include <chrono>
@@ -54,19 +55,25 @@ __global__ __launch_bounds__(kThreads) void code_parity_kernel(const double2* __
     out[((size_t)prn * 2 + 1) * N + k] = o;
 }
 
+// The replica of one code period, N samples at chip period tc, followed by T - N zeros (T == N: none; the zero-padded search
+// of sdr_pcps_signal transforms two periods' length).
 __global__ __launch_bounds__(kThreads) void upsample_batch_kernel(const int8_t* __restrict__ codes,
                                                                   const int32_t* __restrict__ code_len,
                                                                   int code_stride, const int32_t* __restrict__ slots,
-                                                                  double ts, double tc, int N,
+                                                                  double ts, double tc, int N, int T,
                                                                   int8_t* __restrict__ out) {
     int k = blockIdx.x * kThreads + threadIdx.x;
-    if (k >= N) return;
-    const int slot = slots[blockIdx.y];
-    const int L = code_len[slot];
-    double v = (ts * (double)k) / tc;  // gnsssignal.py:53
-    int idx = (int)trunc(v);
-    if (idx >= L) idx = L - 1;
-    out[(size_t)blockIdx.y * N + k] = codes[(size_t)slot * code_stride + idx];
+    if (k >= T) return;
+    int8_t chip = 0;
+    if (k < N) {
+        const int slot = slots[blockIdx.y];
+        const int L = code_len[slot];
+        double v = (ts * (double)k) / tc;  // gnsssignal.py:53
+        int idx = (int)trunc(v);
+        if (idx >= L) idx = L - 1;
+        chip = codes[(size_t)slot * code_stride + idx];
+    }
+    out[(size_t)blockIdx.y * T + k] = chip;
 }
 
 // map += |csum| (acquisition.py:68)
@@ -134,9 +141,12 @@ int code_spectra(sdr_engine* e, const PcpsPlan& p, const PcpsCall& c) {
     const int N = p.N, n_prn = p.n_prn;
     std::vector<int64_t> key;
     if (c.slots) {
-        int64_t fs_bits;
+        // (the transform length, the samples per code inside it, both rates: a circular and a zero-padded search of the same
+        // slots, or two chip rates of one code, never share spectra)
+        int64_t fs_bits, chip_bits;
         memcpy(&fs_bits, &p.fs, sizeof(fs_bits));
-        key = {(int64_t)N, fs_bits, e->code_generation};
+        memcpy(&chip_bits, &p.chip_rate, sizeof(chip_bits));
+        key = {(int64_t)N, (int64_t)p.cols, fs_bits, chip_bits, e->code_generation};
         for (int i = 0; i < n_prn; ++i) {
             key.push_back(c.slots[i]);
             key.push_back(e->code_stamp[c.slots[i]]);
@@ -155,7 +165,7 @@ int code_spectra(sdr_engine* e, const PcpsPlan& p, const PcpsCall& c) {
     {
         ProfScope ps(e, "pcps_upsample");
         hipLaunchKernelGGL(upsample_batch_kernel, dim3((N + kThreads - 1) / kThreads, n_prn), dim3(kThreads), 0,
-                           e->stream, e->codes, e->code_len, e->code_stride, c.d_slots, 1.0 / p.fs, 1.0 / 1.023e6, N, up);
+                           e->stream, e->codes, e->code_len, e->code_stride, c.d_slots, 1.0 / p.fs, 1.0 / p.chip_rate, p.cols, N, up);
     }
     PassArgs a = {};
     a.tw = (const double2*)e->pcps_tw.ptr;
@@ -170,7 +180,8 @@ int code_spectra(sdr_engine* e, const PcpsPlan& p, const PcpsCall& c) {
 }
 
 // Forward transforms of the Doppler-mixed millisecond number `block` (coherent index ic), `batch` bins (or classes of
-// shared spectra, written with their halos: F holds P rows of H + N) at once.
+// shared spectra, written with their halos: F holds P rows of H + N) at once.  A block starts p.cols samples behind the one
+// before it and is p.N samples long: the zero-padded search's blocks overlap by one code period.
 template <int FMT>
 void forward(sdr_engine* e, const PcpsPlan& p, const PcpsCall& c, int batch, int64_t block, int ic, int iq_blocks) {
     PassArgs f = {};
@@ -178,7 +189,7 @@ void forward(sdr_engine* e, const PcpsPlan& p, const PcpsCall& c, int batch, int
     f.N = p.N;
     f.ring = e->iq;
     f.capacity = e->iq_capacity;
-    f.first_sample = c.start + block * p.N;
+    f.first_sample = c.start + block * p.cols;
     f.carrier_offset = (int64_t)ic * p.N;
     f.fs = p.fs;
     f.if_hz = c.if_hz;
@@ -199,7 +210,8 @@ PassArgs sweep_args(const sdr_engine* e, const PcpsPlan& p, int p0) {
     g.code_spec = (const double2*)e->pcps_code.ptr + (size_t)p0 * p.N;
     g.nbins = p.nbins;
     g.scale = 1.0 / (double)p.N;
-    g.map = (double*)e->pcps_map.ptr + (size_t)p0 * p.nbins * p.N;
+    g.map = (double*)e->pcps_map.ptr + (size_t)p0 * p.nbins * p.cols;
+    g.cols = p.cols;
     g.csum = e->pcps_csum.ptr ? (double2*)e->pcps_csum.ptr + (size_t)p0 * p.nbins * p.N : nullptr;
     return g;
 }
@@ -304,7 +316,7 @@ int run_sweeps(sdr_engine* e, const PcpsPlan& p, const PcpsCall& c) {
 // ones first), then its peaks.
 template <int FMT>
 int run_map(sdr_engine* e, const PcpsPlan& p, const PcpsCall& c) {
-    const int n_prn = p.n_prn, nbins = p.nbins, N = p.N;
+    const int n_prn = p.n_prn, nbins = p.nbins, N = p.cols;      // (the map's columns)
     double2* A = (double2*)e->pcps_a.ptr;
     double2* B = (double2*)e->pcps_b.ptr;
     double* map = (double*)e->pcps_map.ptr;
@@ -314,7 +326,10 @@ int run_map(sdr_engine* e, const PcpsPlan& p, const PcpsCall& c) {
             for (int p0 = 0; p0 < n_prn; p0 += p.prn_chunk) {
                 const int pc = std::min(n_prn - p0, p.prn_chunk);
                 PassArgs g = sweep_args(e, p, p0);
-                if (p.coh == 1) {
+                if (p.cols != p.N) {       // (zero-padded: coh == 1; the inverse pass reads no ring sample, one format serves)
+                    g.first_block = inc == 0;
+                    run_fft<true, LOAD_MUL_CODE, STORE_MAG_KEEP, SDR_FMT_CF64>(e, p.xf, g, pc * nbins, A, B, nullptr, "pcps_inv_fft", c.blu);
+                } else if (p.coh == 1) {
                     g.first_block = inc == 0;
                     run_fft<true, LOAD_MUL_CODE, STORE_MAG_ACC, FMT>(e, p.xf, g, pc * nbins, A, B, nullptr, "pcps_inv_fft", c.blu);
                 } else {
@@ -495,22 +510,34 @@ int sdr_two_peak_compare(sdr_engine* e, const double* corr_map, int n_bins, int 
     return SDR_OK;
 }
 
-static int pcps_impl(sdr_engine* e, const int32_t* code_slots, const double* code_spectra, int n_code_in, int n_prn,
-                     int64_t start_sample, double fs, double if_hz, double doppler_range, double doppler_step,
-                     int coh, int noncoh, int64_t* peak_bin, int64_t* peak_code, double* peak_ratio,
-                     double* corr_map, int* n_bins_out) {
+// by_signal: sdr_pcps_signal's request (acq_signal_check: `sig` gives the chip rate, the padding and the exclusion window,
+// the slots the code length); else sdr_pcps's and sdr_pcps_spectra's.  Behind the check the two are one search: a transform
+// length, the samples per code kept of it, a chip rate.
+static int pcps_impl(sdr_engine* e, bool by_signal, const sdr_acq_signal* sig, const int32_t* code_slots, const double* code_spectra,
+                     int n_code_in, int n_prn, int64_t start_sample, double fs, double if_hz, double doppler_range,
+                     double doppler_step, int coh, int noncoh, int64_t* peak_bin, int64_t* peak_code, double* peak_ratio,
+                     double* corr_map, int* n_bins_out, int* n_code_out) {
     if (int rc = sdr_set_device(e)) return rc;
     if (!peak_bin || !peak_code || !peak_ratio) return sdr_fail(SDR_ERR_INVALID, "NULL peak outputs");
     sdr::AcqRequest rq = sdr_acq_request(e, code_slots, n_prn, start_sample, fs, doppler_range, doppler_step,
                                          coh < 1 || noncoh < 1 ? 0 : (int64_t)coh * noncoh);
     rq.n_code = n_code_in;
     sdr::AcqShape shape;
-    int rc = sdr::acq_request_check(rq, sdr::kAcqLimitsPcps, &shape);
-    const int nbins = shape.grid.nbins, N = shape.N;
+    sdr::AcqSignalShape sg;
+    int rc;
+    if (by_signal) {
+        rc = sdr::acq_signal_check(rq, sig, coh, noncoh, &shape, &sg);
+    } else {
+        rc = sdr::acq_request_check(rq, sdr::kAcqLimitsPcps, &shape);
+        sg.N = sg.T = shape.N, sg.chip_rate = 1.023e6;
+    }
+    // N: the transform length; cols: the samples per code = the map's columns
+    const int nbins = shape.grid.nbins, N = sg.T, cols = sg.N;
     if (n_bins_out && nbins > 0) *n_bins_out = nbins;
     if (rc) return sdr_fail(rc, "%s", shape.text);
+    if (n_code_out) *n_code_out = cols;
     const PcpsPlan p = plan_pcps(pcps_switches(e), N, shape.spc, fs, nbins, shape.grid.bin_start, shape.grid.bin_delta, coh, noncoh,
-                                 n_prn, corr_map != nullptr);
+                                 n_prn, corr_map != nullptr, cols, sg.chip_rate);
 
     const void* code2_before = e->pcps_code2.ptr;
     const std::pair<DevBuf*, size_t> bufs[] = {{&e->pcps_fwd, p.fwd_bytes}, {&e->pcps_a, p.work_bytes}, {&e->pcps_b, p.work_bytes},
@@ -546,7 +573,7 @@ static int pcps_impl(sdr_engine* e, const int32_t* code_slots, const double* cod
 
     {
         // (one event pair around every kernel of the search: its in-stream time; while it records, the search stays on one stream)
-        ProfScope whole(e, "call_pcps");
+        ProfScope whole(e, by_signal ? "call_pcps_signal" : "call_pcps");
         rc = sdr::with_fmt(e->iq_fmt, [&](auto fmt) { return pcps_search<decltype(fmt)::value>(e, p, c); });
     }
     if (rc) {
@@ -558,7 +585,7 @@ static int pcps_impl(sdr_engine* e, const int32_t* code_slots, const double* cod
     }
 
     if (corr_map)
-        SDR_HIP(hipMemcpyAsync(corr_map, e->pcps_map.ptr, (size_t)n_prn * nbins * N * sizeof(double),
+        SDR_HIP(hipMemcpyAsync(corr_map, e->pcps_map.ptr, (size_t)n_prn * nbins * cols * sizeof(double),
                                hipMemcpyDeviceToHost, e->stream));
     bool seen = false;
     if (p.done_words) {       // (bounded: a launch that died never raises the words -- the stream is asked then)
@@ -586,8 +613,15 @@ int sdr_pcps(sdr_engine* e, const int32_t* code_slots, int n_prn, int64_t start_
              double doppler_range, double doppler_step, int coh, int noncoh, int64_t* peak_bin,
              int64_t* peak_code, double* peak_ratio, double* corr_map, int* n_bins_out) {
     if (!code_slots) return sdr_fail(SDR_ERR_INVALID, "code_slots is NULL");
-    return pcps_impl(e, code_slots, nullptr, 0, n_prn, start_sample, fs, if_hz, doppler_range, doppler_step, coh,
-                     noncoh, peak_bin, peak_code, peak_ratio, corr_map, n_bins_out);
+    return pcps_impl(e, false, nullptr, code_slots, nullptr, 0, n_prn, start_sample, fs, if_hz, doppler_range, doppler_step, coh,
+                     noncoh, peak_bin, peak_code, peak_ratio, corr_map, n_bins_out, nullptr);
+}
+
+int sdr_pcps_signal(sdr_engine* e, const sdr_acq_signal* sig, const int32_t* code_slots, int n_prn, int64_t start_sample, double fs,
+                    double if_hz, double doppler_range, double doppler_step, int coh, int noncoh, int64_t* peak_bin,
+                    int64_t* peak_code, double* peak_ratio, double* corr_map, int* n_bins_out, int* n_code_out) {
+    return pcps_impl(e, true, sig, code_slots, nullptr, 0, n_prn, start_sample, fs, if_hz, doppler_range, doppler_step, coh, noncoh,
+                     peak_bin, peak_code, peak_ratio, corr_map, n_bins_out, n_code_out);
 }
 
 int sdr_pcps_spectra(sdr_engine* e, const double* code_spectra, int n_prn, int n_code, int64_t start_sample,
@@ -595,8 +629,8 @@ int sdr_pcps_spectra(sdr_engine* e, const double* code_spectra, int n_prn, int n
                      int64_t* peak_bin, int64_t* peak_code, double* peak_ratio, double* corr_map,
                      int* n_bins_out) {
     if (!code_spectra || n_code < 2) return sdr_fail(SDR_ERR_INVALID, "code_spectra is NULL or too short");
-    return pcps_impl(e, nullptr, code_spectra, n_code, n_prn, start_sample, fs, if_hz, doppler_range, doppler_step,
-                     coh, noncoh, peak_bin, peak_code, peak_ratio, corr_map, n_bins_out);
+    return pcps_impl(e, false, nullptr, nullptr, code_spectra, n_code, n_prn, start_sample, fs, if_hz, doppler_range, doppler_step,
+                     coh, noncoh, peak_bin, peak_code, peak_ratio, corr_map, n_bins_out, nullptr);
 }
 
 

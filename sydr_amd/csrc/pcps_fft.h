@@ -32,7 +32,10 @@ using pcps::FAST_25K;
 enum LoadMode { LOAD_PLAIN = 0, LOAD_IQ_MIX = 1, LOAD_MUL_CODE = 2, LOAD_CODE_REAL = 3, LOAD_MUL_CODE_SEL = 4 };
 // STORE_MAG_MAX: nothing is stored -- the last stage keeps a running (maximum, first index) of |.|/N per wave and
 // writes one 16-byte record per wave (the map-free search: the caller only wants indices and ratio).
-enum StoreMode { STORE_PLAIN = 0, STORE_CONJ = 1, STORE_MAG_ACC = 2, STORE_CPLX_ACC = 3, STORE_MAG_MAX = 4 };
+// STORE_MAG_KEEP: STORE_MAG_ACC for the first `cols` outputs of every transform alone, at row pitch `cols` (the zero-padded
+// search of sdr_pcps_signal: the lags at and beyond one code period of a two-period transform are neither turned into
+// magnitudes nor written).
+enum StoreMode { STORE_PLAIN = 0, STORE_CONJ = 1, STORE_MAG_ACC = 2, STORE_CPLX_ACC = 3, STORE_MAG_MAX = 4, STORE_MAG_KEEP = 5 };
 
 
 struct PassArgs {
@@ -72,6 +75,8 @@ struct PassArgs {
     // STORE_PLAIN with a halo (shared spectra): row t of the output is halo + N elements long, element k goes to halo + k and
     // the row's last `halo` elements are written in front of it as well -- out[t][i] = X_t[(i - halo) mod N]
     int halo;
+    // STORE_MAG_KEEP: outputs kept per transform = the map's row pitch, 1 <= cols <= N
+    int cols;
 };
 
 __device__ __forceinline__ double2 cmul(double2 a, double2 b) {
@@ -222,6 +227,11 @@ __device__ __forceinline__ void store_elem(const PassArgs& a, int batch, int idx
         a.map[o] = a.first_block ? 0.0 + mag : a.map[o] + mag;
     } else if (STORE == STORE_MAG_MAX) {
         // (only the four-step row kernel implements the running maximum; the launcher never selects it elsewhere)
+    } else if (STORE == STORE_MAG_KEEP) {
+        if (idx >= a.cols) return;
+        const size_t k = (size_t)batch * a.cols + idx;
+        double mag = hypot(v.x * a.scale, v.y * a.scale);
+        a.map[k] = a.first_block ? 0.0 + mag : a.map[k] + mag;
     } else {
         double2 s = make_double2(v.x * a.scale, v.y * a.scale);
         a.csum[o] = a.first_block ? s : cadd(a.csum[o], s);
@@ -663,7 +673,17 @@ __global__ __launch_bounds__(kThreads) void fft4_rows_kernel(const PassArgs a, i
         }
         return;
     }
-    for (int e = threadIdx.x; e < N2 * T; e += kThreads) {
+    // Output k1 + N1*k2 of row k1: a row of the tile holds every N1-th lag.  STORE_MAG_KEEP ends the walk behind the last k2 that
+    // still has a lag below `cols` in the tile's first row (the rows after it reach `cols` no later): the discarded lags of
+    // the tile are not read from LDS, and store_elem drops what the last kept k2 holds beyond `cols`.  Lanes walk c fastest,
+    // so a wave's stores to one k2 are T adjacent doubles of a map row at either pitch.
+    int k2_end = N2;
+    if constexpr (STORE == STORE_MAG_KEEP) {
+        const int left = a.cols - k1_0;                       // (k1_0 < N1 <= cols is not required: left <= 0 keeps nothing)
+        k2_end = left <= 0 ? 0 : (left - 1) / N1 + 1;
+        if (k2_end > N2) k2_end = N2;
+    }
+    for (int e = threadIdx.x; e < k2_end * T; e += kThreads) {
         const int k2 = e / T, c = e - k2 * T;
         const int k1 = k1_0 + c;
         if (k1 < N1) store_elem<STORE>(a, batch, k1 + N1 * k2, res[k2 * pitch + c]);
@@ -800,6 +820,7 @@ __global__ __launch_bounds__(kThreads) void blu_post_kernel(const PassArgs a, co
     const int k = blockIdx.x * kThreads + threadIdx.x;
     const int batch = blockIdx.y;
     if (k >= a.N) return;
+    if (STORE == STORE_MAG_KEEP && k >= a.cols) return;
     double2 c = chirp[k];
     if (!INV) c.y = -c.y;
     const double inv_m = 1.0 / (double)M;
@@ -819,7 +840,8 @@ template <bool INV, int LOAD0, int STORE_LAST, int FMT>
 void run_bluestein(sdr_engine* e, const BluPlan& blu, PassArgs a, int batch, double2* final_out) {
     a.out = final_out;
     const int M = blu.M;
-    const dim3 gm((M + kThreads - 1) / kThreads, batch), gn((a.N + kThreads - 1) / kThreads, batch);
+    const int n_out = STORE_LAST == STORE_MAG_KEEP ? a.cols : a.N;      // (outputs the post kernel keeps)
+    const dim3 gm((M + kThreads - 1) / kThreads, batch), gn((n_out + kThreads - 1) / kThreads, batch);
     hipLaunchKernelGGL((blu_pre_kernel<LOAD0, FMT, INV>), gm, dim3(kThreads), 0, e->stream, a, blu.chirp, M, blu.x);
     PassArgs p = {};
     p.N = M;

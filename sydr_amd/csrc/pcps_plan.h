@@ -1,4 +1,4 @@
-// The plan of one acquisition search (sdr_pcps, sdr_pcps_spectra; the deep search takes the map route's): which of the four
+// The plan of one acquisition search (sdr_pcps, sdr_pcps_spectra, sdr_pcps_signal; the deep search takes the map route's): which of the four
 // routes it takes, how one transform is done, how many PRNs go into one inverse sweep, whether two streams alternate, how many
 // class spectra are shared, the chirp-z length and every buffer size -- and the layout of the result block the searches and
 // the peak comparisons hand their results over in.  Host arithmetic only, no HIP runtime and no engine in sight:
@@ -193,6 +193,11 @@ enum Route {
 struct PcpsPlan {
     int N = 0, spc = 0, nbins = 0, coh = 1, noncoh = 1, n_prn = 0;
     double fs = 0.0, bin_start = 0.0, bin_delta = 0.0;
+    // sdr_pcps_signal: N is the transform length T; the map keeps the first `cols` lags of every transform at row pitch
+    // `cols`, and the blocks of the window advance by `cols` samples (cols == N: the circular search, all of the above alike);
+    // chip_rate is what the replica is resampled with
+    int cols = 0;
+    double chip_rate = 1.023e6;
     Xform xf;                  // the length-N transform
     int M = 0;                 // chirp-z (Bluestein) length, 0 = none; xm its transform (plain loads: never `fast`)
     Xform xm;
@@ -242,14 +247,18 @@ inline int chirpz_length(int N) {
 }
 
 // The request (samples per code N and per chip spc, Doppler grid, integration, PRNs, map wanted) and the engine's switches ->
-// the plan.
+// the plan.  The zero-padded search of sdr_pcps_signal hands in the transform length as N and the samples per code as `cols`
+// (0: N), and takes the map route: its last inverse pass stores the first `cols` lags alone.
 inline PcpsPlan plan_pcps(const PcpsSwitches& e, int N, int spc, double fs, int nbins, double bin_start, double bin_delta, int coh,
-                          int noncoh, int n_prn, bool want_map) {
+                          int noncoh, int n_prn, bool want_map, int cols = 0, double chip_rate = 1.023e6) {
     const size_t kComplexBytes = 2 * sizeof(double);
     PcpsPlan p;
     p.N = N, p.fs = fs, p.nbins = nbins, p.bin_start = bin_start, p.bin_delta = bin_delta;
     p.coh = coh, p.noncoh = noncoh, p.n_prn = n_prn;
     p.spc = spc;
+    p.cols = cols > 0 ? cols : N;
+    p.chip_rate = chip_rate;
+    const bool padded = p.cols != N;
     p.xf = plan_xform(e, N);
     const FourStep& four = p.xf.four;
     if (p.xf.radices.empty()) {
@@ -263,7 +272,7 @@ inline PcpsPlan plan_pcps(const PcpsSwitches& e, int N, int spc, double fs, int 
     int prn_chunk = (int)std::min<int64_t>(n_prn, std::max<int64_t>(1, (int64_t)((8ull << 30) / (std::max(tbytes, mbytes) * nbins))));
     if ((int64_t)prn_chunk * nbins > 65535) prn_chunk = std::max(1, 65535 / nbins);
     // Indices and ratio only, one block, four-step transform available: the map is never materialised.
-    const bool map_free = !want_map && coh == 1 && noncoh == 1 && !p.M && four.ok && !e.force_map;
+    const bool map_free = !want_map && coh == 1 && noncoh == 1 && !p.M && four.ok && !e.force_map && !padded;
     // The column kernel of an inverse sweep writes 16 N bytes per (PRN, bin) and the row kernel reads them back: as
     // many PRNs per sweep as keep that intermediate inside the 256 MB Infinity Cache (a 200 MB budget), in sweeps of
     // equal size -- 32 PRNs x 41 bins x 25 000: three sweeps of 11 / 11 / 10 PRNs instead of one of 525 MB, measured
@@ -283,7 +292,7 @@ inline PcpsPlan plan_pcps(const PcpsSwitches& e, int N, int spc, double fs, int 
     p.prn_chunk = prn_chunk;
     // (32 units and more: below that the two-kernel path's many small workgroups finish sooner than one unit per CU)
     const bool fused10k = !want_map && coh == 1 && N == 10000 && !p.M && four.ok && !e.force_map && e.fused &&
-                          !e.no_fast && (int64_t)n_prn * nbins >= 32;
+                          !e.no_fast && (int64_t)n_prn * nbins >= 32 && !padded;
     const bool fused = map_free && fused_takes(e, four, n_prn, nbins);
     p.route = fused10k ? ROUTE_FUSED10K : fused ? ROUTE_FUSED : map_free ? ROUTE_SWEEPS : ROUTE_MAP;
     p.terms = fused ? fused_terms(e, four) : 0;
@@ -306,7 +315,7 @@ inline PcpsPlan plan_pcps(const PcpsSwitches& e, int N, int spc, double fs, int 
     p.code2_bytes = p.terms == 2 ? 2 * tbytes * n_prn : 0;
     // (the fused sweep leaves at most 5 x SDR_PCPS_FUSED_RECORDS records per transform, twice that at N = 50 000)
     const size_t n_records = map_free ? (size_t)n_prn * (nbins + 1) * std::max(std::max(p.records_second, p.records_sweep), 10 * SDR_PCPS_FUSED_RECORDS) + n_prn : 0;
-    p.map_bytes = (size_t)n_prn * ((map_free || fused10k) ? 1 : nbins) * N * sizeof(double);
+    p.map_bytes = (size_t)n_prn * ((map_free || fused10k) ? 1 : nbins) * p.cols * sizeof(double);
     p.csum_bytes = coh > 1 ? (size_t)n_prn * nbins * tbytes : 0;
     p.part_bytes = std::max(std::max((size_t)n_prn * kPeakParts, n_records) * kBestBytes,
                             fused10k ? (size_t)n_prn * nbins * SDR_PCPS_FUSED10K_RECORD_BYTES : 0);

@@ -631,7 +631,7 @@ class Engine:
     # ------------------------------------------------------------------ PRN replicas
     def code_slots(self, n_slots: int, max_chips: int = 1023, max_periods: int = 1):
         check(self._lib.sdr_code_slots_ex(self._h, int(n_slots), int(max_chips), int(max_periods)))
-        self.n_slots = int(n_slots)
+        self.n_slots, self.max_chips = int(n_slots), int(max_chips)
         self.code_generation = getattr(self, "code_generation", 0) + 1  # staged codes are gone
 
     def load_gps_code(self, slot: int, prn: int):
@@ -771,6 +771,33 @@ class Engine:
         check(self._lib.sdr_pcps_spectra(self._h, ptr(spec), n, n_code, int(start_sample), float(fs), float(if_hz),
                                          float(doppler_range), float(doppler_step), int(coh), int(noncoh), ptr(pb),
                                          ptr(pc), ptr(pr), ptr(cmap) if want_map else None, C.byref(nb)))
+        return pb, pc, pr, cmap
+
+    def pcps_signal(self, code_slots, start_sample, fs, if_hz, doppler_range, doppler_step, chip_rate_hz, pad=0,
+                    excl_samples=0, coh=1, noncoh=1, want_map=False, n_chips=None, reserved=(0, 0)):
+        """PCPS for any staged code (sdr_pcps_signal; the NumPy statement is dsp.signalsearch.pcps_signal_statement): the
+        slots' codes, all of one length, at `chip_rate_hz`; pad = 1 searches zero-padded over two code periods (coh = 1),
+        `excl_samples` is the second peak's exclusion half-width (0: round(fs / chip_rate_hz)).  `n_chips`: the slots' code
+        length where a map is wanted (None: read back from the first slot).
+        -> (peak_bin, peak_code, peak_ratio, map[n_prn][bins][N] or None)."""
+        slots = np.ascontiguousarray(code_slots, dtype=np.int32)
+        n = len(slots)
+        sig = _lib.AcqSignal(float(chip_rate_hz), int(pad), int(excl_samples), (C.c_int32 * 2)(int(reserved[0]), int(reserved[1])))
+        nbins = self._lib.sdr_pcps_bins(float(doppler_range), float(doppler_step))
+        cmap = None
+        if want_map:
+            if n_chips is None:
+                n_chips = len(self.read_code(int(slots[0]))) if n else 0
+            ratio = float(fs) * int(n_chips) / float(chip_rate_hz) if chip_rate_hz and chip_rate_hz > 0 else 0.0
+            n_code = int(np.rint(ratio)) if np.isfinite(ratio) and 0 <= ratio <= 1 << 24 else 0
+            cmap = np.empty((n, max(0, nbins), n_code), dtype=np.float64)
+        pb, pc, pr = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int64), np.empty(n, dtype=np.float64)
+        nb, nc = C.c_int(0), C.c_int(0)
+        check(self._lib.sdr_pcps_signal(self._h, C.byref(sig), ptr(slots), n, int(start_sample), float(fs), float(if_hz),
+                                        float(doppler_range), float(doppler_step), int(coh), int(noncoh), ptr(pb), ptr(pc),
+                                        ptr(pr), ptr(cmap) if want_map else None, C.byref(nb), C.byref(nc)))
+        if want_map and cmap.shape[2] != nc.value:
+            raise ValueError(f"map of {cmap.shape[2]} columns allocated, the search wrote {nc.value}")
         return pb, pc, pr, cmap
 
     def serial_search(self, code_slots, start_sample, fs, doppler_range, doppler_step, noncoh=1, want_map=False,
