@@ -453,6 +453,56 @@ int sdr_acq_refine(sdr_engine* e, const sdr_refine_item* items, int n_items, dou
                    double* power /* nullable [n_items][n_periods][K] */,
                    double* segment_sums /* nullable [n_items][n_periods][n_segments][2] */);
 
+/* ------------------------------- secondary-code phase and fine carrier frequency behind an acquisition
+ * The step behind sdr_pcps_signal's zero-padded search for signals whose sign may change at every code period (E1-B/C, L5,
+ * E5a/b, B1C): where the secondary (overlay) code stands, and with it the carrier to a fine grid's step.  For each item --
+ * code_slot (the staged PRIMARY code), sec_row (its row of sec_codes), start_sample = s0, a ring index at which a primary
+ * code period begins, carrier_hz = f0, code_hz -- with M = n_periods, S = n_segments, Ls = sec_len, c = the item's row:
+ *   Stage 1 is sdr_acq_refine's stage 1, word for word: N = nearbyint(fs * L / code_hz); segment (m, s) covers window samples
+ *   [m*N + (s*N)/S, m*N + ((s+1)*N)/S) = [a, b); z[m][s] = EPL's prompt with the rem_carrier, rem_code and code_step written
+ *   there; tau[m][s] = (a + b - 1) / 2 / fs.
+ *   Frequencies: K = 2*floor(span_hz/step_hz) + 1 (sdr_acq_refine_bins), d_k = (k - (K-1)/2) * step_hz,
+ *   Z[m][k] = sum_s z[m][s] * exp(-2j*pi*d_k*tau[m][s]).
+ *   Hypotheses: h, 0 <= h < Ls, means that period 0 of the window carries secondary chip c[h]: w_h(m) = c[(h + m) mod Ls].
+ *   mode SDR_SEC_PILOT: X[h][k] = sum_m w_h(m) Z[m][k], P[h][k] = |X[h][k]|^2.
+ *   mode SDR_SEC_DATA (a data symbol as long as the secondary period: L5-I, E5a-I): periods are grouped by
+ *   g = (h + m) div Ls, P[h][k] = sum_g | sum_{m in g} w_h(m) Z[m][k] |^2, partial groups at the window's ends included.
+ *   Result: (h*, k*) = first maximum of P in row-major (h, k) order; sec_phase = h*, fine_idx = k*, fine_hz = f0 + d_k*,
+ *   power = P[h*][k*], power_other = max of P[h][k] over h != h*, all k; prompt = X[h*][k*] (SDR_SEC_DATA: 0.0, 0.0).
+ * n_periods need not be a multiple of sec_len and may be below it (a partial-code search).  One call serves all items; all
+ * stages run on the device on the engine's stream; every sum has a fixed order and no atomics (two identical calls return
+ * identical bits, whatever else the engine has done).  power (nullable) receives P as [n_items][sec_len][K], segment_sums
+ * (nullable) z as [n_items][n_periods][n_segments][2].
+ * A window that holds NaN / Inf samples (a float ring) is reported as sdr_acq_refine reports it: power = power_other = NaN,
+ * fine_hz = f0, fine_idx = (K-1)/2, sec_phase = 0, prompt 0.
+ * Limits: n_periods 2..128, sec_len 2..128, n_segments 1..64 with n_periods * n_segments <= 2048, K <= 4096, n_sec 1..n_items
+ * with every sec_row inside it, mode 0 or 1.
+ * SDR_ERR_INVALID: NULL items / sec_codes / results, counts outside these ranges, a secondary chip that is neither +1 nor -1,
+ * a bad sec_row, a slot that is not staged, a bad grid, a non-finite carrier or a non-positive code_hz; SDR_ERR_UNSUPPORTED:
+ * n_periods * n_segments > 2048, n_segments > N, K > 4096, a code period of more than ~16 000 chips or 2^30 samples;
+ * SDR_ERR_RANGE: a window longer than the ring, a negative start_sample; SDR_ERR_STATE: no ring or no code slots.  A refused
+ * call changes nothing.
+ * sdr_prof_enable scopes: "call_secondary" around "secondary_segments", "secondary_search", "secondary_pick". */
+typedef struct sdr_sec_item {
+    int32_t code_slot;      /* the staged PRIMARY code                                   */
+    int32_t sec_row;        /* which row of sec_codes this item's signal carries         */
+    int64_t start_sample;   /* a ring index at which a primary code period begins        */
+    double  carrier_hz, code_hz;
+} sdr_sec_item;
+typedef struct sdr_sec_result {
+    double  fine_hz, power, power_other;  /* power_other: max of P[h][k] over h != sec_phase, all k */
+    double  prompt_re, prompt_im;         /* mode 0: the coherent sum X[h*][k*]; mode 1: 0.0, 0.0    */
+    int32_t fine_idx, sec_phase;
+} sdr_sec_result;
+#define SDR_SEC_PILOT 0
+#define SDR_SEC_DATA  1
+int sdr_acq_secondary(sdr_engine* e, const sdr_sec_item* items, int n_items,
+                      const int8_t* sec_codes /* [n_sec][sec_len], each +1 or -1 */, int n_sec, int sec_len,
+                      double fs, int n_periods, int n_segments, double span_hz, double step_hz, int mode,
+                      sdr_sec_result* results,
+                      double* power /* nullable [n_items][sec_len][K] */,
+                      double* segment_sums /* nullable [n_items][n_periods][n_segments][2] */);
+
 /* ------------------------------- deep acquisition: folded coherent blocks, code-Doppler shift, bit-edge groups
  * The search for weak signals (opt-in like sdr_acq_refine; sdr_pcps is unchanged).  N, the Doppler grid d_b = bins[b]
  * (np.arange(-doppler_range, doppler_range + 1, doppler_step)), the code spectra codeFFT_p = conj(fft(UpsampleCode(code_p)))

@@ -55,6 +55,26 @@ REFINE_RESULT_DTYPE = np.dtype([("fine_hz", np.float64), ("power", np.float64), 
                                 ("fine_idx", np.int32), ("bit_edge", np.int32)], align=True)
 
 
+class SecItem(C.Structure):
+    """sdr_sec_item (include/sydr_amd.h): a primary code slot, its row of the secondary codes, where a code period begins."""
+    _fields_ = [("code_slot", C.c_int32), ("sec_row", C.c_int32), ("start_sample", C.c_int64),
+                ("carrier_hz", C.c_double), ("code_hz", C.c_double)]
+
+
+class SecResult(C.Structure):
+    """sdr_sec_result (include/sydr_amd.h)."""
+    _fields_ = [("fine_hz", C.c_double), ("power", C.c_double), ("power_other", C.c_double),
+                ("prompt_re", C.c_double), ("prompt_im", C.c_double), ("fine_idx", C.c_int32), ("sec_phase", C.c_int32)]
+
+
+SEC_ITEM_DTYPE = np.dtype([("code_slot", np.int32), ("sec_row", np.int32), ("start_sample", np.int64),
+                           ("carrier_hz", np.float64), ("code_hz", np.float64)], align=True)
+SEC_RESULT_DTYPE = np.dtype([("fine_hz", np.float64), ("power", np.float64), ("power_other", np.float64),
+                             ("prompt_re", np.float64), ("prompt_im", np.float64), ("fine_idx", np.int32),
+                             ("sec_phase", np.int32)], align=True)
+SEC_PILOT, SEC_DATA = 0, 1
+
+
 class DdmCfg(C.Structure):
     """sdr_ddm_cfg (include/sydr_amd.h): the tap grid, the frequency grid and the blocks / segments of a delay-Doppler map."""
     _fields_ = [("fs", C.c_double), ("first_chips", C.c_double), ("step_chips", C.c_double), ("span_hz", C.c_double),
@@ -285,6 +305,8 @@ _PROTOTYPES = {
                                           C.POINTER(C.c_double)]),
     "sdr_acq_refine_bins": (C.c_int, [C.c_double, C.c_double]),
     "sdr_acq_refine": (C.c_int, [_VP, _VP, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double, _VP, _VP, _VP]),
+    "sdr_acq_secondary": (C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double,
+                                    C.c_int, _VP, _VP, _VP]),
     "sdr_acq_deep": (C.c_int, [_VP, _VP, C.c_int, C.c_int64, C.POINTER(DeepCfg), _VP, _VP]),
     "sdr_acq_deep_shift": (C.c_int64, [C.POINTER(DeepCfg), C.c_int, C.c_int64]),
     "sdr_acq_deep_detect": (C.c_int, [_VP, _VP, C.c_int, C.c_int64, C.POINTER(DeepCfg), C.POINTER(DetectCfg), _VP, _VP, _VP, _VP]),

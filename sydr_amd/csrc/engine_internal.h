@@ -119,6 +119,8 @@ struct sdr_engine {
     int pcps_tickets_n = 0;
     DevBuf refine_ws;             // sdr_acq_refine (refine.hip): [items][segment sums][results][power table]
     std::vector<char> refine_host;   // ... and the host image of its item list (the source of the upload)
+    DevBuf secondary_ws;          // sdr_acq_secondary (secondary.hip): [items][sec rows][segment sums][partials][results][power table]
+    std::vector<char> secondary_host;   // ... and the host image of its item list and secondary rows (the source of the upload)
     DevBuf deep_fold, deep_mag, deep_q;   // sdr_acq_deep (pcps.hip run_deep): a block's folded periods [bins][N], the magnitudes of one
                                           // inverse sweep [PRNs of the sweep][bins][N], the shift table [blocks][bins]
     DevBuf deep_det;                      // sdr_acq_deep_detect (acq_detect.hip): the peaks, the noise figures and a pass's partials

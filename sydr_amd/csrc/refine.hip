@@ -10,76 +10,16 @@
 #include <algorithm>
 #include <cmath>
 
-#include "correlator.h"
+#include "refine_segments.h"
 
 namespace {
 
 using namespace sdr;
 
-constexpr int kRefineMaxPeriods = 20;    // one data bit: at most one edge inside the window
-constexpr int kRefineMaxSegments = 64;
-constexpr int kRefineMaxBins = 4096;
-constexpr int kRefineMaxLutWords = 16 * 1024 - 64;   // the replica of ONE period in the default 64 KB of dynamic LDS
 constexpr int kSearchThreads = 256;
 
-struct RefineItemDev {   // what the kernels need of one sdr_refine_item
-    int32_t slot, N;     // N = samples per code period
-    int64_t base;        // start_sample modulo the ring's capacity
-    double f0, code_step;
-    int32_t lut_words, reserved;   // words of the slot's LDS image one period needs: checked against the row and the LDS by the host
-};
-
-__constant__ double kPromptSpacing[1] = {0.0};
-
-// Window samples [a, b) of segment (m, s): a = m*N + (s*N)/S, b = m*N + ((s+1)*N)/S.
-__device__ __forceinline__ void segment_bounds(int N, int S, int m, int s, int64_t& a0, int64_t& a, int64_t& b) {
-    a0 = ((int64_t)s * N) / S;
-    a = (int64_t)m * N + a0;
-    b = (int64_t)m * N + ((int64_t)(s + 1) * N) / S;
-}
-
-template <int FMT>
-__global__ __launch_bounds__(64) void refine_segments_kernel(const void* __restrict__ ring, int64_t capacity,
-                                                             const RefineItemDev* __restrict__ items, int M, int S,
-                                                             const uint32_t* __restrict__ luts, int lut_stride, double fs,
-                                                             double2* __restrict__ z) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t refine_lut[];
-    const int lane = threadIdx.x;
-    const int per_item = M * S;
-    const int item = blockIdx.x / per_item, q = blockIdx.x - item * per_item;
-    const int m = q / S, s = q - m * S;
-    const RefineItemDev it = items[item];
-    // one code period of the staged replica: chip indices 0 .. L + 1 of the padded table
-    stage_lut<64>(refine_lut, luts + (size_t)it.slot * lut_stride, it.lut_words, lane);
-
-    int64_t a0, a, b;
-    segment_bounds(it.N, S, m, s, a0, a, b);
-    EpochParams ep;
-    ep.start_sample = it.base + a;
-    ep.n = (int)(b - a);
-    ep.carrier_hz = it.f0;
-    // the coarse carrier's phase runs on through the window: (-(f0*2.0*pi*a/fs)) mod 2*pi, in [0, 2*pi)
-    double rem = fmod(-((((it.f0 * 2.0) * M_PI) * (double)a) / fs), 2.0 * M_PI);
-    if (rem < 0.0) rem += 2.0 * M_PI;
-    ep.rem_carrier = uniform(rem);
-    ep.rem_code = (double)a0 * it.code_step;
-    ep.code_step = it.code_step;
-    const double dphi = carrier_step(it.f0, fs);
-    EpochConsts<1> K;
-    compute_constants<1>(K, ep, kPromptSpacing, dphi, 64);
-    __syncthreads();   // replica staged
-
-    double accr[1], acci[1];
-    correlate_epoch<FMT, 1>(ring, capacity, ep, dphi, K, refine_lut, lane, 64, lane, accr, acci);
-    const double re = wave_sum(accr[0]), im = wave_sum(acci[0]);
-    if (lane == 0) z[blockIdx.x] = make_double2(re, im);
-}
-
-// (value, index) records order by value, then by the LOWER index: the first maximum in row-major (h, k) order.
-// A NaN never wins a comparison: a window that holds NaN / Inf samples (a float ring) keeps the initial record, which
-// the last thread turns into power = power_no_edge = NaN, fine_hz = f0, fine_idx = (K-1)/2, bit_edge = 0.
-__device__ __forceinline__ bool better(double v, int i, double bv, int bi) { return v > bv || (v == bv && i < bi); }
-
+// better() (refine_segments.h): a NaN never wins a comparison, so a window that holds NaN / Inf samples (a float ring) keeps
+// the initial record, which the last thread turns into power = power_no_edge = NaN, fine_hz = f0, fine_idx = (K-1)/2, bit_edge = 0.
 __global__ __launch_bounds__(kSearchThreads) void refine_search_kernel(const RefineItemDev* __restrict__ items, int M, int S, int K,
                                                                        double step_hz, double fs, const double2* __restrict__ z,
                                                                        double* __restrict__ power /* nullable */,
@@ -190,31 +130,14 @@ int sdr_acq_refine(sdr_engine* e, const sdr_refine_item* items, int n_items, dou
     // (the engine's own block, not a local: the list outlives every return below, whatever state its copy is in)
     e->refine_host.resize((size_t)n_items * sizeof(RefineItemDev));
     RefineItemDev* host = reinterpret_cast<RefineItemDev*>(e->refine_host.data());
+    const RefineRing ring{e->iq_capacity, e->n_slots, e->code_len_host.data(), e->lut_stride};
     int max_words = 0;
     for (int i = 0; i < n_items; ++i) {
         const sdr_refine_item& it = items[i];
-        if (it.code_slot < 0 || it.code_slot >= e->n_slots || e->code_len_host[it.code_slot] <= 0)
-            return sdr_fail(SDR_ERR_INVALID, "item %d: code slot %d is not staged", i, it.code_slot);
-        if (!(it.code_hz > 0.0) || !std::isfinite(it.code_hz) || !std::isfinite(it.carrier_hz))
-            return sdr_fail(SDR_ERR_INVALID, "item %d: non-finite carrier or non-positive code frequency", i);
-        if (it.start_sample < 0) return sdr_fail(SDR_ERR_RANGE, "item %d: negative start_sample", i);
-        const int L = e->code_len_host[it.code_slot];
-        const double n_exact = std::nearbyint(fs * (double)L / it.code_hz);   // samples per code period
-        if (!(n_exact >= 1.0) || n_exact * M > (double)e->iq_capacity)
-            return sdr_fail(SDR_ERR_RANGE, "item %d: a window of %d code periods of %.0f samples, ring holds %lld", i, M, n_exact,
-                            (long long)e->iq_capacity);
-        if (n_exact > (double)(1 << 30))
-            return sdr_fail(SDR_ERR_UNSUPPORTED, "item %d: a code period of %.0f samples (at most 2^30)", i, n_exact);
-        const int N = (int)n_exact;
-        if (S > N) return sdr_fail(SDR_ERR_UNSUPPORTED, "item %d: %d segments in a code period of %d samples", i, S, N);
-        const double code_step = it.code_hz / fs;
-        // the chip indices a period reaches (ceil(N * code_step) + 1 at most) must lie inside the staged row and fit the LDS
-        const int words = (int)std::ceil((double)N * code_step) + SDR_LUT_PAD + 4;
-        if (words > e->lut_stride || words > kRefineMaxLutWords)
-            return sdr_fail(SDR_ERR_UNSUPPORTED, "item %d: a code period of %d chips (at most %d)", i, L,
-                            std::min(e->lut_stride, kRefineMaxLutWords) - SDR_LUT_PAD - 4);
-        max_words = std::max(max_words, words);
-        host[i] = RefineItemDev{it.code_slot, N, it.start_sample % e->iq_capacity, it.carrier_hz, code_step, words, 0};
+        char text[200];
+        if (int rc = refine_admit_item(ring, i, it.code_slot, it.start_sample, it.carrier_hz, it.code_hz, fs, M, S, &host[i], text, sizeof text))
+            return sdr_fail(rc, "%s", text);
+        max_words = std::max(max_words, (int)host[i].lut_words);
     }
 
     // one workspace: [items][z: n*M*S complex][results][power: n*M*K, when asked for]
@@ -235,13 +158,7 @@ int sdr_acq_refine(sdr_engine* e, const sdr_refine_item* items, int n_items, dou
         ProfScope whole(e, "call_refine");
         {
             ProfScope ps(e, "refine_segments");
-            const dim3 grid((unsigned)(n_items * M * S)), block(64);
-            const size_t shmem = (size_t)((max_words + 3) & ~3) * sizeof(uint32_t);
-            with_fmt(e->iq_fmt, [&](auto fmt) {
-                hipLaunchKernelGGL(refine_segments_kernel<decltype(fmt)::value>, grid, block, shmem, e->stream, (const void*)e->iq,
-                                   e->iq_capacity, d_items, M, S, e->luts, e->lut_stride, fs, d_z);
-            });
-            SDR_HIP(hipGetLastError());
+            if (int rc = refine_launch_segments(e, d_items, n_items, M, S, max_words, fs, d_z)) return rc;
         }
         {
             ProfScope ps(e, "refine_search");

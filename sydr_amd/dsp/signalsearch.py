@@ -8,10 +8,22 @@ chips long) flips sign at a code boundary, and that boundary lies inside almost 
 correlation over one period then splits its peak over the neighbouring Doppler bins.  pad = 1 correlates two periods of
 signal with one period of code followed by zeros -- a linear correlation, whose lags below one period each see one whole,
 unbroken code period -- and keeps those lags alone.  A BOC(1,1) signal is searched as its half-chip code (`boc_doubled`) at
-twice the chip rate, with `excl_samples` covering the side peaks."""
+twice the chip rate, with `excl_samples` covering the side peaks.
+
+Behind that search, `SecondarySync` (sdr_acq_secondary) finds where the secondary (overlay) code of such a signal stands and
+its carrier to a fine grid's step; NH10 and NH20 are the two Neuman-Hofman codes (L5-I, L5-Q), the only secondary tables here."""
 from __future__ import annotations
 
 import numpy as np
+
+
+def _bits(text):
+    """'0' -> +1, '1' -> -1."""
+    return np.array([1 if b == "0" else -1 for b in text], dtype=np.int8)
+
+
+NH10 = _bits("0000110101")
+NH20 = _bits("00000100110101001110")
 
 
 def boc_doubled(code):
@@ -119,3 +131,32 @@ def PCPSSignal(rfData, interFrequency, samplingFrequency, code, chipRate, dopple
                                        excl_samples=exclSamples, coh=coherentIntegration, noncoh=nonCoherentIntegration,
                                        want_map=True, n_chips=len(chips))
     return np.squeeze(np.squeeze(cmap[0])), [int(pb[0]), int(pc[0])], float(pr[0])
+
+
+def SecondarySync(rfData, samplingFrequency, code, chipRate, secondary, coarseFrequency, nbPeriods, nbSegments=4,
+                  frequencySpan=125.0, frequencyStep=5.0, mode=0):
+    """Secondary-code phase and fine carrier frequency behind an acquisition (the definition is sdr_acq_secondary's in
+    include/sydr_amd.h), on the GPU, in the shape of dsp.acquisition.FineFrequencySearch.  `rfData` starts where a period of
+    the primary `code` (its chips, at `chipRate`) begins and holds `nbPeriods` periods; `secondary` = the +-1 chips of the
+    overlay code, one per primary period; `coarseFrequency` = the carrier the search found (IF included); mode 0: a pilot,
+    1: a data symbol as long as the secondary period.
+    -> (fineFrequency, secPhase, powerRatio, P[len(secondary)][K]): secPhase = the secondary chip the first period carries,
+    powerRatio = the best cell over the best cell of any other phase."""
+    from ..engine import FMT_CF64, make_secondary_items
+    from ..runtime import get_engine
+    rf = np.squeeze(np.asarray(rfData, dtype=np.complex128))
+    chips = np.asarray(code)
+    need = samples_per_code(samplingFrequency, len(chips), chipRate) * int(nbPeriods)
+    if rf.size < need:
+        raise ValueError(f"SecondarySync needs {need} samples, got {rf.size}")
+    eng = get_engine()
+    if getattr(eng, "n_slots", 0) < 4 or getattr(eng, "max_chips", 0) < len(chips):
+        eng.code_slots(4, max(4092, len(chips)))
+    eng.set_code(3, chips.astype(np.int8))
+    cap = (need + 7) // 8 * 8
+    if eng.iq_fmt != FMT_CF64 or eng.iq_capacity < cap:
+        eng.iq_alloc(cap, FMT_CF64)
+    eng.iq_upload(rf[:need], 0)
+    res, power, _ = eng.acq_secondary(make_secondary_items(3, 0, 0, coarseFrequency, chipRate), np.asarray(secondary),
+                                      samplingFrequency, nbPeriods, nbSegments, frequencySpan, frequencyStep, mode, want_tables=True)
+    return float(res["fine_hz"][0]), int(res["sec_phase"][0]), float(res["power"][0] / res["power_other"][0]), power[0]

@@ -9,9 +9,11 @@ import numpy as np
 
 from . import _lib
 from ._lib import (EPL_ITEM_DTYPE, FMT_CF32, FMT_CF64, FMT_CI16, FMT_CI8, LOOP_CFG_DTYPE, REFINE_ITEM_DTYPE,
-                   REFINE_RESULT_DTYPE, TRACK_EPOCH_DTYPE, TRACK_STATE_DTYPE, LoopCfg, SynthSat, TrackState, check, ptr)
+                   REFINE_RESULT_DTYPE, SEC_ITEM_DTYPE, SEC_RESULT_DTYPE, TRACK_EPOCH_DTYPE, TRACK_STATE_DTYPE, LoopCfg, SynthSat,
+                   TrackState, check, ptr)
 
-__all__ = ["Engine", "EplPlan", "Bank", "make_items", "make_refine_items", "FMT_CI8", "FMT_CI16", "FMT_CF32", "FMT_CF64"]
+__all__ = ["Engine", "EplPlan", "Bank", "make_items", "make_refine_items", "make_secondary_items", "FMT_CI8", "FMT_CI16", "FMT_CF32",
+           "FMT_CF64"]
 
 
 def make_refine_items(code_slot, start_sample, carrier_hz, code_hz=1.023e6) -> np.ndarray:
@@ -19,6 +21,15 @@ def make_refine_items(code_slot, start_sample, carrier_hz, code_hz=1.023e6) -> n
     arrs = np.broadcast_arrays(code_slot, start_sample, carrier_hz, code_hz)
     items = np.zeros(arrs[0].shape, dtype=REFINE_ITEM_DTYPE).reshape(-1)
     for name, a in zip(("code_slot", "start_sample", "carrier_hz", "code_hz"), arrs):
+        items[name] = np.asarray(a).reshape(-1)
+    return items
+
+
+def make_secondary_items(code_slot, sec_row, start_sample, carrier_hz, code_hz) -> np.ndarray:
+    """Pack acquisition results (scalars or equal-length arrays) into sdr_sec_item records."""
+    arrs = np.broadcast_arrays(code_slot, sec_row, start_sample, carrier_hz, code_hz)
+    items = np.zeros(arrs[0].shape, dtype=SEC_ITEM_DTYPE).reshape(-1)
+    for name, a in zip(SEC_ITEM_DTYPE.names, arrs):
         items[name] = np.asarray(a).reshape(-1)
     return items
 
@@ -832,6 +843,31 @@ class Engine:
         check(self._lib.sdr_acq_refine(self._h, ptr(items), n, float(fs), int(n_periods), int(n_segments), float(span_hz),
                                        float(step_hz), ptr(res), ptr(power) if want_tables else None,
                                        ptr(z) if want_tables else None))
+        return (res, power, z) if want_tables else res
+
+    def acq_secondary(self, items, sec_codes, fs, n_periods, n_segments=4, span_hz=125.0, step_hz=5.0, mode=0, want_tables=False):
+        """Secondary-code phase and fine carrier frequency behind an acquisition (sdr_acq_secondary): `items` = sdr_sec_item
+        records (SEC_ITEM_DTYPE, see `make_secondary_items`), `sec_codes` = the +-1 secondary codes, one per row (a single
+        code may be given as one row) -- one call for all items.  mode 0: a pilot, 1: a data symbol as long as the secondary
+        period.  -> results (SEC_RESULT_DTYPE: fine_hz, power, power_other, prompt_re, prompt_im, fine_idx, sec_phase), and
+        with want_tables also (power[n][sec_len][K], segment_sums[n][n_periods][n_segments] complex)."""
+        items = np.ascontiguousarray(items, dtype=SEC_ITEM_DTYPE).reshape(-1)
+        sec = np.asarray(sec_codes)
+        if sec.ndim != 2:
+            sec = sec.reshape(1, -1)
+        if not np.array_equal(sec, sec.astype(np.int8)):
+            raise ValueError("secondary chips are +1 or -1")
+        sec = np.ascontiguousarray(sec, dtype=np.int8)
+        n = len(items)
+        res = np.zeros(n, dtype=SEC_RESULT_DTYPE)
+        power = z = None
+        if want_tables:
+            k = max(0, self.acq_refine_bins(span_hz, step_hz))
+            power = np.empty((n, sec.shape[1], k), dtype=np.float64)
+            z = np.empty((n, max(0, int(n_periods)), max(0, int(n_segments))), dtype=np.complex128)
+        check(self._lib.sdr_acq_secondary(self._h, ptr(items), n, ptr(sec), sec.shape[0], sec.shape[1], float(fs), int(n_periods),
+                                          int(n_segments), float(span_hz), float(step_hz), int(mode), ptr(res),
+                                          ptr(power) if want_tables else None, ptr(z) if want_tables else None))
         return (res, power, z) if want_tables else res
 
     def acq_deep(self, code_slots, start_sample, fs, if_hz, doppler_range, doppler_step, coh, noncoh, groups=1,
