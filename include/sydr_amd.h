@@ -275,9 +275,12 @@ int sdr_pcps_signal(sdr_engine* e, const sdr_acq_signal* sig, const int32_t* cod
 /* SerialSearch acquisition (sydr/dsp/acquisition.py:119-155; plugin sydr/channel/channel_l1ca_kaplan_ss.py):
  *   map[prn][b][k] = sum over `noncoh` successive code periods of
  *                    |sum_n x[n]*exp(+1j*bins[b]*n*2*pi/fs) * code[(trunc((ts*n)/tc) - k) mod L]|^2
- * for the L circular chip shifts k, and TwoCorrelationPeakComparison_SS (:159-193) on each map
- * (second peak = maximum outside the 3x3 block around the first, with Python's slice semantics).
- * corr_map (nullable) is [n_prn][bins][L]. */
+ * with ts = 1/fs, tc = 1/1.023e6, n < N = the samples of a code period, for the L circular chip shifts k, and
+ * TwoCorrelationPeakComparison_SS (:159-193) on each map (second peak = maximum outside the 3x3 block around
+ * the first, with Python's slice semantics).  The slots' codes have one length L <= 4096 that holds every chip a
+ * period's samples land on, L >= trunc((ts*(N-1))/tc) + 1 (1023 at 4 MHz, 1022 at 1.0 MHz): a shorter code is
+ * refused with SDR_ERR_INVALID, as the reference raises IndexError; a longer code's further chips enter through
+ * the circular shift alone.  corr_map (nullable) is [n_prn][bins][L]. */
 int sdr_serial_search(sdr_engine* e, const int32_t* code_slots, int n_prn, int64_t start_sample, double fs,
                       double doppler_range, double doppler_step, int noncoh, int64_t* peak_bin,
                       int64_t* peak_code, double* peak_ratio, double* corr_map, int* n_bins_out);

@@ -46,7 +46,8 @@ struct AcqLimits {
     const char* who;          // names the search in the ring-range text
     int grid_status;          // more than 65535 bins or PRNs: the FFT searches SDR_ERR_UNSUPPORTED, SerialSearch SDR_ERR_INVALID
     int length_status;        // samples per code outside 2 .. 2^24: SDR_ERR_UNSUPPORTED, SerialSearch SDR_ERR_RANGE
-    bool one_code_length;     // SerialSearch: the staged codes of a request have one length ...
+    bool one_code_length;     // SerialSearch: the staged codes of a request have one length, which holds every chip
+                              // index trunc((ts*n)/tc) of a code period's samples, n < N ...
     int max_chips;            // ... of at most this many chips (0: any)
 };
 constexpr AcqLimits kAcqLimitsPcps = {"acquisition", SDR_ERR_UNSUPPORTED, SDR_ERR_UNSUPPORTED, false, 0};
@@ -109,6 +110,16 @@ inline int acq_request_check(const AcqRequest& r, const AcqLimits& lim, AcqShape
         if (lim.one_code_length && s->chips && r.code_len[slot] != s->chips)
             return fail(SDR_ERR_INVALID, "the search needs codes of one length");
         s->chips = r.code_len[slot];
+    }
+    if (lim.one_code_length) {
+        // the highest chip a code period's samples land on, with the kernel's own expression (ss_chipsum_kernel): a code
+        // that ends before it has no chip for those samples (the reference raises IndexError there)
+        const double ts = 1.0 / r.fs, tc = 1.0 / 1.023e6;
+        const int reach = (int)std::trunc((ts * (double)(s->N - 1)) / tc) + 1;
+        if (s->chips < reach) {
+            snprintf(s->text, sizeof s->text, "codes of %d chips, the samples of a code period reach %d chips", s->chips, reach);
+            return SDR_ERR_INVALID;
+        }
     }
     if (lim.max_chips && s->chips > lim.max_chips) {
         snprintf(s->text, sizeof s->text, "codes longer than %d chips", lim.max_chips);

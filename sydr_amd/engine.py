@@ -812,12 +812,24 @@ class Engine:
         return pb, pc, pr, cmap
 
     def serial_search(self, code_slots, start_sample, fs, doppler_range, doppler_step, noncoh=1, want_map=False,
-                      n_chips=1023):
+                      n_chips=None):
+        """SerialSearch (sdr_serial_search) of the slots' codes, all of one length.  `n_chips`: that length where a map is
+        wanted (None: read back from the first slot; a value that disagrees with the slot raises ValueError, since the
+        library writes map[n_prn][bins][L] with the staged length L).
+        -> (peak_bin, peak_code, peak_ratio, map[n_prn][bins][L] or None)."""
         slots = np.ascontiguousarray(code_slots, dtype=np.int32)
         n = len(slots)
         nbins = self._lib.sdr_pcps_bins(float(doppler_range), float(doppler_step))
         pb, pc, pr = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int64), np.empty(n, dtype=np.float64)
-        cmap = np.empty((n, nbins, n_chips), dtype=np.float64) if want_map else None
+        cmap = None
+        if want_map:
+            try:
+                staged = len(self.read_code(int(slots[0]))) if n else 0
+            except _lib.SdrError:       # (no such slot, nothing staged: the search itself says what is wrong)
+                staged = 0
+            if n_chips is not None and staged and int(n_chips) != staged:
+                raise ValueError(f"n_chips = {int(n_chips)}, code slot {int(slots[0])} holds {staged} chips")
+            cmap = np.empty((n, max(0, nbins), staged), dtype=np.float64)
         nb = C.c_int(0)
         check(self._lib.sdr_serial_search(self._h, ptr(slots), n, int(start_sample), float(fs), float(doppler_range),
                                           float(doppler_step), int(noncoh), ptr(pb), ptr(pc), ptr(pr),

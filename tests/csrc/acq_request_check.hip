@@ -126,6 +126,37 @@ int main(int argc, char** argv) {
         expect(acq_request_check(r, kAcqLimitsDeep, &s) == SDR_OK, "deep: 5000 chips");
     }
     {
+        // SerialSearch alone: the code holds every chip index trunc((ts*n)/tc), n < N, that a code period's samples reach --
+        // 1023 at 4 MHz and at 1.023 MHz + 1 kHz, 1022 at 1.0 and 1.023 MHz; the rule follows the index, not the number 1023
+        static const int32_t lens[4] = {1022, 1023, 1021, 4096};
+        static const int32_t slot0[1] = {0}, slot1[1] = {1}, slot2[1] = {2}, slot3[1] = {3};
+        AcqShape s;
+        auto with = [&](const int32_t* slots, double fs) {
+            AcqRequest r = good(slots);
+            r.n_slots = 4, r.code_len = lens, r.fs = fs, r.doppler_range = 500.0, r.capacity = 1 << 20;
+            return r;
+        };
+        expect(acq_request_check(with(slot0, 4e6), kAcqLimitsSerial, &s) == SDR_ERR_INVALID && strstr(s.text, "1022") &&
+                   strstr(s.text, "1023"), "serial: 1022 chips at 4 MHz, the text names both numbers");
+        expect(acq_request_check(with(slot0, 4e6), kAcqLimitsPcps, &s) == SDR_OK && s.text[0] == 0, "pcps: 1022 chips at 4 MHz");
+        expect(acq_request_check(with(slot1, 4e6), kAcqLimitsSerial, &s) == SDR_OK && s.chips == 1023, "serial: 1023 chips at 4 MHz");
+        expect(acq_request_check(with(slot3, 4e6), kAcqLimitsSerial, &s) == SDR_OK && s.chips == 4096, "serial: 4096 chips at 4 MHz");
+        expect(acq_request_check(with(slot0, 1.0e6), kAcqLimitsSerial, &s) == SDR_OK && s.N == 1000 && s.chips == 1022,
+               "serial: 1022 chips at 1.0 MHz (highest index 1021)");
+        expect(acq_request_check(with(slot0, 1.023e6), kAcqLimitsSerial, &s) == SDR_OK && s.N == 1023,
+               "serial: 1022 chips at 1.023 MHz (highest index 1021)");
+        expect(acq_request_check(with(slot2, 1.0e6), kAcqLimitsSerial, &s) == SDR_ERR_INVALID && strstr(s.text, "1021") &&
+                   strstr(s.text, "1022"), "serial: 1021 chips at 1.0 MHz");
+        expect(acq_request_check(with(slot2, 1.023e6), kAcqLimitsSerial, &s) == SDR_ERR_INVALID, "serial: 1021 chips at 1.023 MHz");
+        expect(acq_request_check(with(slot0, 16.368e6), kAcqLimitsSerial, &s) == SDR_ERR_INVALID, "serial: 1022 chips at 16.368 MHz");
+        expect(acq_request_check(with(slot1, 16.368e6), kAcqLimitsSerial, &s) == SDR_OK, "serial: 1023 chips at 16.368 MHz");
+        // a slot that is not staged is named before the length is looked at
+        static const int32_t none[1] = {1};
+        AcqRequest r = good(none);
+        r.fs = 1.0e6;
+        expect(acq_request_check(r, kAcqLimitsSerial, &s) == SDR_ERR_INVALID && strstr(s.text, "not staged"), "serial: unstaged slot");
+    }
+    {
         // sdr_pcps_spectra: no slots, the code length is the caller's
         AcqShape s;
         AcqRequest r = good(nullptr);

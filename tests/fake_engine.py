@@ -313,8 +313,10 @@ OracleEngine.sync = lambda self: None
 
 
 def _serial_search(self, code_slots, start_sample, fs, doppler_range, doppler_step, noncoh=1, want_map=False,
-                   n_chips=1023):
+                   n_chips=None):
     n = orc.samples_per_code(fs)
+    if want_map and n_chips is not None and len(code_slots) and int(n_chips) != len(self.codes[int(code_slots[0])]):
+        raise ValueError(f"n_chips = {int(n_chips)}, code slot {int(code_slots[0])} holds {len(self.codes[int(code_slots[0])])} chips")
     maps, pb, pc, pr = [], [], [], []
     for s in code_slots:
         m = None

@@ -549,6 +549,35 @@ def make_serial():
          edge_maps=np.stack(edge_maps), edge_idx=np.array(edge_idx), edge_ratio=np.array(edge_ratio))
 
 
+# ---------------------------------------------------------------------------------------------- G9b
+def make_serial_rates():
+    """UpsampleCode's index and SerialSearch at rates where the index's rounding matters (whole multiples of the chip rate)
+    and where chips get no sample or two; a 2046-chip code.  The rates and the signal are tests/serial_cases.py's."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import serial_cases as sc
+    out = {}
+    ramp = np.arange(1023, dtype=np.float64)      # upsampling a ramp returns the index map itself
+    for rate in sc.RATES:
+        idx = ref_sig.UpsampleCode(ramp, rate.fs)
+        assert len(idx) == ref_sig.getSamplesPerCode(rate.fs) == rate.n
+        out[f"upsample_idx_{int(rate.fs)}"] = idx.astype(np.int16)
+    code = ref_sig.GenerateGPSGoldCode(sc.SAT["prn"])
+    for fs in (1.023e6, 2.046e6, 16.368e6):
+        n = ref_sig.getSamplesPerCode(fs)
+        raw = np.array(sc.samples(fs))
+        rf = (raw[0::2] + 1j * raw[1::2]).reshape(1, -1)
+        out[f"iq_{int(fs)}"] = raw
+        out[f"map_{int(fs)}"] = ref_acq.SerialSearch(rf, code, sc.GRID[0], sc.GRID[1], fs, n)
+    fs = 2.046e6
+    raw = out[f"iq_{int(fs)}"]
+    long_code = np.array(sc.random_code(2046), dtype=np.float64)
+    out["long_code"] = long_code.astype(np.int8)
+    out["long_map"] = ref_acq.SerialSearch((raw[0::2] + 1j * raw[1::2]).reshape(1, -1), long_code, sc.ONE_BIN[0], sc.ONE_BIN[1],
+                                           fs, ref_sig.getSamplesPerCode(fs))
+    save("g9b_serial_rates.npz", rates=np.array([r.fs for r in sc.RATES]), map_rates=np.array([1.023e6, 2.046e6, 16.368e6]),
+         grid=np.array(sc.GRID), long_grid=np.array(sc.ONE_BIN), prn=np.array(sc.SAT["prn"]), **out)
+
+
 # ---------------------------------------------------------------------------------------------- G7
 def make_loopmath():
     rng = np.random.default_rng(20260700)
@@ -576,6 +605,8 @@ if __name__ == "__main__":
     which = sys.argv[1:] or ["codes", "pcps", "peaks", "epl", "ref_c", "traj", "edges", "loop", "serial", "decoding"]
     if "serial" in which:
         make_serial()
+    if "serial_rates" in which:      # (by its own name only: the default list regenerates what it always did)
+        make_serial_rates()
     if "codes" in which:
         make_codes()
     if "pcps" in which:

@@ -26,7 +26,7 @@ def check(tmp_path_factory):
 def test_single_faults_and_rounding(check):
     out = subprocess.run([check], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and out.stdout.startswith("ok "), out.stdout[-2000:] + out.stderr[-2000:]
-    assert int(out.stdout.split()[1]) >= 3 * 25
+    assert int(out.stdout.split()[1]) >= 3 * 25 + 11      # (+ SerialSearch's short-code rule at 1.0, 1.023, 4 and 16.368 MHz)
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")

@@ -351,3 +351,38 @@ def test_serial_search_matches_reference():
     for m, i, q in zip(g["edge_maps"], g["edge_idx"], g["edge_ratio"]):
         gi, gq = orc.two_peak_compare_ss(m)
         assert gi == list(i) and gq == q
+
+
+# ------------------------------------------------------------------------------------------------ G9b rates where the index rounds
+def test_upsample_index_bit_exact_where_rounding_matters():
+    """below, at and at whole multiples of the chip rate (tests/serial_cases.py): at five of the eight rates the reference's
+    floating-point index differs from the exact quotient's for some samples, and the oracle's is the reference's"""
+    import serial_cases as sc
+    g = load_golden("g9b_serial_rates.npz")
+    assert list(g["rates"]) == [r.fs for r in sc.RATES]
+    differing = 0
+    for rate in sc.RATES:
+        ref = g[f"upsample_idx_{int(rate.fs)}"]
+        assert ref.dtype == np.int16 and len(ref) == rate.n == orc.samples_per_code(rate.fs)
+        assert np.array_equal(orc.upsample_index(rate.fs), ref)
+        assert np.count_nonzero(ref != sc.exact_index(rate.fs)) == rate.sensitive
+        differing += rate.sensitive > 0
+    assert differing == 5
+
+
+def test_serial_search_matches_reference_where_rounding_matters():
+    g = load_golden("g9b_serial_rates.npz")
+    code = orc.gold_code(int(g["prn"]))
+    for fs in g["map_rates"]:
+        raw = g[f"iq_{int(fs)}"]
+        n = orc.samples_per_code(float(fs))
+        assert len(raw) == 2 * n
+        m = orc.serial_search(orc.iq_to_complex(raw).reshape(1, -1), code, *g["grid"], float(fs), n)
+        np.testing.assert_allclose(m, g[f"map_{int(fs)}"], rtol=1e-13, atol=0)
+    # a 2046-chip code at 2.046 MHz, one bin: the chips past 1022 enter through the circular shift alone
+    fs = 2.046e6
+    long_code = g["long_code"].astype(np.float64)
+    assert len(long_code) == 2046
+    m = orc.serial_search(orc.iq_to_complex(g[f"iq_{int(fs)}"]).reshape(1, -1), long_code, *g["long_grid"], fs, 2046)
+    assert m.shape == (2046,)
+    np.testing.assert_allclose(m, g["long_map"], rtol=1e-13, atol=0)
