@@ -39,7 +39,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define SDR_ABI_VERSION 5   /* 5 (still): + sdr_pcps_signal, sdr_acq_signal (additive); 5 (still): + sdr_acq_deep_detect, sdr_detect_cfg / _peak / _noise (additive); 5 (still): + sdr_iq_cancel, sdr_cancel_stats (additive); 5 (still): + sdr_acq_deep, sdr_acq_deep_shift (additive); 5 (still): + sdr_ddc_cfg, sdr_ddc_create / _destroy / _reset / _push / _push_queue / _out_count (additive); 5 (still): + sdr_iq_probe (additive); 5 (still): + sdr_corr_profile, option "corr_profile_per_sample" (additive); 5 (still): + sdr_iq_packing, sdr_iq_packed_bytes, sdr_iq_upload_packed / _begin / _queue (additive); 5 (still): + sdr_acq_refine, sdr_acq_refine_bins (additive); 5: + sdr_bank_tick_mirrored_begin / _end, sdr_iq_upload_queue, sdr_host_alloc / _free, options "tick_server" + sdr_tick_server_stats, "bind_thread_to_device" (additive); 4: + sdr_build_id, sdr_epl_plan_create_dev, sdr_bank_tick_mirrored, sdr_iq_upload_begin, sdr_block_schedule, sdr_bank_step_begin / _end (additive) */
+#define SDR_ABI_VERSION 5   /* 5 (still): + sdr_pcps_coherent, sdr_coh_cfg / _result, option "coherent_scratch_kb" (additive); 5 (still): + sdr_pcps_signal, sdr_acq_signal (additive); 5 (still): + sdr_acq_deep_detect, sdr_detect_cfg / _peak / _noise (additive); 5 (still): + sdr_iq_cancel, sdr_cancel_stats (additive); 5 (still): + sdr_acq_deep, sdr_acq_deep_shift (additive); 5 (still): + sdr_ddc_cfg, sdr_ddc_create / _destroy / _reset / _push / _push_queue / _out_count (additive); 5 (still): + sdr_iq_probe (additive); 5 (still): + sdr_corr_profile, option "corr_profile_per_sample" (additive); 5 (still): + sdr_iq_packing, sdr_iq_packed_bytes, sdr_iq_upload_packed / _begin / _queue (additive); 5 (still): + sdr_acq_refine, sdr_acq_refine_bins (additive); 5: + sdr_bank_tick_mirrored_begin / _end, sdr_iq_upload_queue, sdr_host_alloc / _free, options "tick_server" + sdr_tick_server_stats, "bind_thread_to_device" (additive); 4: + sdr_build_id, sdr_epl_plan_create_dev, sdr_bank_tick_mirrored, sdr_iq_upload_begin, sdr_block_schedule, sdr_bank_step_begin / _end (additive) */
 
 typedef struct sdr_engine sdr_engine;
 
@@ -505,6 +505,66 @@ int sdr_acq_secondary(sdr_engine* e, const sdr_sec_item* items, int n_items,
                       sdr_sec_result* results,
                       double* power /* nullable [n_items][sec_len][K] */,
                       double* segment_sums /* nullable [n_items][n_periods][n_segments][2] */);
+
+/* ------------------------------- coherent search under secondary-code hypotheses
+ * The acquisition of a signal that carries a secondary (overlay) code, coherent across its code periods: where
+ * sdr_pcps_signal's zero-padded search adds the M periods of a window as magnitudes, this one adds the complex per-period
+ * correlations under every hypothesis of the overlay phase and every frequency of a fine grid, and returns code sample,
+ * Doppler bin, overlay phase and fine carrier in one call (opt-in by calling it; the NumPy statement is
+ * dsp.signalsearch.pcps_coherent_statement).  With M = n_periods, Ls = sec_len, c = the PRN's row sec_rows[p] of sec_codes,
+ * s0 = start_sample:
+ *   L, N, r_p, bins: exactly sdr_pcps_signal's.  T = 2N.  codeFFT_p = conj(fft(r_p followed by N zeros)).
+ *   Blocks: for m < M and n < 2N, y_m[n] = x[s0 + m*N + n] * exp(-1j*(if_hz - bins[b])*(n*2*pi/fs)).  This is block j = m of
+ *   sdr_pcps_signal's pad = 1.  The carrier restarts per block, as there.
+ *   Per-period correlation: C_m[b][tau] = ifft(fft(y_m) * codeFFT_p)[tau] for tau < N.  The complex value is kept.  It is the
+ *   linear correlation of the period that begins at window sample m*N + tau.
+ *   Rotation: g(m,b,k) = exp(-2j*pi*(if_hz - bins[b] + d_k)*(m*N)/fs).  This continues the carrier across blocks and moves it
+ *   by the fine offset.  K = sdr_acq_refine_bins(span_hz, step_hz), d_k = (k - (K-1)/2) * step_hz.
+ *   Hypotheses: w_h(m) = c[(h + m) mod Ls], as in sdr_acq_secondary.
+ *   Pilot mode (SDR_SEC_PILOT): X[b][h][k][tau] = sum_m w_h(m) g(m,b,k) C_m[b][tau], with m ascending.  P = |X|^2.
+ *   Data mode (SDR_SEC_DATA): periods are grouped by g = (h + m) div Ls.
+ *   P = sum_g |sum_{m in g} w_h(m) g(m,b,k) C_m[b][tau]|^2.  Partial groups at both ends are included.
+ *   Reduced map: R[p][b][tau] = sqrt(max_{h,k} P[b][h][k][tau]).  It is a magnitude, like every other map here, so the ini
+ *   files' ratio threshold means what it means elsewhere.  corr_map receives it.
+ *   Peak: peak_bin, peak_code and peak_ratio are sdr_two_peak_compare's on R[p], with samples_per_chip = excl_samples (or its
+ *   default).  The window quirks of the reference are kept, as in sdr_pcps_signal.
+ *   Pick at the peak cell: (h*, k*) is the first maximum of P[b*][.][.][tau*] in row-major (h, k) order.  power_other and
+ *   prompt are as in sdr_acq_secondary.  power receives that [Ls][K] table.
+ *   Window: (M + 1) * N samples.  It may cross the ring's end where sdr_pcps's may.  All four ring formats are supported.
+ *   Order: every sum has a fixed order and nothing is added atomically.  Maxima are taken with p > best, so NaN never wins,
+ *   as in refine / secondary (a cell whose every P is NaN has R = 0).  Two identical calls return identical bits, whatever the
+ *   engine did before.
+ * Limits: n_periods 2..128 and sec_len 2..128, neither needing to divide the other.  K <= 64 and sec_len * K <= 4096.
+ * n_sec 1..n_prn, with every sec_rows[p] inside it.  T within sdr_pcps_signal's 2..2^24.
+ * Statuses: sdr_pcps_signal's and sdr_acq_secondary's causes, each with the status it has there (K > 64 and
+ * sec_len * K > 4096: SDR_ERR_UNSUPPORTED, as K > 4096 there).  A refused call changes nothing.
+ * The per-period correlations of a chunk of (PRN, bin) units lie in a scratch of [M][units][T] complex doubles; the units are
+ * cut into chunks under a byte budget (sdr_set_option "coherent_scratch_kb", 0 = the default of 2 GiB; never less than one
+ * unit).  No result depends on the cut.
+ * sdr_prof_enable scopes: "call_pcps_coherent" around "coherent_fwd_fft", "coherent_inv_fft", "coherent_combine",
+ * "coherent_peak", "coherent_pick". */
+typedef struct sdr_coh_cfg {
+    double  chip_rate_hz;        /* as sdr_acq_signal                                                    */
+    double  span_hz, step_hz;    /* fine grid: K = sdr_acq_refine_bins(span_hz, step_hz), d_k = (k-(K-1)/2)*step_hz */
+    int32_t n_periods;           /* M: code periods added coherently (pilot) / per symbol group (data)   */
+    int32_t sec_len;             /* Ls                                                                   */
+    int32_t mode;                /* SDR_SEC_PILOT / SDR_SEC_DATA, sdr_acq_secondary's meaning            */
+    int32_t excl_samples;        /* as sdr_acq_signal; 0 = nearbyint(fs / chip_rate_hz)                  */
+    int32_t reserved[2];         /* 0 */
+} sdr_coh_cfg;
+typedef struct sdr_coh_result {
+    double  carrier_hz;          /* if_hz - bins[peak_bin] + d_{fine_idx}                                */
+    double  peak, peak_ratio;    /* R at the peak cell; sdr_two_peak_compare's ratio on R[p]             */
+    double  power, power_other;  /* P[h*][k*] at the peak cell; max of P[h][k], h != h*, at that cell    */
+    double  prompt_re, prompt_im;/* pilot: X[h*][k*] at the peak cell; data: 0.0, 0.0                    */
+    int64_t peak_code;           /* tau*: window sample at which a code period begins                    */
+    int32_t peak_bin, fine_idx, sec_phase, reserved;
+} sdr_coh_result;
+int sdr_pcps_coherent(sdr_engine* e, const sdr_coh_cfg* cfg, const int32_t* code_slots, const int32_t* sec_rows, int n_prn,
+                      const int8_t* sec_codes /* [n_sec][sec_len], +1 / -1 */, int n_sec,
+                      int64_t start_sample, double fs, double if_hz, double doppler_range, double doppler_step,
+                      sdr_coh_result* results /* [n_prn] */, double* corr_map /* nullable [n_prn][bins][N] */,
+                      double* power /* nullable [n_prn][sec_len][K] */, int* n_bins_out, int* n_code_out);
 
 /* ------------------------------- deep acquisition: folded coherent blocks, code-Doppler shift, bit-edge groups
  * The search for weak signals (opt-in like sdr_acq_refine; sdr_pcps is unchanged).  N, the Doppler grid d_b = bins[b]

@@ -75,6 +75,28 @@ SEC_RESULT_DTYPE = np.dtype([("fine_hz", np.float64), ("power", np.float64), ("p
 SEC_PILOT, SEC_DATA = 0, 1
 
 
+class CohCfg(C.Structure):
+    """sdr_coh_cfg (include/sydr_amd.h): chip rate, fine grid, periods, overlay length and mode of sdr_pcps_coherent."""
+    _fields_ = [("chip_rate_hz", C.c_double), ("span_hz", C.c_double), ("step_hz", C.c_double), ("n_periods", C.c_int32),
+                ("sec_len", C.c_int32), ("mode", C.c_int32), ("excl_samples", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class CohResult(C.Structure):
+    """sdr_coh_result (include/sydr_amd.h)."""
+    _fields_ = [("carrier_hz", C.c_double), ("peak", C.c_double), ("peak_ratio", C.c_double), ("power", C.c_double),
+                ("power_other", C.c_double), ("prompt_re", C.c_double), ("prompt_im", C.c_double), ("peak_code", C.c_int64),
+                ("peak_bin", C.c_int32), ("fine_idx", C.c_int32), ("sec_phase", C.c_int32), ("reserved", C.c_int32)]
+
+
+COH_CFG_DTYPE = np.dtype([("chip_rate_hz", np.float64), ("span_hz", np.float64), ("step_hz", np.float64),
+                          ("n_periods", np.int32), ("sec_len", np.int32), ("mode", np.int32), ("excl_samples", np.int32),
+                          ("reserved", np.int32, (2,))], align=True)
+COH_RESULT_DTYPE = np.dtype([("carrier_hz", np.float64), ("peak", np.float64), ("peak_ratio", np.float64),
+                             ("power", np.float64), ("power_other", np.float64), ("prompt_re", np.float64),
+                             ("prompt_im", np.float64), ("peak_code", np.int64), ("peak_bin", np.int32), ("fine_idx", np.int32),
+                             ("sec_phase", np.int32), ("reserved", np.int32)], align=True)
+
+
 class DdmCfg(C.Structure):
     """sdr_ddm_cfg (include/sydr_amd.h): the tap grid, the frequency grid and the blocks / segments of a delay-Doppler map."""
     _fields_ = [("fs", C.c_double), ("first_chips", C.c_double), ("step_chips", C.c_double), ("span_hz", C.c_double),
@@ -307,6 +329,8 @@ _PROTOTYPES = {
     "sdr_acq_refine": (C.c_int, [_VP, _VP, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double, _VP, _VP, _VP]),
     "sdr_acq_secondary": (C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double,
                                     C.c_int, _VP, _VP, _VP]),
+    "sdr_pcps_coherent": (C.c_int, [_VP, C.POINTER(CohCfg), _VP, _VP, C.c_int, _VP, C.c_int, C.c_int64, C.c_double, C.c_double,
+                                    C.c_double, C.c_double, _VP, _VP, _VP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "sdr_acq_deep": (C.c_int, [_VP, _VP, C.c_int, C.c_int64, C.POINTER(DeepCfg), _VP, _VP]),
     "sdr_acq_deep_shift": (C.c_int64, [C.POINTER(DeepCfg), C.c_int, C.c_int64]),
     "sdr_acq_deep_detect": (C.c_int, [_VP, _VP, C.c_int, C.c_int64, C.POINTER(DeepCfg), C.POINTER(DetectCfg), _VP, _VP, _VP, _VP]),

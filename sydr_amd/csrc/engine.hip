@@ -268,6 +268,10 @@ int sdr_set_option(sdr_engine* e, const char* name, int value) {
     }
     else if (!strcmp(name, "bind_thread_to_device")) return bind_thread_to_device(e, value);
     else if (!strcmp(name, "pcps_prn_chunk")) e->pcps_prn_chunk = value;
+    else if (!strcmp(name, "coherent_scratch_kb")) {
+        if (value < 0) return sdr_fail(SDR_ERR_RANGE, "coherent_scratch_kb %d is negative", value);
+        e->coh_scratch_kb = value;
+    }
     else if (!strcmp(name, "epl_no_chip_variant")) e->epl_no_chip = value != 0;
     else if (!strcmp(name, "epl_no_split_variant")) e->epl_no_split = value != 0;
     else if (!strcmp(name, "epl_xcd_run")) {
@@ -388,7 +392,7 @@ void sdr_engine_destroy(sdr_engine* e) {
     DevBuf* bufs[] = {&e->ws_items,  &e->ws_out,   &e->ws_spacing, &e->ws_setups, &e->ws_stats, &e->pcps_fwd,   &e->pcps_a,
                       &e->pcps_b,    &e->pcps_code, &e->pcps_code2, &e->pcps_tickets, &e->pcps_spec_off, &e->pcps_tw,   &e->pcps_map,   &e->pcps_csum,
                       &e->pcps_part, &e->pcps_res,  &e->track_state, &e->track_cfg,
-                      &e->pcps_blu,  &e->pcps_blu_x, &e->pcps_blu_a, &e->pcps_blu_b, &e->pcps_work, &e->pcps_theta, &e->refine_ws, &e->secondary_ws, &e->deep_fold, &e->deep_mag, &e->deep_q, &e->deep_det, &e->corr_ws, &e->unpack_stage, &e->probe_ws, &e->probe_tab, &e->ddc_stage, &e->cancel_ws, &e->ddm_ws};
+                      &e->pcps_blu,  &e->pcps_blu_x, &e->pcps_blu_a, &e->pcps_blu_b, &e->pcps_work, &e->pcps_theta, &e->refine_ws, &e->secondary_ws, &e->deep_fold, &e->deep_mag, &e->deep_q, &e->deep_det, &e->coh_scr, &e->coh_ws, &e->corr_ws, &e->unpack_stage, &e->probe_ws, &e->probe_tab, &e->ddc_stage, &e->cancel_ws, &e->ddm_ws};
     for (DevBuf* b : bufs)
         if (b->ptr) (void)hipFree(b->ptr);
     for (DevBuf& b : e->plan_pool)

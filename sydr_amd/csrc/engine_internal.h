@@ -123,6 +123,10 @@ struct sdr_engine {
     std::vector<char> secondary_host;   // ... and the host image of its item list and secondary rows (the source of the upload)
     DevBuf deep_fold, deep_mag, deep_q;   // sdr_acq_deep (pcps.hip run_deep): a block's folded periods [bins][N], the magnitudes of one
                                           // inverse sweep [PRNs of the sweep][bins][N], the shift table [blocks][bins]
+    DevBuf coh_scr, coh_ws;               // sdr_pcps_coherent (pcps.hip run_coherent): a chunk's per-period correlations [M][units][T];
+                                          // [overlay rows][row per PRN][running maxima][kept columns][results][power tables]
+    std::vector<char> coh_host;           // ... and the host image of its overlay rows and row numbers (the source of the upload)
+    int64_t coh_scratch_kb = 0;           // "coherent_scratch_kb": the byte budget of coh_scr in KB (0: coherent_request.h's default)
     DevBuf deep_det;                      // sdr_acq_deep_detect (acq_detect.hip): the peaks, the noise figures and a pass's partials
     DevBuf track_state, track_cfg;
     int n_cus = 0;              // compute units of the device (sizes the closed-loop clusters)

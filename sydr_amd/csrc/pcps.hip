@@ -16,13 +16,15 @@
 //
 // This file: the code spectra, the forward transforms, the four routes of a search (pcps_plan.h chooses), the deep search's
 // driver and the entry points (sdr_pcps_signal: the same search by chip rate and code period, circular or zero-padded over two
-// periods -- pcps_impl).  The transforms are pcps_fft.h's, the peak kernels pcps_peak.h's, what a request means
+// periods -- pcps_impl; sdr_pcps_coherent: that search's transforms with the complex results kept, run_coherent).  The transforms are pcps_fft.h's, the peak kernels pcps_peak.h's, what a request means
 // acq_request.h's; SerialSearch is serial_search.hip.  docs/notes/pcps_layout.md has the map.
 #include "engine_internal.h"
 #include <chrono>
 #include "acq_deep.h"
 #include "acq_request.h"
+#include "coherent_request.h"
 #include "detect_zone.h"
+#include "pcps_coherent.h"
 #include "pcps_fft.h"
 #include "pcps_fast.h"
 #include "pcps_fastn.h"
@@ -423,6 +425,78 @@ int run_deep(sdr_engine* e, const PcpsPlan& p, const PcpsCall& c, const DeepCall
     return SDR_OK;
 }
 
+// ---- the coherent search (sdr_pcps_coherent): the zero-padded search's transforms with the complex results kept.  Forward:
+// the padded route's, one launch per period, all M periods' spectra side by side ([M][nbins][T], PRN independent, made once
+// however the units are cut).  Per chunk of (PRN, bin) units (coherent_request.h coherent_chunk): M inverse sweeps with
+// STORE_CPLX_ACC as a plain store (first_block = 1) into the scratch [M][units][T] -- the instantiation of the map route's
+// coherent blocks, the code-spectrum product numbered inside the chunk -- then pcps_coherent.hip's combine into the chunk's
+// rows of R, the chunk's maxima and the kept column.  Behind the last chunk the map's peaks as run_deep takes them, and the
+// pick.  A transform does not depend on the batch it runs in, so no value depends on the cut.
+struct CohCall {
+    double2* scr = nullptr;      // [M][units of the largest chunk][T]
+    int cap = 0;                 // units a chunk may hold
+    void *best = nullptr, *keep = nullptr;
+    sdr_coh_result* results = nullptr;   // device
+    double* power = nullptr;             // device
+};
+
+template <int FMT>
+int run_coherent(sdr_engine* e, const PcpsPlan& p, const PcpsCall& c, const CohGeom& g, const CohCall& k) {
+    const int T = p.N, N = p.cols, nbins = p.nbins, n_prn = p.n_prn, M = g.M;
+    if (int rc = code_spectra<FMT>(e, p, c)) return rc;
+    double2* A = (double2*)e->pcps_a.ptr;
+    double2* B = (double2*)e->pcps_b.ptr;
+    double2* F = (double2*)e->pcps_fwd.ptr;
+    double* map = (double*)e->pcps_map.ptr;
+    Best* parts = (Best*)e->pcps_part.ptr;
+    for (int m = 0; m < M; ++m) {
+        PassArgs f = {};
+        f.tw = (const double2*)e->pcps_tw.ptr;
+        f.N = T;
+        f.ring = e->iq;
+        f.capacity = e->iq_capacity;
+        f.first_sample = c.start + (int64_t)m * N;
+        f.fs = p.fs;
+        f.if_hz = c.if_hz;
+        f.bin_start = p.bin_start;
+        f.bin_delta = p.bin_delta;
+        run_fft<false, LOAD_IQ_MIX, STORE_PLAIN, FMT>(e, p.xf, f, nbins, A, B, F + (size_t)m * nbins * T, "coherent_fwd_fft", c.blu);
+    }
+    const int chunks = sdr::coherent_chunk_count(k.cap, n_prn, nbins);
+    for (int i = 0; i < chunks; ++i) {
+        const sdr::CohChunk ch = sdr::coherent_chunk(k.cap, n_prn, nbins, i);
+        const int units = ch.units();
+        for (int m = 0; m < M; ++m) {
+            PassArgs q = {};
+            q.tw = (const double2*)e->pcps_tw.ptr;
+            q.N = T;
+            q.in = F + ((size_t)m * nbins + ch.bin0) * T;
+            q.code_spec = (const double2*)e->pcps_code.ptr + (size_t)ch.prn0 * T;
+            q.nbins = ch.bins;
+            q.scale = 1.0 / (double)T;
+            q.cols = N;
+            q.csum = k.scr + (size_t)m * units * T;
+            q.first_block = 1;
+            run_fft<true, LOAD_MUL_CODE, STORE_CPLX_ACC, SDR_FMT_CF64>(e, p.xf, q, units, A, B, nullptr, "coherent_inv_fft", c.blu);
+        }
+        if (int rc = sdr_coh_combine(e, g, ch, k.scr, map)) return rc;
+        {
+            ProfScope ps(e, "coherent_peak");
+            hipLaunchKernelGGL(argmax_part_kernel, dim3(kPeakParts, ch.prns), dim3(kThreads), 0, e->stream,
+                               map + ((size_t)ch.prn0 * nbins + ch.bin0) * N, (long long)ch.bins * N, parts);
+            if (int rc = sdr_coh_keep(e, g, ch, k.scr, parts, k.best, k.keep)) return rc;
+        }
+    }
+    {
+        ProfScope ps(e, "coherent_peak");
+        hipLaunchKernelGGL(argmax_part_kernel, dim3(kPeakParts, n_prn), dim3(kThreads), 0, e->stream, map, (long long)nbins * N, parts);
+        hipLaunchKernelGGL(peak_finish_kernel, dim3(n_prn), dim3(kThreads), 0, e->stream, map, nbins, N, p.spc, parts, c.res_bin,
+                           c.res_code, c.res_ratio);
+    }
+    SDR_HIP(hipGetLastError());
+    return sdr_coh_pick(e, g, n_prn, k.keep, map, c.res_bin, c.res_code, c.res_ratio, k.results, k.power);
+}
+
 // The tables a plan's transforms read, made when the code length changes: the twiddles, and for a chirp-z length the chirp,
 // the length-M twiddles and the spectra of both kernels (*blu_out: the chirp-z plan, filled where p.M is set).
 int prepare_tables(sdr_engine* e, const PcpsPlan& p, BluPlan* blu_out) {
@@ -776,6 +850,90 @@ int sdr_acq_deep_detect(sdr_engine* e, const int32_t* code_slots, int n_prn, int
                         double* corr_map) {
     if (!det) return sdr_fail(SDR_ERR_INVALID, "NULL detection settings");
     return acq_deep_impl(e, code_slots, n_prn, start_sample, cfg, results, corr_map, det, peaks, noise);
+}
+
+int sdr_pcps_coherent(sdr_engine* e, const sdr_coh_cfg* cfg, const int32_t* code_slots, const int32_t* sec_rows, int n_prn,
+                      const int8_t* sec_codes, int n_sec, int64_t start_sample, double fs, double if_hz, double doppler_range,
+                      double doppler_step, sdr_coh_result* results, double* corr_map, double* power, int* n_bins_out, int* n_code_out) {
+    if (int rc = sdr_set_device(e)) return rc;
+    sdr::CohRequest rq;
+    rq.acq = sdr_acq_request(e, code_slots, n_prn, start_sample, fs, doppler_range, doppler_step, 1);
+    rq.cfg = cfg, rq.sec_rows = sec_rows, rq.sec_codes = sec_codes, rq.n_sec = n_sec;
+    rq.K = cfg ? sdr_acq_refine_bins(cfg->span_hz, cfg->step_hz) : 0;
+    rq.results = results != nullptr;
+    sdr::CohShape shape;
+    int rc = sdr::coherent_request_check(rq, &shape);
+    const int nbins = shape.acq.grid.nbins;
+    if (n_bins_out && nbins > 0) *n_bins_out = nbins;
+    if (rc) return sdr_fail(rc, "%s", shape.acq.text);
+    const int N = shape.sig.N, T = shape.sig.T, M = cfg->n_periods, Ls = cfg->sec_len, K = rq.K;
+    if (n_code_out) *n_code_out = N;
+    // the zero-padded map route's plan (the transforms, the tables, the code spectra, the peaks); the buffers of this route on top
+    PcpsPlan p = plan_pcps(pcps_switches(e), T, shape.acq.spc, fs, nbins, shape.acq.grid.bin_start, shape.acq.grid.bin_delta, 1, M,
+                           n_prn, true, N, shape.sig.chip_rate);
+    CohCall k;
+    k.cap = sdr::coherent_chunk_units(e->coh_scratch_kb * 1024, M, T);
+    int most = 0;      // units of the largest chunk
+    for (int i = 0, n = sdr::coherent_chunk_count(k.cap, n_prn, nbins); i < n; ++i)
+        most = std::max(most, sdr::coherent_chunk(k.cap, n_prn, nbins, i).units());
+    const size_t in_flight = (size_t)std::max(most, std::max(nbins, n_prn));
+    p.work_bytes = p.tbytes * in_flight;
+    if (p.M) p.blu_work_bytes = (size_t)p.M * sizeof(double2) * std::max<size_t>(2, in_flight);
+    auto round16 = [](size_t n) { return (n + 15) & ~(size_t)15; };
+    const size_t b_sec = round16((size_t)n_sec * Ls), b_rows = round16((size_t)n_prn * sizeof(int32_t));
+    const size_t b_best = (size_t)n_prn * sizeof(Best), b_keep = (size_t)n_prn * M * sizeof(double2);
+    const size_t b_res = (size_t)n_prn * sizeof(sdr_coh_result), b_pow = (size_t)n_prn * Ls * K * sizeof(double);
+    static_assert(sizeof(sdr_coh_result) % 16 == 0, "the power table behind the results stays aligned");
+    const std::pair<DevBuf*, size_t> bufs[] = {{&e->pcps_fwd, std::max(p.fwd_bytes, p.tbytes * (size_t)M * nbins)},
+                                               {&e->pcps_a, p.work_bytes}, {&e->pcps_b, p.work_bytes}, {&e->pcps_code, p.code_bytes},
+                                               {&e->pcps_map, p.map_bytes}, {&e->pcps_part, p.part_bytes}, {&e->pcps_res, p.res_bytes},
+                                               {&e->coh_scr, p.tbytes * (size_t)M * most},
+                                               {&e->coh_ws, b_sec + b_rows + b_best + b_keep + b_res + b_pow}};
+    for (const auto& b : bufs)
+        if ((rc = sdr_devbuf_reserve(e, b.first, b.second))) return rc;
+    BluPlan blu;
+    if ((rc = prepare_tables(e, p, &blu))) return rc;
+    if ((rc = sdr_pinned_reserve(e, &e->ctx0, (size_t)n_prn * sizeof(int32_t)))) return rc;
+    memcpy(e->ctx0.pinned, code_slots, (size_t)n_prn * sizeof(int32_t));
+    // the overlay rows and every PRN's row number, in the engine's own block (the source of the upload outlives the call)
+    e->coh_host.resize(b_sec + b_rows);
+    memcpy(e->coh_host.data(), sec_codes, (size_t)n_sec * Ls);
+    memcpy(e->coh_host.data() + b_sec, sec_rows, (size_t)n_prn * sizeof(int32_t));
+    char* ws = (char*)e->coh_ws.ptr;
+    SDR_HIP(hipMemcpyAsync(ws, e->coh_host.data(), b_sec + b_rows, hipMemcpyHostToDevice, e->stream));
+
+    CohGeom g;
+    g.N = N, g.T = T, g.M = M, g.Ls = Ls, g.K = K, g.mode = cfg->mode, g.nbins = nbins;
+    g.fs = fs, g.if_hz = if_hz, g.bin_start = p.bin_start, g.bin_delta = p.bin_delta, g.step_hz = cfg->step_hz;
+    g.sec = (const int8_t*)ws, g.sec_rows = (const int32_t*)(ws + b_sec);
+    k.scr = (double2*)e->coh_scr.ptr;
+    k.best = ws + b_sec + b_rows;
+    k.keep = ws + b_sec + b_rows + b_best;
+    k.results = (sdr_coh_result*)(ws + b_sec + b_rows + b_best + b_keep);
+    k.power = (double*)(ws + b_sec + b_rows + b_best + b_keep + b_res);
+    PcpsCall c;
+    c.start = start_sample;
+    c.if_hz = if_hz;
+    c.slots = code_slots;
+    c.slots_pinned = (const int32_t*)e->ctx0.pinned;
+    const ResultBlock dev = result_block(n_prn, false, true, false, e->pcps_res.ptr);
+    c.d_slots = dev.slots;
+    c.res_bin = dev.bin, c.res_code = dev.code, c.res_ratio = dev.ratio;
+    c.blu = p.M ? &blu : nullptr;
+    {
+        ProfScope whole(e, "call_pcps_coherent");
+        rc = sdr::with_fmt(e->iq_fmt, [&](auto fmt) { return run_coherent<decltype(fmt)::value>(e, p, c, g, k); });
+    }
+    if (rc) {
+        e->pcps_spec_key.clear();      // (a search that stopped half way: what the code-spectra buffer holds is unknown)
+        return rc;
+    }
+    SDR_HIP(hipMemcpyAsync(results, k.results, b_res, hipMemcpyDeviceToHost, e->stream));
+    if (power) SDR_HIP(hipMemcpyAsync(power, k.power, b_pow, hipMemcpyDeviceToHost, e->stream));
+    if (corr_map)
+        SDR_HIP(hipMemcpyAsync(corr_map, e->pcps_map.ptr, (size_t)n_prn * nbins * N * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    SDR_HIP(hipStreamSynchronize(e->stream));
+    return SDR_OK;
 }
 
 }  // extern "C"

@@ -4,6 +4,7 @@
 // stand-alone check tests/csrc/secondary_request_check.hip (`make check-sanitize`, tests/test_secondary.py).
 //   refine_admit_item         one item of either call: slot staged, rates finite, window inside the ring, the code period
 //                             inside the staged row and the LDS -> what the kernels need of it (RefineItemDev)
+//   secondary_chips_check     the rows of secondary codes hold +1 and -1 alone (shared with coherent_request.h)
 //   secondary_request_check   the whole of a sdr_acq_secondary call, items included
 #pragma once
 
@@ -84,6 +85,17 @@ inline int refine_admit_item(const RefineRing& g, int i, int32_t code_slot, int6
     return SDR_OK;
 }
 
+// Every chip of the secondary rows [n_sec][sec_len] is +1 or -1 (sdr_acq_secondary, sdr_pcps_coherent).
+inline int secondary_chips_check(const int8_t* sec_codes, int n_sec, int sec_len, char* text, size_t text_len) {
+    for (int64_t q = 0; q < (int64_t)n_sec * sec_len; ++q)
+        if (sec_codes[q] != 1 && sec_codes[q] != -1) {
+            snprintf(text, text_len, "secondary code %d, chip %d: %d is neither +1 nor -1", (int)(q / sec_len), (int)(q % sec_len),
+                     (int)sec_codes[q]);
+            return SDR_ERR_INVALID;
+        }
+    return SDR_OK;
+}
+
 struct SecRequest {
     // of the engine
     bool ring = false, slots_allocated = false;
@@ -138,12 +150,7 @@ inline int secondary_request_check(const SecRequest& r, SecShape* s, RefineItemD
     }
     if (r.mode != SDR_SEC_PILOT && r.mode != SDR_SEC_DATA) return fail(SDR_ERR_INVALID, "mode is neither SDR_SEC_PILOT nor SDR_SEC_DATA");
     if (r.K <= 0 || !std::isfinite(r.span_hz) || !std::isfinite(r.step_hz)) return fail(SDR_ERR_INVALID, "bad fine frequency grid");
-    for (int64_t q = 0; q < (int64_t)r.n_sec * r.sec_len; ++q)
-        if (r.sec_codes[q] != 1 && r.sec_codes[q] != -1) {
-            snprintf(s->text, sizeof s->text, "secondary code %d, chip %d: %d is neither +1 nor -1", (int)(q / r.sec_len),
-                     (int)(q % r.sec_len), (int)r.sec_codes[q]);
-            return SDR_ERR_INVALID;
-        }
+    if (int rc = secondary_chips_check(r.sec_codes, r.n_sec, r.sec_len, s->text, sizeof s->text)) return rc;
     if (M * S > kSecMaxProducts) {
         snprintf(s->text, sizeof s->text, "%d periods of %d segments (at most %d segments in all)", M, S, kSecMaxProducts);
         return SDR_ERR_UNSUPPORTED;

@@ -11,7 +11,10 @@ unbroken code period -- and keeps those lags alone.  A BOC(1,1) signal is search
 twice the chip rate, with `excl_samples` covering the side peaks.
 
 Behind that search, `SecondarySync` (sdr_acq_secondary) finds where the secondary (overlay) code of such a signal stands and
-its carrier to a fine grid's step; NH10 and NH20 are the two Neuman-Hofman codes (L5-I, L5-Q), the only secondary tables here."""
+its carrier to a fine grid's step; NH10 and NH20 are the two Neuman-Hofman codes (L5-I, L5-Q), the only secondary tables here.
+
+`CoherentSearch` (sdr_pcps_coherent, statement `pcps_coherent_statement`) is both steps at once for a weak signal: the padded
+search's per-period correlations added coherently under every overlay phase and every frequency of a fine grid."""
 from __future__ import annotations
 
 import numpy as np
@@ -160,3 +163,123 @@ def SecondarySync(rfData, samplingFrequency, code, chipRate, secondary, coarseFr
     res, power, _ = eng.acq_secondary(make_secondary_items(3, 0, 0, coarseFrequency, chipRate), np.asarray(secondary),
                                       samplingFrequency, nbPeriods, nbSegments, frequencySpan, frequencyStep, mode, want_tables=True)
     return float(res["fine_hz"][0]), int(res["sec_phase"][0]), float(res["power"][0] / res["power_other"][0]), power[0]
+
+
+def fine_grid(span_hz, step_hz):
+    """d_k = (k - (K-1)/2) * step_hz, K = 2*floor(span_hz/step_hz) + 1 (sdr_acq_refine_bins)."""
+    k = 2 * int(np.floor(span_hz / step_hz)) + 1
+    return (np.arange(k) - (k - 1) // 2) * step_hz
+
+
+def _coh_rotation(freq, m, n_code, fs):
+    """g = exp(-2j*pi*freq*(m*N)/fs), from the phase in cycles less its nearest whole number."""
+    ph = freq * ((m * n_code) / fs)
+    return np.exp(-1j * (2 * np.pi * (ph - np.rint(ph))))
+
+
+def coherent_cell(col, sec, freqs, n_code, fs, mode=0):
+    """P[Ls][K] and X[Ls][K] of one cell from its M per-period correlations `col`, m ascending (mode 1: X = 0)."""
+    sec = np.asarray(sec, dtype=np.float64)
+    n_per, n_sec = len(col), len(sec)
+    power = np.zeros((n_sec, len(freqs)))
+    prompt = np.zeros((n_sec, len(freqs)), complex)
+    for k, f in enumerate(freqs):
+        z = [col[m] * _coh_rotation(f, m, n_code, fs) for m in range(n_per)]
+        for h in range(n_sec):
+            acc, groups = 0j, 0.0
+            for m in range(n_per):
+                acc = acc + sec[(h + m) % n_sec] * z[m]
+                if mode == 1 and (h + m) % n_sec == n_sec - 1:
+                    groups, acc = groups + abs(acc) ** 2, 0j
+            power[h, k] = groups + abs(acc) ** 2
+            prompt[h, k] = acc if mode == 0 else 0j
+    return power, prompt
+
+
+def pcps_coherent_statement(x, codes, sec_codes, sec_rows, fs, if_hz, doppler_range, doppler_step, chip_rate_hz, n_periods,
+                            span_hz=125.0, step_hz=25.0, mode=0, excl_samples=0, start_sample=0):
+    """sdr_pcps_coherent in NumPy.  x: the ring's samples (complex, flat; the window wraps at its end), codes: [n_prn][L],
+    sec_codes: [n_sec][Ls] of +-1, sec_rows: the row of every PRN.
+    -> (results: COH_RESULT_DTYPE records, R[n_prn][bins][N], P[n_prn][Ls][K] at each PRN's peak cell)."""
+    from .._lib import COH_RESULT_DTYPE     # (a record layout: no library is loaded)
+    x = np.squeeze(np.asarray(x, dtype=np.complex128))
+    codes = np.atleast_2d(np.asarray(codes))
+    sec_codes = np.atleast_2d(np.asarray(sec_codes))
+    n_prn = codes.shape[0]
+    sec_rows = np.broadcast_to(np.asarray(sec_rows, dtype=int), (n_prn,))
+    n_per, n_sec = int(n_periods), sec_codes.shape[1]
+    n_code = samples_per_code(fs, codes.shape[1], chip_rate_hz)
+    t_len = 2 * n_code
+    bins = np.arange(-doppler_range, doppler_range + 1, doppler_step)
+    fine = fine_grid(span_hz, step_hz)
+    spc = int(excl_samples) if excl_samples else int(np.rint(fs / chip_rate_hz))
+    phase_points = np.array(range(t_len)) * 2 * np.pi / fs
+    blocks = [x[(start_sample + m * n_code + np.arange(t_len)) % x.size] for m in range(n_per)]
+    code_fft = [np.conj(np.fft.fft(np.r_[replica(c, fs, chip_rate_hz, n_code), np.zeros(n_code)])) for c in codes]
+    spectra = [[np.fft.fft(np.exp(-1j * (if_hz - b) * phase_points) * blk) for blk in blocks] for b in bins]
+    results = np.zeros(n_prn, dtype=COH_RESULT_DTYPE)
+    rmap = np.zeros((n_prn, len(bins), n_code))
+    tables = np.zeros((n_prn, n_sec, len(fine)))
+    for p in range(n_prn):
+        sec = sec_codes[sec_rows[p]].astype(np.float64)
+        idx = (np.arange(n_sec)[:, None] + np.arange(n_per)[None, :])          # h + m
+        signs = sec[idx % n_sec]                                                # w_h(m)
+        corr = []
+        for row, b in enumerate(bins):
+            c = np.array([np.fft.ifft(spec * code_fft[p])[:n_code] for spec in spectra[row]])      # C_m[tau]
+            corr.append(c)
+            best = np.zeros(n_code)
+            for d in fine:
+                z = c * _coh_rotation((if_hz - b) + d, np.arange(n_per), n_code, fs)[:, None]
+                if mode == 0:
+                    pw = np.abs(signs @ z) ** 2
+                else:
+                    pw = np.zeros((n_sec, n_code))
+                    for h in range(n_sec):
+                        grp = idx[h] // n_sec
+                        for gg in np.unique(grp):
+                            pw[h] += np.abs(signs[h, grp == gg] @ z[grp == gg]) ** 2
+                best = np.fmax(best, np.fmax.reduce(pw, axis=0))                # (a NaN never wins)
+            rmap[p, row] = np.sqrt(best)
+        top, ratio = two_peak_compare(rmap[p], n_code, spc)
+        b_top = bins[top[0]]
+        power, prompt = coherent_cell(corr[top[0]][:, top[1]], sec, [(if_hz - b_top) + d for d in fine], n_code, fs, mode)
+        h, k = np.unravel_index(power.argmax(), power.shape)                    # first maximum in row-major order
+        tables[p] = power
+        r = results[p]
+        r["carrier_hz"] = (if_hz - b_top) + fine[k]
+        r["peak"], r["peak_ratio"] = rmap[p, top[0], top[1]], ratio
+        r["power"], r["power_other"] = power[h, k], np.delete(power, h, axis=0).max()
+        r["prompt_re"], r["prompt_im"] = prompt[h, k].real, prompt[h, k].imag
+        r["peak_code"], r["peak_bin"], r["fine_idx"], r["sec_phase"] = top[1], top[0], k, h
+    return results, rmap, tables
+
+
+def CoherentSearch(rfData, interFrequency, samplingFrequency, code, chipRate, secondary, dopplerRange, dopplerStep, nbPeriods,
+                   frequencySpan=125.0, frequencyStep=25.0, mode=0, exclSamples=0):
+    """Coherent search of one code (its chips, at `chipRate`) under its `secondary` (overlay) code over `rfData`, on the GPU, in
+    the shape of PCPSSignal / SecondarySync (the definition is sdr_pcps_coherent's in include/sydr_amd.h): `nbPeriods` code
+    periods are added coherently under every overlay phase and every frequency of the fine grid; `rfData` holds
+    `nbPeriods` + 1 periods.  mode 0: a pilot, 1: a data symbol as long as the overlay code.
+    -> (map R[bins][N], [bin, code], peak ratio, carrierFrequency, secPhase, powerRatio)."""
+    from ..engine import FMT_CF64
+    from ..runtime import get_engine
+    rf = np.squeeze(np.asarray(rfData, dtype=np.complex128))
+    chips = np.asarray(code)
+    need = samples_per_code(samplingFrequency, len(chips), chipRate) * (int(nbPeriods) + 1)
+    if rf.size < need:
+        raise ValueError(f"CoherentSearch needs {need} samples, got {rf.size}")
+    eng = get_engine()
+    if getattr(eng, "n_slots", 0) < 4 or getattr(eng, "max_chips", 0) < len(chips):
+        eng.code_slots(4, max(4092, len(chips)))
+    eng.set_code(3, chips.astype(np.int8))
+    cap = (need + 7) // 8 * 8
+    if eng.iq_fmt != FMT_CF64 or eng.iq_capacity < cap:
+        eng.iq_alloc(cap, FMT_CF64)
+    eng.iq_upload(rf[:need], 0)
+    res, cmap, _ = eng.pcps_coherent([3], 0, np.asarray(secondary), 0, samplingFrequency, interFrequency, dopplerRange, dopplerStep,
+                                     chipRate, nbPeriods, frequencySpan, frequencyStep, mode, exclSamples, want_map=True,
+                                     n_chips=len(chips))
+    r = res[0]
+    return (cmap[0], [int(r["peak_bin"]), int(r["peak_code"])], float(r["peak_ratio"]), float(r["carrier_hz"]),
+            int(r["sec_phase"]), float(r["power"] / r["power_other"]))

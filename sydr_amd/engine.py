@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (EPL_ITEM_DTYPE, FMT_CF32, FMT_CF64, FMT_CI16, FMT_CI8, LOOP_CFG_DTYPE, REFINE_ITEM_DTYPE,
+from ._lib import (COH_RESULT_DTYPE, EPL_ITEM_DTYPE, FMT_CF32, FMT_CF64, FMT_CI16, FMT_CI8, LOOP_CFG_DTYPE, REFINE_ITEM_DTYPE,
                    REFINE_RESULT_DTYPE, SEC_ITEM_DTYPE, SEC_RESULT_DTYPE, TRACK_EPOCH_DTYPE, TRACK_STATE_DTYPE, LoopCfg, SynthSat,
                    TrackState, check, ptr)
 
@@ -881,6 +881,48 @@ class Engine:
                                           int(n_segments), float(span_hz), float(step_hz), int(mode), ptr(res),
                                           ptr(power) if want_tables else None, ptr(z) if want_tables else None))
         return (res, power, z) if want_tables else res
+
+    def pcps_coherent(self, code_slots, sec_rows, sec_codes, start_sample, fs, if_hz, doppler_range, doppler_step, chip_rate_hz,
+                      n_periods, span_hz=125.0, step_hz=25.0, mode=0, excl_samples=0, want_map=False, want_power=False,
+                      n_chips=None, reserved=(0, 0)):
+        """The coherent search under secondary-code hypotheses (sdr_pcps_coherent; the NumPy statement is
+        dsp.signalsearch.pcps_coherent_statement): the slots' codes, all of one length, at `chip_rate_hz`, each under its row
+        `sec_rows[p]` of the +-1 overlay codes `sec_codes` (a single code may be given as one row); `n_periods` code periods
+        are added coherently under every overlay phase and every frequency of the fine grid (span_hz, step_hz).  mode 0: a
+        pilot, 1: a data symbol as long as the overlay code.  `n_chips`: the slots' code length where a map is wanted (None:
+        read back from the first slot).
+        -> (results: COH_RESULT_DTYPE records -- carrier_hz, peak, peak_ratio, power, power_other, prompt_re, prompt_im,
+        peak_code, peak_bin, fine_idx, sec_phase --, R[n_prn][bins][N] or None, power[n_prn][sec_len][K] or None)."""
+        slots = np.ascontiguousarray(code_slots, dtype=np.int32)
+        n = len(slots)
+        rows = np.ascontiguousarray(np.broadcast_to(np.asarray(sec_rows, dtype=np.int32), (n,)))
+        sec = np.asarray(sec_codes)
+        if sec.ndim != 2:
+            sec = sec.reshape(1, -1)
+        if not np.array_equal(sec, sec.astype(np.int8)):
+            raise ValueError("secondary chips are +1 or -1")
+        sec = np.ascontiguousarray(sec, dtype=np.int8)
+        cfg = _lib.CohCfg(float(chip_rate_hz), float(span_hz), float(step_hz), int(n_periods), sec.shape[1], int(mode),
+                          int(excl_samples), (C.c_int32 * 2)(int(reserved[0]), int(reserved[1])))
+        nbins = self._lib.sdr_pcps_bins(float(doppler_range), float(doppler_step))
+        cmap = power = None
+        if want_map:
+            if n_chips is None:
+                n_chips = len(self.read_code(int(slots[0]))) if n else 0
+            ratio = float(fs) * int(n_chips) / float(chip_rate_hz) if chip_rate_hz and chip_rate_hz > 0 else 0.0
+            n_code = int(np.rint(ratio)) if np.isfinite(ratio) and 0 <= ratio <= 1 << 24 else 0
+            cmap = np.empty((n, max(0, nbins), n_code), dtype=np.float64)
+        if want_power:
+            power = np.empty((n, sec.shape[1], max(0, self.acq_refine_bins(span_hz, step_hz))), dtype=np.float64)
+        res = np.zeros(n, dtype=COH_RESULT_DTYPE)
+        nb, nc = C.c_int(0), C.c_int(0)
+        check(self._lib.sdr_pcps_coherent(self._h, C.byref(cfg), ptr(slots), ptr(rows), n, ptr(sec), sec.shape[0], int(start_sample),
+                                          float(fs), float(if_hz), float(doppler_range), float(doppler_step), ptr(res),
+                                          ptr(cmap) if want_map else None, ptr(power) if want_power else None, C.byref(nb),
+                                          C.byref(nc)))
+        if want_map and cmap.shape[2] != nc.value:
+            raise ValueError(f"map of {cmap.shape[2]} columns allocated, the search wrote {nc.value}")
+        return res, cmap, power
 
     def acq_deep(self, code_slots, start_sample, fs, if_hz, doppler_range, doppler_step, coh, noncoh, groups=1,
                  carrier_rf_hz=0.0, want_map=False):
