@@ -132,9 +132,17 @@ int sdr_iq_download(sdr_engine* e, void* iq, int64_t n_samples, int64_t ring_off
 
 /* Synthetic multi-satellite IQ written straight into the ring:
  *   x[n] = sum_s amp * c_s(chip_s(n)) * d_s(n) * exp(j*2*pi*(doppler_s*n/fs + phase_s)) + CN(0, sigma^2)
- * rounded and clipped to the ring's integer format.  chip_s(n) =
- * code_phase_s + n * 1.023e6*(1+doppler_s/1575.42e6)/fs (chips, mod 1023); d_s is a
- * seeded +-1 sequence changing every 20 code periods.  Deterministic in (seed, n). */
+ * for ring sample numbers n = first_sample .. first_sample + n_samples - 1, each written to slot n mod capacity
+ * (n_samples <= capacity; first_sample >= 0 may lie beyond the capacity).  One float32 value per component:
+ * integer rings hold it rounded to even and clipped to +-127 / +-32767 (never -128 / -32768), float rings
+ * hold the float32 value (a cf64 ring the same value widened).  chip_s(n) =
+ * code_phase_s + n * 1.023e6*(1+doppler_s/1575.42e6)/fs (chips, modulo the code's length L: 1023 for a GPS
+ * PRN, the staged length of a code slot; code_phase_s may be negative); with SDR_SYNTH_BOC11 the sign flips
+ * in the second half of every chip.  d_s is a seeded +-1 sequence that changes every 20 code periods when
+ * L == 1023 and every code period otherwise, keyed by the PRN number, or by slot + 1000 for a staged code
+ * (so PRN p and slot p carry different data).  The noise is Box-Muller from 24-bit uniforms: its radius stops
+ * at sqrt(2 ln 2^24) = 5.77 sigma.  Deterministic in (seed, n): a stream written in several calls is the
+ * stream written in one.  The statement in NumPy: tests/synth_cases.py; docs/notes/synth.md. */
 #define SDR_SYNTH_CODE_SLOT 1 /* `prn` is a staged code slot (any length), not a GPS PRN number      */
 #define SDR_SYNTH_BOC11 2     /* multiply by the BOC(1,1) square sub-carrier (flip every half chip)  */
 typedef struct sdr_synth_sat {

@@ -98,6 +98,10 @@ def make_codes():
         ups[f"upsample_idx_{int(fs)}"] = ref_sig.UpsampleCode(ramp, fs).astype(np.int16)
         assert len(ups[f"upsample_idx_{int(fs)}"]) == n
     save("g1_codes.npz", prns=np.array(prns), chips=chips, first10=octal, **ups)
+    # every PRN of the delay table, one bit per chip (chip +1 -> 1), 128 bytes a row: np.unpackbits(packed, axis=1)[:, :1023]
+    every = np.arange(1, 211)
+    bits = np.stack([ref_sig.GenerateGPSGoldCode(int(p)) > 0 for p in every])
+    save("g1_codes_all.npz", prns=every, packed=np.packbits(bits, axis=1))
 
 
 # ---------------------------------------------------------------------------------------------- G3

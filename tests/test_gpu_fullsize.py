@@ -9,6 +9,7 @@ import pytest
 
 from conftest import REPO
 from oracle import sydr_oracle as orc
+from synth_cases import mix64 as _mix64      # (mix64 of the device generator: the synthesiser's statement)
 from sydr_amd.channel.manager import shard_channels
 from sydr_amd.engine import FMT_CI8, make_items
 
@@ -132,14 +133,6 @@ def test_config5_256_channels_sharded_32_per_gpu(engine):
             mine = shard_channels(n_ch, rank, 8)
             got = engine.epl_batch(np.ascontiguousarray(grid[:, mine]).reshape(-1), spacing, fs).reshape(n_ep, len(mine), 10)
             assert np.array_equal(got, whole[:, mine]), rank
-
-
-def _mix64(z):
-    """mix64 of the device generator (sydr_amd/csrc/codes.hip), vectorised over uint64 arrays."""
-    z = (z + np.uint64(0x9E3779B97F4A7C15)).astype(np.uint64)
-    z = ((z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)).astype(np.uint64)
-    z = ((z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)).astype(np.uint64)
-    return z ^ (z >> np.uint64(31))
 
 
 def test_config3_closed_loop_sixty_seconds_recovers_every_data_bit(engine):

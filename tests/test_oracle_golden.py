@@ -20,6 +20,19 @@ def test_gold_codes_match_reference():
         assert orc.first_10_chips_octal(int(prn)) == int(octal)
 
 
+def test_every_gold_code_matches_reference():
+    """All 210 PRNs of the G2 delay table (g1_codes.npz holds 42 of them), one bit per chip."""
+    g = load_golden("g1_codes_all.npz")
+    assert list(g["prns"]) == list(range(1, 211)) and g["packed"].shape == (210, 128)
+    chips = np.unpackbits(g["packed"], axis=1)[:, :1023].astype(np.int8) * 2 - 1
+    old = load_golden("g1_codes.npz")
+    for prn, row in zip(old["prns"], old["chips"]):
+        assert np.array_equal(chips[int(prn) - 1], row), f"PRN {prn}"
+    for prn in range(1, 211):
+        assert np.array_equal(orc.gold_code(prn).astype(np.int8), chips[prn - 1]), f"PRN {prn}"
+    assert len({row.tobytes() for row in chips}) == 209          # (PRN 34 and 37 share a delay; every other code is its own)
+
+
 def test_first_ten_chips_icd_table():
     # IS-GPS-200 table, PRN 1..10 (also printed by the reference's ca.py:137-149)
     expect = [0o1440, 0o1620, 0o1710, 0o1744, 0o1133, 0o1455, 0o1131, 0o1454, 0o1626, 0o1504]
