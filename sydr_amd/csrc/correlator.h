@@ -887,7 +887,10 @@ __device__ __forceinline__ void scatter_steps(double (&v)[N > 0 ? N : 1], int (&
             const double keep = upper ? v[2 * i + 1] : v[2 * i];
             const double give = upper ? v[2 * i] : v[2 * i + 1];
             nv[i] = keep + lane_xor_f64<D>(give);
-            ns[i] = upper ? slot[2 * i + 1] : slot[2 * i];
+            // (the slots as a blend of two VALUES under the lane's bit: written as a choice between two elements, the choice is
+            // made between their addresses and the little array lands in scratch memory, two stores and two loads per epoch)
+            const int s_lo = slot[2 * i], s_hi = slot[2 * i + 1];
+            ns[i] = s_lo ^ ((s_lo ^ s_hi) & -(int)upper);
         }
         if constexpr (N & 1) {
             nv[M - 1] = v[N - 1] + lane_xor_f64<D>(v[N - 1]);

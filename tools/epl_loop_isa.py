@@ -103,23 +103,28 @@ def fall_through(ins, at, head, back):
     return path
 
 
-def report(asm_lines, args, histogram):
-    body, info = kernel_body(asm_lines, args)
-    ins = parse(body)
+def pair_loops(ins, share=0.85):
+    """The copies of the round-pair loop, in the order of the text: [(VALU on the fall-through path, header index, back-branch
+    index, path)] of every innermost loop with at least `share` of the largest one's vector instructions."""
     at, found = loops(ins)
     cands = []
     for head, back in found:
         if any(head < h and b < back for h, b in found if (h, b) != (head, back)):
             continue                                   # not innermost
         path = fall_through(ins, at, head, back)
-        cands.append((sum(is_valu(op) for op, _ in path), head, path))
+        cands.append((sum(is_valu(op) for op, _ in path), head, back, path))
     if not cands:
         raise SystemExit("no loop found")
     # the pair loop comes twice where the last rounds are peeled off it: first the plain one (all but the last two or three
     # rounds of an epoch), then the one that can clamp (run once or twice per epoch) -- the first is the one that counts
-    top = max(nv for nv, _, _ in cands)
-    big = sorted((c for c in cands if c[0] >= 0.85 * top), key=lambda c: c[1])
-    nv, head, path = big[0]
+    top = max(c[0] for c in cands)
+    return sorted((c for c in cands if c[0] >= share * top), key=lambda c: c[1])
+
+
+def report(asm_lines, args, histogram):
+    body, info = kernel_body(asm_lines, args)
+    ins = parse(body)
+    nv, head, _, path = pair_loops(ins)[0]
     ops = collections.Counter(op for op, _ in path)
     lanes = sum(n for op, n in ops.items() if op.startswith(("v_readlane", "v_writelane")))
     print(f"epl_kernel<{args}>  loop {ins[head][0]}")
