@@ -217,14 +217,15 @@ struct sdr_epl_plan {
 // The per-epoch setups of the straight-line kernels (ChipSetup / ChipNSetup: tap constants, epoch geometry, ring position,
 // carrier rotations), made when a plan is created: one THREAD per item -- what every wave of an epoch would otherwise
 // repeat in all of its 64 lanes -- with the same functions the run-time-position kernels call per wave.  1.92 M items
-// (60 s x 32 channels) take ~0.1 ms of one launch.
+// (60 s x 32 channels) take ~0.22 ms of one launch on an idle device (DESIGN.md's kernel table).
 template <int NT, int KM, int KS, int KI>
 __global__ __launch_bounds__(64) void chip_setup_kernel(const sdr_epl_item* __restrict__ items, int n_items,
                                                         const double* __restrict__ spacing, double fs, int64_t capacity,
                                                         sdr::ChipSetup<NT>* __restrict__ out) {
-    // One wave per 64 items.  A thread's setup is 480 / 560 bytes: stored where it belongs by the thread itself, a wave's store
-    // instruction touches 64 places that far apart (1.4 ms for the 0.92 GB of a 60 s x 32 channel plan); through LDS the
-    // wave writes its 64 setups -- contiguous in memory -- sixteen bytes per lane, a kilobyte per instruction (round 6).
+    // One wave per 64 items.  A thread's setup is 784 / 864 bytes (three / five taps): stored where it belongs by the thread
+    // itself, a wave's store instruction touches 64 places that far apart (1.4 ms for a 60 s x 32 channel plan, when a setup
+    // had 480 bytes); through LDS the wave writes its 64 setups -- contiguous in memory -- sixteen bytes per lane, a kilobyte
+    // per instruction (round 6).
     constexpr int kWords = (int)(sizeof(sdr::ChipSetup<NT>) / 16);
     static_assert(sizeof(sdr::ChipSetup<NT>) % 16 == 0, "setups are copied out in 16-byte granules");
     __shared__ uint4 stage[64 * kWords];
@@ -366,73 +367,71 @@ __device__ __forceinline__ unsigned long long dbits(double x) { return (unsigned
 // Two rule sets at once (the list as it is and its half-chip view): one upload, one launch, one read-back.  A thread walks
 // the list with the grid's stride and keeps its own statistics; a wave reduces them and adds them to the list's with ONE set
 // of atomics -- at 1.92 M items a set per 64 items was 420 k atomics on seven addresses, 2.2 ms of a 4.5 ms plan (round 6).
+//
+// One rule set per workgroup (blockIdx.y), not both per thread: a plan is made while the segment before it is correlated, by a
+// launch that keeps three waves of 152 registers on every SIMD.  56 registers are what those leave of a SIMD's 512; with the 80
+// a thread took for both rule sets, no wave of this kernel could be placed before that launch had drained, and the check of a
+// segment's 160 000 items ended with it, 0.92 ms after it began; with 54 (-Rpass-analysis=kernel-resource-usage) it takes
+// 0.087 ms beside that launch (kernel traces: profiles/epl_plan_stream_ab_same_box.txt; docs/notes/K1.md, "A plan beside a
+// running launch").  The items are read twice, out of the L2 the second time.
 __global__ __launch_bounds__(256) void validate_items_kernel(const sdr_epl_item* __restrict__ items, int n_items, ItemRules r1,
                                                              ItemRules r2, const int32_t* __restrict__ code_len,
                                                              ItemStats* __restrict__ out) {
     const int stride = (int)(gridDim.x * 256);
+    const int v = blockIdx.y;
+    const ItemRules& r = v ? r2 : r1;
     // (a lane without an item, or with a bad one, carries the neutral element of every reduction: all 64 lanes take part)
-    int ml[2] = {0, 0}, mlo[2] = {0x7fffffff, 0x7fffffff}, mhi[2] = {0, 0}, a12[2] = {1, 1}, fb[2] = {0x7fffffff, 0x7fffffff};
-    unsigned long long mx[2] = {0ull, 0ull}, mn[2] = {~0ull, ~0ull};
+    int ml = 0, mlo = 0x7fffffff, mhi = 0, a12 = 1, fb = 0x7fffffff;
+    unsigned long long mx = 0ull, mn = ~0ull;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n_items; i += stride) {
         const sdr_epl_item it = items[i];
-#pragma unroll
-        for (int v = 0; v < 2; ++v) {
-            const ItemRules& r = v ? r2 : r1;
-            int maxlen = 0, m_chip = 0;
-            double step = 0.0, lo, hi;
-            bool split = true;
-            const int bad = check_item(it, r, code_len, maxlen, step, m_chip, split, lo, hi);
-            if (bad) {
-                fb[v] = min(fb[v], i);
-            } else {
-                ml[v] = max(ml[v], maxlen);
-                const unsigned long long sb = dbits(step);
-                mx[v] = sb > mx[v] ? sb : mx[v];
-                mn[v] = sb < mn[v] ? sb : mn[v];
-                mlo[v] = min(mlo[v], m_chip);
-                mhi[v] = max(mhi[v], m_chip);
-                a12[v] &= split ? 1 : 0;
-            }
+        int maxlen = 0, m_chip = 0;
+        double step = 0.0, lo, hi;
+        bool split = true;
+        const int bad = check_item(it, r, code_len, maxlen, step, m_chip, split, lo, hi);
+        if (bad) {
+            fb = min(fb, i);
+        } else {
+            ml = max(ml, maxlen);
+            const unsigned long long sb = dbits(step);
+            mx = sb > mx ? sb : mx;
+            mn = sb < mn ? sb : mn;
+            mlo = min(mlo, m_chip);
+            mhi = max(mhi, m_chip);
+            a12 &= split ? 1 : 0;
         }
     }
 #pragma unroll
-    for (int v = 0; v < 2; ++v) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            ml[v] = max(ml[v], __shfl_xor(ml[v], off, 64));
-            const unsigned long long ox = __shfl_xor(mx[v], off, 64), on = __shfl_xor(mn[v], off, 64);
-            mx[v] = ox > mx[v] ? ox : mx[v];
-            mn[v] = on < mn[v] ? on : mn[v];
-            mlo[v] = min(mlo[v], __shfl_xor(mlo[v], off, 64));
-            mhi[v] = max(mhi[v], __shfl_xor(mhi[v], off, 64));
-            a12[v] &= __shfl_xor(a12[v], off, 64);
-            fb[v] = min(fb[v], __shfl_xor(fb[v], off, 64));
-        }
+    for (int off = 32; off > 0; off >>= 1) {
+        ml = max(ml, __shfl_xor(ml, off, 64));
+        const unsigned long long ox = __shfl_xor(mx, off, 64), on = __shfl_xor(mn, off, 64);
+        mx = ox > mx ? ox : mx;
+        mn = on < mn ? on : mn;
+        mlo = min(mlo, __shfl_xor(mlo, off, 64));
+        mhi = max(mhi, __shfl_xor(mhi, off, 64));
+        a12 &= __shfl_xor(a12, off, 64);
+        fb = min(fb, __shfl_xor(fb, off, 64));
     }
-    // the block's four waves through LDS, then one set of atomics per block and rule set
-    __shared__ int sh_i[4][2][5];
-    __shared__ unsigned long long sh_u[4][2][2];
+    // the block's four waves through LDS, then one set of atomics per block
+    __shared__ int sh_i[4][5];
+    __shared__ unsigned long long sh_u[4][2];
     const int wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int v = 0; v < 2; ++v) {
-            sh_i[wave][v][0] = ml[v], sh_i[wave][v][1] = mlo[v], sh_i[wave][v][2] = mhi[v], sh_i[wave][v][3] = a12[v], sh_i[wave][v][4] = fb[v];
-            sh_u[wave][v][0] = mx[v], sh_u[wave][v][1] = mn[v];
-        }
+        sh_i[wave][0] = ml, sh_i[wave][1] = mlo, sh_i[wave][2] = mhi, sh_i[wave][3] = a12, sh_i[wave][4] = fb;
+        sh_u[wave][0] = mx, sh_u[wave][1] = mn;
     }
     __syncthreads();
-    if (threadIdx.x < 2) {
-        const int v = threadIdx.x;
+    if (threadIdx.x == 0) {
         int b_ml = 0, b_lo = 0x7fffffff, b_hi = 0, b_a12 = 1, b_fb = 0x7fffffff;
         unsigned long long b_mx = 0ull, b_mn = ~0ull;
         for (int w = 0; w < 4; ++w) {
-            b_ml = max(b_ml, sh_i[w][v][0]);
-            b_lo = min(b_lo, sh_i[w][v][1]);
-            b_hi = max(b_hi, sh_i[w][v][2]);
-            b_a12 &= sh_i[w][v][3];
-            b_fb = min(b_fb, sh_i[w][v][4]);
-            b_mx = sh_u[w][v][0] > b_mx ? sh_u[w][v][0] : b_mx;
-            b_mn = sh_u[w][v][1] < b_mn ? sh_u[w][v][1] : b_mn;
+            b_ml = max(b_ml, sh_i[w][0]);
+            b_lo = min(b_lo, sh_i[w][1]);
+            b_hi = max(b_hi, sh_i[w][2]);
+            b_a12 &= sh_i[w][3];
+            b_fb = min(b_fb, sh_i[w][4]);
+            b_mx = sh_u[w][0] > b_mx ? sh_u[w][0] : b_mx;
+            b_mn = sh_u[w][1] < b_mn ? sh_u[w][1] : b_mn;
         }
         ItemStats* o = out + v;
         atomicMax(&o->maxlen, b_ml);
@@ -516,20 +515,24 @@ static int validate_items(sdr_engine* e, const sdr_epl_item* items, int n_items,
     return SDR_OK;
 }
 
+// Page-locked scratch of a long list's plan (StreamCtx::pinned of the engine's stream): the two ItemStats, then the tap
+// spacings, which the copy queued by plan_create_impl reads until the synchronisation that ends the plan's creation.
+constexpr size_t kPlanPinnedBytes = 2 * sizeof(ItemStats) + SDR_MAX_TAPS * sizeof(double);
+
 // The same for a list that is already on the device (long lists: behind their upload).  ok2: the half-chip view's rules
 // were met as well (wide2 then holds its answer).
 static int validate_items_dev(sdr_engine* e, const sdr_epl_item* d_items, const sdr_epl_item* h_items, int n_items,
                               const double* spacing, int n_taps, int* lut_words, int* wide, bool* ok2, int* wide2) {
     const ItemRules r1 = item_rules(e, spacing, n_taps, 1.0), r2 = item_rules(e, spacing, n_taps, 2.0);
     if (int rc = sdr_devbuf_reserve(e, &e->ws_stats, 2 * sizeof(ItemStats))) return rc;
-    if (int rc = sdr_pinned_reserve(e, &e->ctx0, 2 * sizeof(ItemStats))) return rc;
+    if (int rc = sdr_pinned_reserve(e, &e->ctx0, kPlanPinnedBytes)) return rc;
     ItemStats* host = static_cast<ItemStats*>(e->ctx0.pinned);
     for (int v = 0; v < 2; ++v) {
         host[v] = ItemStats{0x7fffffff, 0, 0, 0ull, ~0ull, 0x7fffffff, 0, (v ? r2 : r1).want_s12 ? 1 : 0};
     }
     SDR_HIP(hipMemcpyAsync(e->ws_stats.ptr, host, 2 * sizeof(ItemStats), hipMemcpyHostToDevice, e->stream));
     const unsigned check_blocks = (unsigned)((n_items + 255) / 256) < 2048u ? (unsigned)((n_items + 255) / 256) : 2048u;      // (eight per CU)
-    hipLaunchKernelGGL(validate_items_kernel, dim3(check_blocks), dim3(256), 0, e->stream, d_items, n_items, r1, r2,
+    hipLaunchKernelGGL(validate_items_kernel, dim3(check_blocks, 2), dim3(256), 0, e->stream, d_items, n_items, r1, r2,
                        (const int32_t*)e->code_len, static_cast<ItemStats*>(e->ws_stats.ptr));
     SDR_HIP(hipGetLastError());
     SDR_HIP(hipMemcpyAsync(host, e->ws_stats.ptr, 2 * sizeof(ItemStats), hipMemcpyDeviceToHost, e->stream));
@@ -699,6 +702,7 @@ static int plan_create_impl(sdr_engine* e, const sdr_epl_item* items, const sdr_
             return rc;
         }
     }
+    const double t_checked = now();
     p->lut_words = lut_words;
     p->wide = wide;
     p->doubled = doubled;
@@ -733,8 +737,17 @@ static int plan_create_impl(sdr_engine* e, const sdr_epl_item* items, const sdr_
             err = hipGetLastError();
         }
     }
-    if (err == hipSuccess)
-        err = hipMemcpyAsync(p->d_spacing, doubled ? spacing2 : spacing, n_taps * sizeof(double), hipMemcpyHostToDevice, e->stream);
+    if (err == hipSuccess) {
+        // (a long list's spacings go through the page-locked scratch its statistics came back to -- validate_items_dev reserved
+        // it; the final synchronisation below is what the copy's source waits for -- not out of the caller's pageable memory)
+        const double* src = doubled ? spacing2 : spacing;
+        if (long_list) {
+            double* const stage = reinterpret_cast<double*>(static_cast<char*>(e->ctx0.pinned) + 2 * sizeof(ItemStats));
+            std::memcpy(stage, src, n_taps * sizeof(double));
+            src = stage;
+        }
+        err = hipMemcpyAsync(p->d_spacing, src, n_taps * sizeof(double), hipMemcpyHostToDevice, e->stream);
+    }
     // ---- the per-item setups of the straight-line kernels: one launch, one thread per item (items and spacings are on the device)
     auto reserve_setups = [&](size_t bytes_per_item) {
         p->setup_bytes = bytes_per_item;
@@ -809,8 +822,8 @@ static int plan_create_impl(sdr_engine* e, const sdr_epl_item* items, const sdr_
     const double t_queued = now();
     if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
     if (timing)
-        fprintf(stderr, "plan_create %d items: validate %.2f ms, alloc %.2f, queue copies+setups %.2f, sync %.2f\n", n_items,
-                t_valid - t_begin, t_alloc - t_valid, t_queued - t_alloc, now() - t_queued);
+        fprintf(stderr, "plan_create %d items: validate %.3f ms, alloc %.3f, copy+check %.3f, queue setups %.3f, sync %.3f\n", n_items,
+                t_valid - t_begin, t_alloc - t_valid, t_checked - t_alloc, t_queued - t_checked, now() - t_queued);
     if (err != hipSuccess) {
         sdr_epl_plan_destroy(e, p);
         return sdr_fail(err == hipErrorOutOfMemory ? SDR_ERR_NOMEM : SDR_ERR_HIP, "plan setup failed: %s",
