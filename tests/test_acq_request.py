@@ -3,33 +3,27 @@ half-even samples per code, the status of every request that is wrong in one way
 searches and SerialSearch differ above 65535 bins or PRNs and on the code lengths -- and the grid length against NumPy's own
 len(np.arange(-R, R + 1, S)) for the pairs of test_doppler_grid_length_host_helper and a few thousand random ones (`make
 check-sanitize` runs the same program under the address and undefined-behaviour sanitizers)."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+import host_check
 
 
 @pytest.fixture(scope="module")
-def check(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("acq_request") / "acq_request_check")
-    subprocess.run([HIPCC, "-O1", "-std=c++17", "--cuda-host-only", "-ffp-contract=off", "-o", exe,
-                    os.path.join(REPO, "tests", "csrc", "acq_request_check.hip")], check=True, capture_output=True, timeout=300)
-    return exe
+def check():
+    return host_check.build("acq_request_check")
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+@host_check.requires_hipcc
 def test_single_faults_and_rounding(check):
     out = subprocess.run([check], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and out.stdout.startswith("ok "), out.stdout[-2000:] + out.stderr[-2000:]
     assert int(out.stdout.split()[1]) >= 3 * 25 + 11      # (+ SerialSearch's short-code rule at 1.0, 1.023, 4 and 16.368 MHz)
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+@host_check.requires_hipcc
 def test_grid_length_is_numpys(check):
     pairs = [(5000.0, 250.0), (5000.0, 100.0), (5000.0, 300.0), (7000.0, 125.0), (10.0, 3.0)]
     rng = np.random.default_rng(20261020)

@@ -3,35 +3,28 @@ host only: every refusal in the header's order, N / T / the exclusion width for 
 old check and the old request's unchanged answers -- and the samples per code against NumPy's rint(fs * L / chip_rate) for
 the rates of the tests and a few thousand random ones (`make check-sanitize` runs the same program under the address and
 undefined-behaviour sanitizers)."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import host_check
 from sydr_amd.dsp import signalsearch as ss
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
 @pytest.fixture(scope="module")
-def check(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("acq_signal") / "acq_signal_check")
-    subprocess.run([HIPCC, "-O1", "-std=c++17", "--cuda-host-only", "-ffp-contract=off", "-o", exe,
-                    os.path.join(REPO, "tests", "csrc", "acq_signal_check.hip")], check=True, capture_output=True, timeout=300)
-    return exe
+def check():
+    return host_check.build("acq_signal_check")
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+@host_check.requires_hipcc
 def test_refusals_lengths_and_the_old_request(check):
     out = subprocess.run([check], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and out.stdout.startswith("ok "), out.stdout[-2000:] + out.stderr[-2000:]
     assert int(out.stdout.split()[1]) >= 120
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+@host_check.requires_hipcc
 def test_samples_per_code_is_numpys(check):
     triples = [(4.092e6, 4092, 1.023e6), (4.0e6, 8184, 2.046e6), (2.038e6, 1023, 1.023e6), (50e6, 4092, 1.023e6),
                (50e6, 10230, 10.23e6), (4000500.0, 1023, 1.023e6), (4001500.0, 1023, 1.023e6), (2500.0, 1, 1000.0), (3500.0, 1, 1000.0)]

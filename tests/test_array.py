@@ -5,7 +5,6 @@ of the end-to-end recording the GPU test relies on -- the oracle misses the sate
 power-inversion combination."""
 import ctypes as C
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -14,13 +13,13 @@ import pytest
 from conftest import REPO
 import array_cases as cases
 import ddc_layout_cases as lcases
+import host_check
 
 from sydr_amd import _lib
 from sydr_amd.engine import array_struct
 from sydr_amd.signal import array as ar
 from sydr_amd.signal import downconvert as dc
 
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 INVALID = -1
 
 
@@ -210,15 +209,14 @@ def test_c_struct_prototypes_and_host_side_refusals(tmp_path):
     assert (c.n_elements, c.flags, list(c.lanes), [list(w) for w in c.weights][:3]) == (3, 1, [5, 0, 2, 0, 0, 0, 0, 0], [[1.0, 2.0], [3.0, -4.0], [0.0, 0.5]])
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_array_arithmetic_on_the_host(tmp_path):
+@host_check.requires_hipcc
+def test_array_arithmetic_on_the_host():
     """sydr_amd/csrc/ddc_array.h, the decode and the combine the converter's kernels and its host side share, compiled for the host
     alone (tests/csrc/ddc_array_check.hip): limits, the K-element decode against a bit-by-bit reading, the combine's order against
     a restatement that stores every intermediate -- once as it is, once with contraction allowed to the compiler, which the
     header must withstand."""
-    for flags in (["-O1"], ["-O3", "-ffp-contract=fast"]):
-        exe = tmp_path / "ddc_array_check"
-        subprocess.check_call([HIPCC, *flags, "-std=c++17", "--cuda-host-only", "-o", str(exe), os.path.join(REPO, "tests", "csrc", "ddc_array_check.hip")])
+    for flags in (("-O1",), ("-O3", "-ffp-contract=fast")):
+        exe = host_check.build("ddc_array_check", flags)
         out = subprocess.run([str(exe)], capture_output=True, text=True)
         assert out.returncode == 0 and out.stdout.startswith("ok "), out.stdout + out.stderr
         assert int(out.stdout.split()[1]) > 30000

@@ -17,32 +17,26 @@ half (operands below 2^12: 2^-42 each): under 60 roundings, 4.4e-10.  Asserted: 
 
 Covered: random bytes and rail bytes (every u = 0 or 255: sums and differences of 0 / 510 before the offset), carriers of
 0, +-5 kHz and +-4 MHz at 25 MHz, every (block length, half) the kernels are instantiated for."""
-import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import REPO
+import host_check
 
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 FS = 25e6
 CARRIERS = (0.0, 5e3, -5e3, 4e6, -4e6)
 # (KM, half, taps switching inside the block): the KS forms (KS = KM // 2, half = KS + 1) and the whole-chip-tap forms
 FORMS = [(km, km // 2 + 1, 1) for km in range(16, 26)] + [(km, (km + 2) // 2, 0) for km in range(15, 26)]
 BLOCK_BOUND = 5e-10
 
-pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+pytestmark = host_check.requires_hipcc
 
 
 @pytest.fixture(scope="module")
-def exe(tmp_path_factory):
-    path = tmp_path_factory.mktemp("chip_fold") / "chip_fold_dump"
-    subprocess.check_call([HIPCC, "-O1", "-std=c++17", "--cuda-host-only", "-ffp-contract=off", "-o", str(path),
-                           os.path.join(REPO, "tests", "csrc", "chip_fold_dump.hip")])
-    return str(path)
+def exe():
+    return host_check.build("chip_fold_dump")
 
 
 def _run(exe, km, half, ks, carrier, mode, n_blocks, seed):

@@ -24,16 +24,13 @@ agree with the per-tap combination to the bound times the number of blocks (the 
 
 Covered: random bytes and rail bytes, carriers of 0, +-5 kHz and +-4 MHz at 25 MHz, every (block length, half) the kernels
 are instantiated for, each both folded and direct (a build chooses per form: chip_folds())."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import REPO
+import host_check
 
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 FS = 25e6
 CARRIERS = (0.0, 5e3, -5e3, 4e6, -4e6)
 # (KM, half, taps switching inside the block): the KS forms (KS = KM // 2, half = KS + 1) and the whole-chip-tap forms
@@ -41,15 +38,12 @@ FORMS = [(km, km // 2 + 1, 1) for km in range(16, 26)] + [(km, (km + 2) // 2, 0)
 BLOCK_BOUND = 5e-10
 N_BLOCKS = 12
 
-pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+pytestmark = host_check.requires_hipcc
 
 
 @pytest.fixture(scope="module")
-def exe(tmp_path_factory):
-    path = tmp_path_factory.mktemp("chip_mask") / "chip_mask_dump"
-    subprocess.check_call([HIPCC, "-O1", "-std=c++17", "--cuda-host-only", "-ffp-contract=off", "-o", str(path),
-                           os.path.join(REPO, "tests", "csrc", "chip_mask_dump.hip")])
-    return str(path)
+def exe():
+    return host_check.build("chip_mask_dump")
 
 
 def _run(exe, km, half, ks, fold, carrier, mode, n_blocks, seed):

@@ -11,30 +11,23 @@ A HOST build of the same __host__ __device__ functions walks every lane and roun
 the last round's clamp included, and a grid of crafted fractions (0, 2^32 - 1, both edges of the window).  Every block is
 compared, inside the window as well: the walk is integer arithmetic and has to agree everywhere.  Away from the window the
 block starts are also the reference's own (oracle: ceil(linspace))."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import REPO
+import host_check
 from oracle import sydr_oracle as orc
 
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 NEAR = 1 << 16
 TWO32 = 1 << 32
 STRIDE = 64
 
-pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+pytestmark = host_check.requires_hipcc
 
 
-def _exe(tmp_path):
-    exe = tmp_path / "chip_walk_dump"
-    if not exe.exists():
-        subprocess.check_call([HIPCC, "-O1", "-std=c++17", "--cuda-host-only", "-ffp-contract=off", "-o", str(exe),
-                               os.path.join(REPO, "tests", "csrc", "chip_walk_dump.hip")])
-    return str(exe)
+def _exe():
+    return host_check.build("chip_walk_dump")
 
 
 def _near(u):
@@ -64,9 +57,9 @@ GEOMETRIES = {"25": (24, 12, False, (-0.5, 0.0, 0.5), 1), "20": (19, 9, False, (
 
 
 @pytest.mark.parametrize("geometry", ["25", "20", "50h"])
-def test_walk_equals_the_64_bit_line(tmp_path, geometry):
+def test_walk_equals_the_64_bit_line(geometry):
     M, m_tap, whole, spacing, view = GEOMETRIES[geometry]
-    items = _items(subprocess.check_output([_exe(tmp_path), geometry, "24", "2027"], text=True))
+    items = _items(subprocess.check_output([_exe(), geometry, "24", "2027"], text=True))
     assert len(items) == 24
     checked = clamped = in_window = against_reference = 0
     for it in items:
@@ -116,8 +109,8 @@ def test_walk_equals_the_64_bit_line(tmp_path, geometry):
     assert checked > 20000 and clamped > 0 and against_reference > 20000
 
 
-def test_crafted_fractions(tmp_path):
-    out = subprocess.check_output([_exe(tmp_path), "crafted"], text=True)
+def test_crafted_fractions():
+    out = subprocess.check_output([_exe(), "crafted"], text=True)
     seen_f, n = set(), 0
     for line in out.splitlines():
         w = line.split()

@@ -11,20 +11,19 @@ The fine grid has K = 2*floor(span/step) + 1 frequencies, an odd number: the lar
 cases k63first / k63last use where the issue spoke of K = 64."""
 import ctypes as C
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
 import coherent_cases as cc
+import host_check
 from conftest import REPO
 from sydr_amd import _lib
 from sydr_amd.dsp.signalsearch import fine_grid
 from test_abi import declared_symbols
 
 MARGIN = 1e-6                  # the project's: a maximum must exceed every other entry by more than this times itself
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
 # ------------------------------------------------------------------------------------------------ 1. ABI
@@ -56,11 +55,9 @@ def test_coherent_struct_layouts_agree_with_the_c_compiler(tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------ 2. the argument checks
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_request_check_single_faults_limits_and_cuts(tmp_path):
-    exe = str(tmp_path / "coherent_request_check")
-    subprocess.run([HIPCC, "-O1", "-std=c++17", "--cuda-host-only", "-ffp-contract=off", "-o", exe,
-                    os.path.join(REPO, "tests", "csrc", "coherent_request_check.hip")], check=True, capture_output=True, timeout=300)
+@host_check.requires_hipcc
+def test_request_check_single_faults_limits_and_cuts():
+    exe = host_check.build("coherent_request_check")
     out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and out.stdout.startswith("ok "), out.stdout[-2000:] + out.stderr[-2000:]
     assert int(out.stdout.split()[1]) >= 90

@@ -2,18 +2,14 @@
 is the existing NumPy statement, the inputs are fair, and the run walk the kernel's lanes execute (sydr_amd/csrc/corr_bounds.h,
 compiled for the host alone) is the run-length encoding of NumPy's chip indices, exactly."""
 import itertools
-import os
-import shutil
 import subprocess
 
 import numpy as np
-import pytest
 
 import corr_cases as cc
-from conftest import REPO, load_golden
+import host_check
+from conftest import load_golden
 from oracle import sydr_oracle as orc
-
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
 # ------------------------------------------------------------------------------------- 1. the model is the statement
@@ -92,14 +88,12 @@ def _rle(idx):
     return first, idx[first]
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_run_walk_is_the_run_length_encoding_of_numpys_indices(tmp_path):
+@host_check.requires_hipcc
+def test_run_walk_is_the_run_length_encoding_of_numpys_indices():
     """corr_bounds.h on the host: for every combination of rate, Doppler, rem_code and spacing, over a 4 ms epoch of a
     4092-chip code, the (first sample, padded index) pairs the walk produces are exactly the run-length encoding of
     orc.epl_indices -- no case excluded."""
-    exe = tmp_path / "corr_bounds_check"
-    subprocess.check_call([HIPCC, "-O1", "-std=c++17", "--cuda-host-only", "-ffp-contract=off", "-o", str(exe),
-                           os.path.join(REPO, "tests", "csrc", "corr_bounds_check.hip")])
+    exe = host_check.build("corr_bounds_check")
     sets = runs = exact_phase = 0
     for fs, dop in itertools.product(cc.BOUNDS_RATES, DOPPLERS):
         cstep = orc.CODE_RATE * (1.0 + dop / 1575.42e6) / fs

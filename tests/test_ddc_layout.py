@@ -4,7 +4,6 @@ decoded integers, bit for bit; `bytes_for`; the [RFSIGNAL] keys and their refusa
 recording (oracle-backed engine); the C struct and sdr_ddc_layout_bytes; the shared field arithmetic run on the host."""
 import ctypes as C
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -12,6 +11,7 @@ import pytest
 
 from conftest import REPO
 import downconvert_cases as dcases
+import host_check
 import ddc_layout_cases as cases
 import packed_cases
 from test_downconvert import ConvertingOracleEngine
@@ -24,7 +24,6 @@ from sydr_amd.signal import packing as pk
 from sydr_amd.signal.iqsource import RFSignal
 from sydr_amd.utils.enumerations import ChannelMessage
 
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 INVALID = -1
 
 
@@ -373,14 +372,12 @@ def test_sdr_ddc_layout_bytes_through_ctypes():
 
 
 # ---------------------------------------------------------------------------------------------- 7. the field arithmetic
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_field_arithmetic_on_the_host(tmp_path):
+@host_check.requires_hipcc
+def test_field_arithmetic_on_the_host():
     """sydr_amd/csrc/ddc_layout.h, the decode the converter's kernels and its host side share, compiled for the host alone and
     checked exhaustively over bits, both bit orders, stride <= 9, every lane, real and complex, swap, j < 64 against a
     bit-by-bit reading (tests/csrc/ddc_layout_check.hip)."""
-    exe = tmp_path / "ddc_layout_check"
-    subprocess.check_call([HIPCC, "-O1", "-std=c++17", "--cuda-host-only", "-o", str(exe),
-                           os.path.join(REPO, "tests", "csrc", "ddc_layout_check.hip")])
+    exe = host_check.build("ddc_layout_check")
     out = subprocess.run([str(exe)], capture_output=True, text=True)
     assert out.returncode == 0 and out.stdout.startswith("ok "), out.stdout + out.stderr
     assert int(out.stdout.split()[1]) > 50000

@@ -4,7 +4,6 @@
 output stored as an ordinary complex recording); the C struct's layout; the shared index arithmetic run on the host."""
 import ctypes as C
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -14,6 +13,7 @@ from conftest import REPO
 from oracle import sydr_oracle as orc
 from fake_engine import OracleEngine
 import downconvert_cases as cases
+import host_check
 import packed_cases
 
 from sydr_amd import _lib
@@ -22,7 +22,6 @@ from sydr_amd.signal import downconvert as dc
 from sydr_amd.signal.iqsource import RFSignal
 from sydr_amd.utils.enumerations import ChannelMessage
 
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
 # ---------------------------------------------------------------------------------------------- 1. the statement
@@ -287,13 +286,11 @@ def test_ddc_cfg_layout_agrees_with_the_c_compiler(tmp_path):
 
 
 # ---------------------------------------------------------------------------------------------- 5. the index arithmetic
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_tile_history_and_ring_arithmetic_on_the_host(tmp_path):
+@host_check.requires_hipcc
+def test_tile_history_and_ring_arithmetic_on_the_host():
     """sydr_amd/csrc/ddc_tiles.h, the arithmetic the converter's kernels and its host side share, compiled for the host alone
     and checked exhaustively over small T, D, tile, push length, ring offset and capacity (tests/csrc/ddc_tiles_check.hip)."""
-    exe = tmp_path / "ddc_tiles_check"
-    subprocess.check_call([HIPCC, "-O1", "-std=c++17", "--cuda-host-only", "-o", str(exe),
-                           os.path.join(REPO, "tests", "csrc", "ddc_tiles_check.hip")])
+    exe = host_check.build("ddc_tiles_check")
     out = subprocess.run([str(exe)], capture_output=True, text=True)
     assert out.returncode == 0 and out.stdout.startswith("ok "), out.stdout + out.stderr
     assert int(out.stdout.split()[1]) > 100000

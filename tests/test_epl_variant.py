@@ -9,28 +9,24 @@
   - "needs setups" is said exactly of the words with a compile-time tap geometry, and of the several-chip shapes;
   - the rows of the two units' lists of straight-line forms are exactly the tuples decode can ask for."""
 import os
-import shutil
 import subprocess
 
 import pytest
 
+import host_check
 from conftest import REPO
 
 import bench
 
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 CI8, CI16 = 0, 1
 CHIP, KS_MASK, KI, C2 = 26, 0xF00, 4096, 8192
 
-pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+pytestmark = host_check.requires_hipcc
 
 
 @pytest.fixture(scope="module")
-def exe(tmp_path_factory):
-    path = tmp_path_factory.mktemp("epl_variant") / "epl_variant_dump"
-    subprocess.check_call([HIPCC, "-O1", "-std=c++17", "--cuda-host-only", "-o", str(path),
-                           os.path.join(REPO, "tests", "csrc", "epl_variant_dump.hip")])
-    return str(path)
+def exe():
+    return host_check.build("epl_variant_dump")
 
 
 @pytest.fixture(scope="module")

@@ -3,32 +3,26 @@ tests/csrc/fused_work_check.hip, host only: the check passes with the key as it 
 lists -- fails with the three ints the key used to be, on the pair a 25 MHz search over 82 bins and a 50 MHz search over 41
 bins make (the proof that the check would have caught the stale list; `make check-sanitize` runs the same program under
 the address and undefined-behaviour sanitizers)."""
-import os
-import shutil
 import subprocess
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+import host_check
 
 
 @pytest.fixture(scope="module")
-def check(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("fused_work") / "fused_work_check")
-    subprocess.run([HIPCC, "-O1", "-std=c++17", "--cuda-host-only", "-o", exe, os.path.join(REPO, "tests", "csrc", "fused_work_check.hip")],
-                   check=True, capture_output=True, timeout=300)
-    return exe
+def check():
+    return host_check.build("fused_work_check")
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+@host_check.requires_hipcc
 def test_work_lists_and_their_key(check):
     out = subprocess.run([check], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and out.stdout.startswith("ok "), out.stdout[-2000:] + out.stderr[-2000:]
     assert int(out.stdout.split()[1]) >= 40 * 90 * 2 * 3
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+@host_check.requires_hipcc
 def test_the_three_int_key_confuses_25_and_50_mhz(check):
     out = subprocess.run([check, "three-int"], capture_output=True, text=True, timeout=300)
     assert out.returncode == 1, out.stdout[-2000:]

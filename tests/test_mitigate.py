@@ -4,7 +4,6 @@ that measure a level and limits; the [RFSIGNAL] keys; the acquisition case that 
 manager's route over the oracle-backed engine; the C structs' layout; the shared index arithmetic run on the host."""
 import ctypes as C
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -13,6 +12,7 @@ import pytest
 from conftest import REPO
 from fake_engine import OracleEngine
 import downconvert_cases as dcases
+import host_check
 import mitigate_cases as cases
 import packed_cases
 
@@ -22,7 +22,6 @@ from sydr_amd.signal import mitigate as mt
 from sydr_amd.signal.iqsource import RFSignal
 from sydr_amd.utils.enumerations import ChannelMessage
 
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
 def stream(n=20001):
@@ -285,14 +284,12 @@ def test_mit_struct_layouts_agree_with_the_c_compiler(tmp_path):
 
 
 # ---------------------------------------------------------------------------------------------- 7. the index arithmetic
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_push_segment_and_state_arithmetic_on_the_host(tmp_path):
+@host_check.requires_hipcc
+def test_push_segment_and_state_arithmetic_on_the_host():
     """sydr_amd/csrc/mit_plan.h, the arithmetic the mitigator's kernels and its host side share, compiled for the host alone
     and held against a brute-force restatement over small N, lead, hold, push lengths, ring offsets and capacities
     (tests/csrc/mit_plan_check.hip)."""
-    exe = tmp_path / "mit_plan_check"
-    subprocess.check_call([HIPCC, "-O1", "-std=c++17", "--cuda-host-only", "-o", str(exe),
-                           os.path.join(REPO, "tests", "csrc", "mit_plan_check.hip")])
+    exe = host_check.build("mit_plan_check")
     out = subprocess.run([str(exe)], capture_output=True, text=True)
     assert out.returncode == 0 and out.stdout.startswith("ok "), out.stdout + out.stderr
     assert int(out.stdout.split()[1]) > 100000

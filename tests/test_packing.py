@@ -3,7 +3,6 @@ host helper of the C-ABI, RFSignal over packed files, the manager's packed route
 equal to those of the same levels stored as int8), the unpack kernels' lane arithmetic run on the host, the packing tool."""
 import ctypes as C
 import os
-import shutil
 import subprocess
 import sys
 
@@ -14,13 +13,13 @@ from conftest import REPO
 from oracle import sydr_oracle as orc
 from fake_engine import OracleEngine
 import packed_cases as cases
+import host_check
 
 from sydr_amd import _lib
 from sydr_amd.signal import packing as pk
 from sydr_amd.signal.iqsource import RFSignal
 from sydr_amd.utils.enumerations import ChannelMessage
 
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 ALL = [(bits, msb) for bits in (1, 2, 4) for msb in (False, True)]
 
 
@@ -273,13 +272,11 @@ def test_manager_over_a_packed_file_equals_the_same_levels_as_int8(tmp_path, two
 
 
 # ---------------------------------------------------------------------------------------------- 5. the lane arithmetic
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_unpack_lane_arithmetic_on_the_host(tmp_path):
+@host_check.requires_hipcc
+def test_unpack_lane_arithmetic_on_the_host():
     """sydr_amd/csrc/unpack_lanes.h, the code the unpack kernels' lanes run, compiled for the host alone: every byte value
     x position x order x width with hostile tables equals the per-field statement."""
-    exe = tmp_path / "unpack_lanes_check"
-    subprocess.check_call([HIPCC, "-O1", "-std=c++17", "--cuda-host-only", "-o", str(exe),
-                           os.path.join(REPO, "tests", "csrc", "unpack_lanes_check.hip")])
+    exe = host_check.build("unpack_lanes_check")
     out = subprocess.run([str(exe)], capture_output=True, text=True)
     assert out.returncode == 0 and out.stdout.startswith("ok "), out.stdout + out.stderr
     assert int(out.stdout.split()[1]) == 6 * 2 * 256 * (2 + 4 + 8)

@@ -4,26 +4,20 @@ the block boundaries are predicted from (correlator_chip.h: chip_geometry, corre
 the reference's own chip-index expression ceil(linspace(...)) (tracking.py:111-112, through the oracle) on the CPU: first
 and last partial chips, every block start, every tap switch.  The kernels trust a prediction unless it lies within 2^-16
 of a sample (where they evaluate the reference expression exactly): so must this test."""
-import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import REPO
+import host_check
 from oracle import sydr_oracle as orc
 
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 NEAR = 1 << 16
 
 
-def _dump(tmp_path, fs, n_items, seed):
-    exe = tmp_path / "chip_geometry_dump"
-    if not exe.exists():
-        subprocess.check_call([HIPCC, "-O1", "-std=c++17", "--cuda-host-only", "-ffp-contract=off", "-o", str(exe),
-                               os.path.join(REPO, "tests", "csrc", "chip_geometry_dump.hip")])
+def _dump(fs, n_items, seed):
+    exe = host_check.build("chip_geometry_dump")
     out = subprocess.check_output([str(exe), repr(fs), str(n_items), str(seed)], text=True)
     items = []
     for line in out.splitlines():
@@ -31,10 +25,10 @@ def _dump(tmp_path, fs, n_items, seed):
     return items
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+@host_check.requires_hipcc
 @pytest.mark.parametrize("fs", [25e6, 10e6])
-def test_plan_geometry_matches_the_reference_chip_indices(tmp_path, fs):
-    items = _dump(tmp_path, fs, 24, 2026)
+def test_plan_geometry_matches_the_reference_chip_indices(fs):
+    items = _dump(fs, 24, 2026)
     assert len(items) == 24
     checked = 0
     for it in items:

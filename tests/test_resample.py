@@ -6,7 +6,6 @@ formulation, against itself however the stream is cut, and at L = 1 against a fr
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -14,13 +13,13 @@ import pytest
 
 from conftest import REPO
 import downconvert_cases as dcases
+import host_check
 import resample_cases as cases
 
 from sydr_amd import _lib
 from sydr_amd.signal import downconvert as dc
 from sydr_amd.signal.iqsource import RFSignal
 
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
 # ---------------------------------------------------------------------------------------------- 1. the statement
@@ -276,14 +275,12 @@ def test_create_rational_prototype_agrees_with_the_header(tmp_path):
 
 
 # ---------------------------------------------------------------------------------------------- 5. the index arithmetic
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_tile_phase_history_and_ring_arithmetic_on_the_host(tmp_path):
+@host_check.requires_hipcc
+def test_tile_phase_history_and_ring_arithmetic_on_the_host():
     """sydr_amd/csrc/resample_tiles.h, the arithmetic the resampler's kernels and its host side share, compiled for the host
     alone and checked exhaustively over small L, M, T, tile, push length, ring offset and capacity
     (tests/csrc/resample_tiles_check.hip)."""
-    exe = tmp_path / "resample_tiles_check"
-    subprocess.check_call([HIPCC, "-O1", "-std=c++17", "--cuda-host-only", "-o", str(exe),
-                           os.path.join(REPO, "tests", "csrc", "resample_tiles_check.hip")])
+    exe = host_check.build("resample_tiles_check")
     out = subprocess.run([str(exe)], capture_output=True, text=True)
     assert out.returncode == 0 and out.stdout.startswith("ok "), out.stdout + out.stderr
     assert int(out.stdout.split()[1]) > 1000000

@@ -7,12 +7,12 @@ margin (max - second) / max: A 0.023-0.123, B 0.0023-0.0064, D 0.017-0.077, E 0.
 second-best hypothesis 2.5-5.2."""
 import ctypes as C
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import host_check
 import refine_cases as rc
 import secondary_cases as sc
 from conftest import REPO
@@ -21,7 +21,6 @@ from sydr_amd.dsp.signalsearch import NH10, NH20
 from test_abi import declared_symbols
 
 MARGIN = 1e-6                  # the project's: the model's maximum must exceed every other entry of P by more than this times itself
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
 # ------------------------------------------------------------------------------------------------ 1. ABI
@@ -64,11 +63,9 @@ def test_neuman_hofman_codes():
 
 
 # ------------------------------------------------------------------------------------------------ 2. the argument checks
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_request_check_single_faults(tmp_path):
-    exe = str(tmp_path / "secondary_request_check")
-    subprocess.run([HIPCC, "-O1", "-std=c++17", "--cuda-host-only", "-ffp-contract=off", "-o", exe,
-                    os.path.join(REPO, "tests", "csrc", "secondary_request_check.hip")], check=True, capture_output=True, timeout=300)
+@host_check.requires_hipcc
+def test_request_check_single_faults():
+    exe = host_check.build("secondary_request_check")
     out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and out.stdout.startswith("ok "), out.stdout[-2000:] + out.stderr[-2000:]
     assert int(out.stdout.split()[1]) >= 70

@@ -5,7 +5,6 @@ prototypes, the shared arithmetic run on the host (tests/csrc/ddc_stap_check.hip
 [RFSIGNAL] keys and the manager's training over a fake engine, and the table of the end-to-end recording the GPU test relies on."""
 import ctypes as C
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -14,6 +13,7 @@ import pytest
 from conftest import REPO
 import array_cases as cases
 import ddc_layout_cases as lcases
+import host_check
 import stap_cases as scases
 
 from sydr_amd import _lib
@@ -21,7 +21,6 @@ from sydr_amd.signal import array as ar
 from sydr_amd.signal import downconvert as dc
 from sydr_amd.signal import stap
 
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
 # ---------------------------------------------------------------------------------------------- 1. identities of the statement
@@ -223,15 +222,14 @@ def test_c_prototypes_and_host_side_refusals(tmp_path):
     assert (c.n_elements, c.flags, list(c.lanes)) == (3, 1, [5, 0, 2, 0, 0, 0, 0, 0])
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_stap_arithmetic_on_the_host(tmp_path):
+@host_check.requires_hipcc
+def test_stap_arithmetic_on_the_host():
     """sydr_amd/csrc/ddc_stap.h, the combine and the raw tail the converter's kernels and its host side share, compiled for the host
     alone (tests/csrc/ddc_stap_check.hip): as it is, with contraction allowed to the compiler, which the header must withstand,
     and as a stand-alone binary under the address and undefined-behaviour sanitizers."""
-    for flags in (["-O1"], ["-O3", "-ffp-contract=fast"],
-                  ["-O1", "-g", "-ffp-contract=off", "-Xarch_host", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"]):
-        exe = tmp_path / "ddc_stap_check"
-        subprocess.check_call([HIPCC, *flags, "-std=c++17", "--cuda-host-only", "-o", str(exe), os.path.join(REPO, "tests", "csrc", "ddc_stap_check.hip")])
+    for flags in (("-O1",), ("-O3", "-ffp-contract=fast"),
+                  ("-O1", "-g", "-ffp-contract=off", "-Xarch_host", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer")):
+        exe = host_check.build("ddc_stap_check", flags)
         out = subprocess.run([str(exe)], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
         assert out.returncode == 0 and out.stdout.startswith("ok "), out.stdout + out.stderr
         assert int(out.stdout.split()[1]) > 50000

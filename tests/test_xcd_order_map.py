@@ -5,28 +5,22 @@ for every run length of the sweep in docs/notes/K1.md and every launch size n = 
   - inside a full tile of 8 * R the ids with the same b % 8 -- one XCD's -- map, in ascending order of b, to ONE contiguous
     ascending run of R items, XCD x to the tile's x-th run;
   - the partial last tile, a launch shorter than a tile and R = 0 keep the linear order."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import REPO
+import host_check
 
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 XCDS = 8
 SWEEP = (0, 8, 16, 32, 64, 128)
 
-pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+pytestmark = host_check.requires_hipcc
 
 
 @pytest.fixture(scope="module")
-def exe(tmp_path_factory):
-    path = tmp_path_factory.mktemp("xcd_order") / "xcd_order_dump"
-    subprocess.check_call([HIPCC, "-O1", "-std=c++17", "--cuda-host-only", "-o", str(path),
-                           os.path.join(REPO, "tests", "csrc", "xcd_order_dump.hip")])
-    return str(path)
+def exe():
+    return host_check.build("xcd_order_dump")
 
 
 def _maps(exe, R, n_max):
