@@ -77,7 +77,7 @@ int sdr_device_count(int* n);
 /* ----------------------------------------------------------------- engine */
 int sdr_engine_create(int device_id, sdr_engine** out);
 void sdr_engine_destroy(sdr_engine* e);
-/* Wait for everything queued on the engine's stream. */
+/* Wait for everything queued on the engine's stream, and for the setups of every E/P/L plan made so far. */
 int sdr_engine_sync(sdr_engine* e);
 /* HIP-event timing.  enable=1 brackets every stage of a call (named scopes: "epl_kernel", "pcps_fwd_fft", ...) with
  * hipEvents on the launch stream; enable=2 brackets each whole call instead ("call_pcps": one event pair around
@@ -202,7 +202,11 @@ int sdr_epl_batch(sdr_engine* e, const sdr_epl_item* items, int n_items, const d
  * straight-line kernels serve (ci8 ring; 24-25 samples per (half-)chip with taps +-0.5 chip or whole chips apart; 9.5-10 or
  * 11.5-12 samples per chip with taps +-0.5 chip), works out each epoch's setup -- tap constants, chip geometry, carrier
  * rotations -- in one launch with a thread per item: 400-560 bytes of device memory per item, so that the correlator
- * starts an epoch with scalar loads instead of ~450 vector instructions repeated in all 64 lanes. */
+ * starts an epoch with scalar loads instead of ~450 vector instructions repeated in all 64 lanes.
+ * For a list of 4096 items or more that launch is made on a stream of its own and creation returns once the list has been
+ * checked (`items` is the caller's again, every error has been reported): run and fetch are ordered behind the setups on
+ * the device, destroy waits for them, and so do sdr_engine_sync, sdr_iq_alloc and sdr_code_slots(_ex).
+ * sdr_set_option(e, "epl_plan_wait", 1) makes creation wait for them itself (A/B timing, tests); same bits either way. */
 typedef struct sdr_epl_plan sdr_epl_plan;
 int sdr_epl_plan_create(sdr_engine* e, const sdr_epl_item* items, int n_items,
                         const double* spacing, int n_taps, double fs, sdr_epl_plan** out);

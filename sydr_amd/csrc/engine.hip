@@ -77,6 +77,8 @@ StreamCtx* sdr_stream_ctx(sdr_engine* e, int stream_id) {
     return e->streams[(size_t)stream_id - 1];
 }
 
+hipError_t sdr_sync_plans(sdr_engine* e) { return e->plan_stream ? hipStreamSynchronize(e->plan_stream) : hipSuccess; }
+
 int sdr_devbuf_reserve_on(sdr_engine* e, hipStream_t stream, DevBuf* b, size_t bytes) {
     (void)e;
     if (bytes <= b->bytes && b->ptr) return SDR_OK;
@@ -278,6 +280,7 @@ int sdr_set_option(sdr_engine* e, const char* name, int value) {
         if (value < -1 || value > kEplXcdRunMax) return sdr_fail(SDR_ERR_RANGE, "epl_xcd_run %d outside -1..%d", value, kEplXcdRunMax);
         e->epl_xcd_run = value < 0 ? kEplXcdRunDefault : value;
     }
+    else if (!strcmp(name, "epl_plan_wait")) e->epl_plan_wait = value != 0;
     else if (!strcmp(name, "epl_no_half_chip_view")) e->epl_no_double = value != 0;
     else if (!strcmp(name, "epl_no_two_chip_variant")) e->epl_no_chip2 = value != 0;
     else if (!strcmp(name, "corr_profile_per_sample")) e->corr_per_sample = value != 0;
@@ -406,6 +409,7 @@ void sdr_engine_destroy(sdr_engine* e) {
     if (e->luts) (void)hipFree(e->luts);
     if (e->luts2) (void)hipFree(e->luts2);
     if (e->pcps_aux) (void)hipStreamDestroy(e->pcps_aux);
+    if (e->plan_stream) (void)hipStreamDestroy(e->plan_stream);   // (idle: the device was waited for above)
     for (hipEvent_t ev : e->pcps_ev)
         if (ev) (void)hipEventDestroy(ev);
     if (e->code_len) (void)hipFree(e->code_len);
@@ -416,6 +420,7 @@ void sdr_engine_destroy(sdr_engine* e) {
 int sdr_engine_sync(sdr_engine* e) {
     if (int rc = sdr_set_device(e)) return rc;
     SDR_HIP(hipStreamSynchronize(e->stream));
+    SDR_HIP(sdr_sync_plans(e));         // (the setups of plans whose creation has returned)
     return SDR_OK;
 }
 
@@ -488,6 +493,7 @@ int sdr_iq_alloc(sdr_engine* e, int64_t capacity_samples, int fmt) {
         return sdr_fail(SDR_ERR_INVALID, "ring capacity %lld must be a positive multiple of 8 samples",
                         (long long)capacity_samples);
     SDR_HIP(hipStreamSynchronize(e->stream));
+    SDR_HIP(sdr_sync_plans(e));         // (setups still being made belong to plans of the old ring: none is in flight when it goes)
     for (DevBuf& b : e->plan_pool)      // (plans of the old ring are stale: what they left behind makes room for the new one)
         if (b.ptr) (void)hipFree(b.ptr);
     e->plan_pool.clear();

@@ -109,6 +109,11 @@ struct sdr_engine {
     // segment by segment makes and drops a plan per segment, and hipMalloc / hipFree cost more than the segment's setups --
     // hipFree also waits for the whole device, i.e. for the segment still running on another stream.
     std::vector<DevBuf> plan_pool;
+    // The stream a long list's per-item setups are made on (epl.hip plan_create_impl), made with the first such plan:
+    // chip_setup_kernel gets room on a SIMD only where the launch of the segment before drains, and on the engine's stream
+    // the NEXT plan's item copy and check would queue behind it.  Every engine-wide wait covers it (sdr_sync_plans).
+    hipStream_t plan_stream = nullptr;
+    bool epl_plan_wait = false;      // "epl_plan_wait": a plan's creation returns when its setups are done, not when they are queued
     DevBuf pcps_fwd, pcps_a, pcps_b, pcps_code, pcps_tw, pcps_map, pcps_csum, pcps_part, pcps_res;
     DevBuf pcps_code2;            // N = 50 000, fused search: [prn][parity][N] -- the spectra and their image with the odd half's twiddle (pcps_fused.h)
     bool pcps_code2_ok = false;   // ... made from what pcps_code holds now
@@ -236,6 +241,9 @@ int sdr_devbuf_reserve(sdr_engine* e, DevBuf* b, size_t bytes);
 int sdr_devbuf_reserve_on(sdr_engine* e, hipStream_t stream, DevBuf* b, size_t bytes);
 int sdr_pinned_reserve(sdr_engine* e, StreamCtx* ctx, size_t bytes);
 StreamCtx* sdr_stream_ctx(sdr_engine* e, int stream_id);   // nullptr when the id does not exist
+// Wait for the setups of every E/P/L plan still being made on plan_stream (no-op before the first): what a wait for "the
+// engine" has to add to the wait for its own stream.
+hipError_t sdr_sync_plans(sdr_engine* e);
 // Queue the ring write of sdr_iq_upload on the engine's stream without waiting for it.
 int sdr_iq_upload_async(sdr_engine* e, const void* iq, int64_t n_samples, int64_t ring_offset);
 // hipSetDevice WITHOUT stopping a resident tick server (the tick's own entry points); sdr_set_device stops it.

@@ -212,6 +212,12 @@ struct sdr_epl_plan {
     // one event per stream a range of the plan was launched on, re-recorded behind every launch: fetch waits for
     // exactly these instead of the whole device
     std::vector<std::pair<hipStream_t, hipEvent_t>> ran_on;
+    // a long list's setups are made on the engine's plan_stream after creation has returned: recorded behind them, waited
+    // for on the device by every launch and fetch and by the host in destroy (nullptr: the setups were done when creation returned)
+    hipEvent_t ready = nullptr;
+    // work of the plan may be pending on the engine's own stream: a creation that ended on an error path or did all its work
+    // there, a range run on stream id 0.  Destroy then waits for that stream as well.
+    bool engine_stream_work = true;
 };
 
 // The per-epoch setups of the straight-line kernels (ChipSetup / ChipNSetup: tap constants, epoch geometry, ring position,
@@ -516,13 +522,18 @@ static int validate_items(sdr_engine* e, const sdr_epl_item* items, int n_items,
 }
 
 // Page-locked scratch of a long list's plan (StreamCtx::pinned of the engine's stream): the two ItemStats, then the tap
-// spacings, which the copy queued by plan_create_impl reads until the synchronisation that ends the plan's creation.
+// spacings.  Every copy that reads it is queued in front of a synchronisation of the engine's stream inside the plan's
+// creation (the statistics'; for the half-chip view's doubled spacings the one that ends the creation): once a creation has
+// returned nothing reads the scratch, so the next plan -- or any other call that stages through ctx0.pinned -- may write it,
+// whether or not the plan's setups are still being made.
 constexpr size_t kPlanPinnedBytes = 2 * sizeof(ItemStats) + SDR_MAX_TAPS * sizeof(double);
 
 // The same for a list that is already on the device (long lists: behind their upload).  ok2: the half-chip view's rules
-// were met as well (wide2 then holds its answer).
+// were met as well (wide2 then holds its answer).  The spacings go to d_spacing on the way: behind the statistics' copy, in
+// front of the wait for it.
 static int validate_items_dev(sdr_engine* e, const sdr_epl_item* d_items, const sdr_epl_item* h_items, int n_items,
-                              const double* spacing, int n_taps, int* lut_words, int* wide, bool* ok2, int* wide2) {
+                              const double* spacing, int n_taps, double* d_spacing, int* lut_words, int* wide, bool* ok2,
+                              int* wide2) {
     const ItemRules r1 = item_rules(e, spacing, n_taps, 1.0), r2 = item_rules(e, spacing, n_taps, 2.0);
     if (int rc = sdr_devbuf_reserve(e, &e->ws_stats, 2 * sizeof(ItemStats))) return rc;
     if (int rc = sdr_pinned_reserve(e, &e->ctx0, kPlanPinnedBytes)) return rc;
@@ -536,6 +547,12 @@ static int validate_items_dev(sdr_engine* e, const sdr_epl_item* d_items, const 
                        (const int32_t*)e->code_len, static_cast<ItemStats*>(e->ws_stats.ptr));
     SDR_HIP(hipGetLastError());
     SDR_HIP(hipMemcpyAsync(host, e->ws_stats.ptr, 2 * sizeof(ItemStats), hipMemcpyDeviceToHost, e->stream));
+    double* const stage = reinterpret_cast<double*>(static_cast<char*>(e->ctx0.pinned) + 2 * sizeof(ItemStats));
+    std::memcpy(stage, spacing, n_taps * sizeof(double));
+    SDR_HIP(hipMemcpyAsync(d_spacing, stage, n_taps * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    // The one wait of a long list's creation.  In front of it on this stream: the copy of the caller's items (truly
+    // asynchronous out of page-locked memory: the caller has its array back when this returns), the check, the statistics
+    // and the spacings -- everything the setups read is in device memory from here on.
     SDR_HIP(hipStreamSynchronize(e->stream));
     auto as_double = [](unsigned long long b) { double d; std::memcpy(&d, &b, sizeof(d)); return d; };
     if (host[0].first_bad != 0x7fffffff) {
@@ -695,7 +712,7 @@ static int plan_create_impl(sdr_engine* e, const sdr_epl_item* items, const sdr_
     if (err == hipSuccess && long_list) {
         int wide2 = 0;
         bool ok2 = false;
-        int rc = validate_items_dev(e, p->d_items, items, n_items, spacing, n_taps, &lut_words, &wide, &ok2, &wide2);
+        int rc = validate_items_dev(e, p->d_items, items, n_items, spacing, n_taps, p->d_spacing, &lut_words, &wide, &ok2, &wide2);
         if (!rc) rc = consider_half_chip_view(ok2, wide2);
         if (rc) {
             sdr_epl_plan_destroy(e, p);
@@ -737,9 +754,9 @@ static int plan_create_impl(sdr_engine* e, const sdr_epl_item* items, const sdr_
             err = hipGetLastError();
         }
     }
-    if (err == hipSuccess) {
-        // (a long list's spacings go through the page-locked scratch its statistics came back to -- validate_items_dev reserved
-        // it; the final synchronisation below is what the copy's source waits for -- not out of the caller's pageable memory)
+    if (err == hipSuccess && !(long_list && !doubled)) {     // (a long list's own spacings went over with its check)
+        // (the doubled spacings of a long list go through the page-locked scratch its statistics came back to -- validate_items_dev
+        // reserved it; the final synchronisation below is what the copy's source waits for -- not out of pageable memory)
         const double* src = doubled ? spacing2 : spacing;
         if (long_list) {
             double* const stage = reinterpret_cast<double*>(static_cast<char*>(e->ctx0.pinned) + 2 * sizeof(ItemStats));
@@ -770,8 +787,25 @@ static int plan_create_impl(sdr_engine* e, const sdr_epl_item* items, const sdr_
             row->on_host(doubled ? items2.data() : items, n_items, doubled ? spacing2 : spacing, fs, e->iq_capacity, host_setups.data());
             err = hipMemcpyAsync(p->d_setups, host_setups.data(), host_setups.size(), hipMemcpyHostToDevice, e->stream);
         } else if (err == hipSuccess) {
-            row->on_device(e->stream, p->d_items, n_items, p->d_spacing, fs, e->iq_capacity, p->d_setups);
-            err = hipGetLastError();
+            // A long list with buffers of its own, run as it is: the setups are queued on the engine's plan_stream and the
+            // creation returns without waiting for them.  Beside the launch of the segment before, chip_setup_kernel (196
+            // registers) gets a SIMD only where that launch drains; a caller that waits for it can queue the next launch only
+            // then, and on the engine's own stream the plan after this one would have its item copy and check stuck behind it.
+            // What the kernel reads is complete: the items and the spacings were waited for with the statistics.  What it
+            // writes is this plan's alone until `ready`, which every reader waits for (run, fetch, destroy).
+            // (Not so: the half-chip view, whose double_items_kernel and doubled spacings are queued on the engine's stream;
+            // sdr_epl_batch's shared workspaces.  Those keep the engine's stream and the wait that ends the creation.)
+            hipStream_t on = e->stream;
+            if (!doubled && !use_workspaces) {
+                if (!e->plan_stream) err = hipStreamCreateWithFlags(&e->plan_stream, hipStreamNonBlocking);
+                if (err == hipSuccess) err = hipEventCreateWithFlags(&p->ready, hipEventDisableTiming);
+                if (err == hipSuccess) on = e->plan_stream;
+            }
+            if (err == hipSuccess) {
+                row->on_device(on, p->d_items, n_items, p->d_spacing, fs, e->iq_capacity, p->d_setups);
+                err = hipGetLastError();
+            }
+            if (err == hipSuccess && p->ready) err = hipEventRecord(p->ready, e->plan_stream);
         }
     }
     // three taps half a chip apart and chips of 9.5 .. 10 or 11.5 .. 12 samples (the reference's shipped 10 MHz; 12 MHz): two
@@ -819,12 +853,21 @@ static int plan_create_impl(sdr_engine* e, const sdr_epl_item* items, const sdr_
             }
         }
     }
+    // (ahead: nothing of this plan is left on the engine's stream -- its last wait there was the statistics' -- and `ready` has
+    // been recorded behind the setups)
+    const bool ahead = err == hipSuccess && p->ready != nullptr;
     const double t_queued = now();
-    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-    if (timing)
-        fprintf(stderr, "plan_create %d items: validate %.3f ms, alloc %.3f, copy+check %.3f, queue setups %.3f, sync %.3f\n", n_items,
-                t_valid - t_begin, t_alloc - t_valid, t_checked - t_alloc, t_queued - t_checked, now() - t_queued);
+    if (err == hipSuccess && !ahead) err = hipStreamSynchronize(e->stream);
+    if (ahead && e->epl_plan_wait) err = hipEventSynchronize(p->ready);       // "epl_plan_wait": as a creation was before
+    if (err == hipSuccess && ahead) p->engine_stream_work = false;
+    if (timing) {    // (last field, ahead: from the call's begin until `ready` was recorded -- the call queues, it does not wait)
+        const bool queued_only = ahead && !e->epl_plan_wait;
+        fprintf(stderr, "plan_create %d items: validate %.3f ms, alloc %.3f, copy+check %.3f, queue setups %.3f, %s %.3f\n", n_items,
+                t_valid - t_begin, t_alloc - t_valid, t_checked - t_alloc, t_queued - t_checked,
+                queued_only ? "ready recorded at" : "sync", queued_only ? t_queued - t_begin : now() - t_queued);
+    }
     if (err != hipSuccess) {
+        if (p->ready) (void)sdr_sync_plans(e);      // (`ready` may not have been recorded behind setups that were queued)
         sdr_epl_plan_destroy(e, p);
         return sdr_fail(err == hipErrorOutOfMemory ? SDR_ERR_NOMEM : SDR_ERR_HIP, "plan setup failed: %s",
                         hipGetErrorString(err));
@@ -860,6 +903,10 @@ int sdr_epl_plan_run_range_on(sdr_engine* e, sdr_epl_plan* p, int64_t first, int
     const void* setups = p->d_setups ? p->d_setups + (size_t)first * p->setup_bytes : nullptr;
     // (the order in which the range's own workgroups, 0 .. count - 1, take its items: xcd_order.h; read when the plan runs)
     const int xcd_run = e->epl_xcd_run;
+    // behind the plan's setups, on the device: the host may be a whole launch ahead of them.  (On every stream, the engine's
+    // own included -- the setups are on none of them; in front of the ProfScope: "epl_kernel" times the launch, not the wait.)
+    if (p->ready) SDR_HIP(hipStreamWaitEvent(ctx->stream, p->ready, 0));
+    if (ctx->stream == e->stream) p->engine_stream_work = true;      // (destroy has the engine's stream to wait for)
     {
         hipStream_t st = ctx->stream;
         ProfScope ps(e, "epl_kernel", st);
@@ -900,6 +947,9 @@ int sdr_epl_plan_fetch(sdr_engine* e, sdr_epl_plan* p, double* out) {
     if (int rc = sdr_set_device(e)) return rc;
     if (!p || !out) return sdr_fail(SDR_ERR_INVALID, "NULL plan or output");
     for (auto& se : p->ran_on) SDR_HIP(hipStreamWaitEvent(e->stream, se.second, 0));   // the streams its ranges ran on, no others
+    // (every launch waited for `ready` itself, so ran_on and the engine's own order cover the setups; a plan that never ran
+    // has its copy behind them all the same)
+    if (p->ready) SDR_HIP(hipStreamWaitEvent(e->stream, p->ready, 0));
     SDR_HIP(hipMemcpyAsync(out, p->d_out, (size_t)p->n_items * 2 * p->n_taps * sizeof(double),
                            hipMemcpyDeviceToHost, e->stream));
     SDR_HIP(hipStreamSynchronize(e->stream));
@@ -908,15 +958,24 @@ int sdr_epl_plan_fetch(sdr_engine* e, sdr_epl_plan* p, double* out) {
 
 void sdr_epl_plan_destroy(sdr_engine* e, sdr_epl_plan* p) {
     if (!p) return;
-    if (e) {
-        (void)hipSetDevice(e->device);
-        (void)hipStreamSynchronize(e->stream);
+    // Waits for THIS plan's work, not for the engine's stream as such: in a segmented pass the next plan's item copy and check
+    // are queued there, and a destroy that waited for them would put the host back behind the running launch.
+    if (e) (void)hipSetDevice(e->device);
+    if (p->ready) {
+        (void)hipEventSynchronize(p->ready);
+        (void)hipEventDestroy(p->ready);
     }
     for (auto& se : p->ran_on) {
         (void)hipEventSynchronize(se.second);
         (void)hipEventDestroy(se.second);
     }
-    if (!p->borrowed) {     // (every stream the plan ran on has been waited for: the buffers are free to serve the next plan)
+    if (e && p->engine_stream_work) (void)hipStreamSynchronize(e->stream);
+    // The four buffers are free to serve the next plan.  d_items, d_spacing: written by copies that the creation waited for
+    // with the statistics (or, a creation that kept to the engine's stream or failed half-way, by work on that stream: waited
+    // for just above); read by the setups (`ready`) and the launches.  d_setups: written by the setups (`ready`, or the
+    // engine's stream), read by the launches.  d_out: written by the launches -- on other streams `ran_on`, on stream id 0 the
+    // engine's stream, waited for above -- and read by fetch, which waits for its own copy.
+    if (!p->borrowed) {
         plan_give(e, p->d_items, p->bytes_items);
         plan_give(e, p->d_out, p->bytes_out);
         plan_give(e, p->d_spacing, p->bytes_spacing);

@@ -10,7 +10,10 @@ Printed for it:
   * every chip_setup_kernel / validate_items_kernel dispatch against the epl_kernel launch that runs when it starts: start and
     end relative to that launch's start, its duration, and whether it starts and ends INSIDE the launch, runs past its end, or
     lies in the gap behind it; the hardware queue each kind of kernel was dispatched on;
-  * from the SDR_PLAN_TIMING lines, the median host time of each stage of sdr_epl_plan_create.
+  * every chip_setup_kernel dispatch against the launch that NEEDED it (a plan's creation returns with its setups queued): how
+    long before that launch's start, and before the end of the launch in front of it, the setups ended;
+  * from the SDR_PLAN_TIMING lines, the median host time of each stage of sdr_epl_plan_create (the last field of a line is
+    the wait that ends a creation, or "ready recorded at": the time from the call's begin to the setups being queued).
 """
 import argparse
 import csv
@@ -82,6 +85,30 @@ def timeline(rows, steps, segments):
             print("  end after the launch's start ms:   min %.4f median %.4f max %.4f" % quantiles(rel_e))
         if late:
             print("  (those in the gap) start after the launch's end ms: min %.4f median %.4f max %.4f" % quantiles(late))
+    setups_against_their_launch(rows, epl, n)
+
+
+def setups_against_their_launch(rows, epl, n):
+    """A plan has one chip_setup_kernel dispatch and, in the headline's passes, one launch: counted from the trace's end the
+    m-th setup belongs to the m-th epl_kernel dispatch, which reads what it wrote.  Per segment of the timed region: how long
+    before that launch's START the setups ended (negative: the launch had to wait for them), and how long before the END of
+    the launch in front of it (positive: they were done while that one still ran, so the next could follow it at once)."""
+    setups = [r for r in rows if kind_of(r[0]) == "chip_setup_kernel"]
+    m = min(n, len(setups), len(epl) - 1)
+    if m == 0:
+        return
+    pairs = list(zip(setups[-m:], epl[-m:], epl[-m - 1:-1]))
+    if any(su[1] > mine[1] for su, mine, _ in pairs):
+        print("chip_setup_kernel against the launch that needed it: the dispatches do not pair one to one from the trace's end "
+              "(a setup starts after its launch); not printed")
+        return
+    before_start = [(mine[1] - su[2]) * 1e-6 for su, mine, _ in pairs]
+    before_prev_end = [(prev[2] - su[2]) * 1e-6 for su, _, prev in pairs]
+    inside = sum(1 for v in before_prev_end if v >= 0)
+    print(f"chip_setup_kernel against the launch that needed it ({m} segments):")
+    print("  ended before that launch's start ms:            min %.4f median %.4f max %.4f" % quantiles(before_start))
+    print("  ended before the end of the launch in front ms: min %.4f median %.4f max %.4f" % quantiles(before_prev_end))
+    print(f"  done while the launch in front still ran: {inside} of {m}")
 
 
 def plan_timing(path, n):
@@ -96,7 +123,8 @@ def plan_timing(path, n):
     total = 0.0
     for k, v in stages.items():
         lo, med, hi = quantiles(v)
-        total += med
+        if k != "ready recorded at":      # (counted from the call's begin: the stages before it over again)
+            total += med
         print(f"  {k:28s} min {lo:.3f} median {med:.3f} max {hi:.3f}")
     print(f"  sum of medians {total:.3f}")
 
