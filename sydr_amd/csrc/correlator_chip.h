@@ -32,6 +32,7 @@
 
 namespace sdr {
 
+constexpr int kWaveThreads = 64;                  // one wave per channel-epoch: the ~5 us fixed latency of a workgroup is amortised over 4x more work
 constexpr int kChipMax = 26;                      // samples a lane's block may hold (k = 0..25)
 constexpr double kChipMinCodeStep = 1.0 / 25.9;   // blocks of at most 26 samples
 constexpr double kChipMaxCodeStep = 1.0 / 15.5;   // (16.368 MHz is 16.0 samples per chip: Doppler must not decide the kernel; 31-32 MHz through the half-chip view)
@@ -108,7 +109,7 @@ constexpr uint32_t cvt_selector(int byte) { return 0x03020000u | ((uint32_t)(4 +
 
 // What the chip-aligned routine needs of an epoch besides its samples and its rotations: wave-uniform integers that
 // follow from the taps' np.linspace constants alone.  The kernels with run-time positions derive them per epoch; for
-// the straight-line ones the HOST does, when a plan is made (epl.hip: sdr_epl_plan_create) -- the same function, the same
+// the straight-line ones the HOST does, when a plan is made (epl_plan.hip: sdr_epl_plan_create) -- the same function, the same
 // IEEE operations -- and a wave reads them with scalar loads: ~300 vector and ~200 scalar instructions less per epoch
 // (of ~5000: int64 conversions, the exact boundary evaluations of the first and last chip, a 64-bit modulo).
 template <int NT>
@@ -298,7 +299,7 @@ struct ChipSetup {
 #endif
 };
 
-// ... and how one is made (one THREAD per item of a plan: epl.hip's chip_setup_kernel; the host builds of the tests).
+// ... and how one is made (one THREAD per item of a plan: epl_plan.hip's chip_setup_kernel; the host builds of the tests).
 // stride: the lanes that share an epoch (a lane's blocks are that many chips apart).
 template <int NT, int KM, int KS, int KI>
 __host__ __device__ inline void chip_setup(int n, int64_t start_sample, int64_t capacity, double carrier_hz, double rem_code,

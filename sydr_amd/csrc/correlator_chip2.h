@@ -76,7 +76,7 @@ struct ChipNSetup {
     double bc[Shape::kMaxLen + 1], bs[Shape::kMaxLen + 1];   // the biased conversion's share of a segment sum of L samples
 };
 
-// One thread per item of a plan (epl.hip: chipn_setup_kernel; the host builds of the tests): false when the scheme does not
+// One thread per item of a plan (epl_plan.hip: chipn_setup_kernel; the host builds of the tests): false when the scheme does not
 // cover the item.
 template <int... P>
 __host__ __device__ inline bool chipn_setup(int n, int64_t start_sample, int64_t capacity, double carrier_hz, double rem_code, double code_step,

@@ -105,11 +105,11 @@ struct sdr_engine {
 
     // workspaces
     DevBuf ws_items, ws_out, ws_spacing, ws_setups, ws_stats;
-    // Device buffers of destroyed E/P/L plans, kept for the next plan (epl.hip plan_take / plan_give): a stream correlated
+    // Device buffers of destroyed E/P/L plans, kept for the next plan (epl_plan.hip plan_take / plan_give): a stream correlated
     // segment by segment makes and drops a plan per segment, and hipMalloc / hipFree cost more than the segment's setups --
     // hipFree also waits for the whole device, i.e. for the segment still running on another stream.
     std::vector<DevBuf> plan_pool;
-    // The stream a long list's per-item setups are made on (epl.hip plan_create_impl), made with the first such plan:
+    // The stream a long list's per-item setups are made on (epl_plan.hip make_setups; epl_plan.h PlanRoute), made with the first such plan:
     // chip_setup_kernel gets room on a SIMD only where the launch of the segment before drains, and on the engine's stream
     // the NEXT plan's item copy and check would queue behind it.  Every engine-wide wait covers it (sdr_sync_plans).
     hipStream_t plan_stream = nullptr;

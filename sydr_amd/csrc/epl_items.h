@@ -1,7 +1,8 @@
 // What sdr_epl_plan_create checks of ONE item of a list (no item may index outside the ring or the staged replica) and what
 // it contributes to the choice of the kernel variant -- one function for the host's walk of a short list, for the thread
-// per item that checks a long one on the device (epl.hip: validate_items_kernel) and for the sanitizer build that feeds it
-// hostile items on the CPU (tests/csrc/fuzz_items.hip, `make check-sanitize`).
+// per item that checks a long one on the device (epl_plan.hip: validate_items_kernel) and for the sanitizer build that feeds it
+// hostile items on the CPU (tests/csrc/fuzz_items.hip, `make check-sanitize`).  How the items' shares fold into a list's
+// statistics, and those into its variant word: epl_plan.h.
 #pragma once
 
 #include <hip/hip_runtime.h>

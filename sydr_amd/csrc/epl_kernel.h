@@ -11,13 +11,11 @@ namespace {
 
 using namespace sdr;
 
-constexpr int kWaveThreads = 64;  // one wave per channel-epoch: the ~5 us fixed latency of a workgroup is amortised over 4x more work
 // (the words of a plan's variant code -- epl_variant.h, host arithmetic alone -- carry these limits under names of their own)
 static_assert(kVariantChip == kChipMax && kVariantFastMaxStep == kFastMaxCodeStep && kVariantFastMaxStep8 == kFastMaxCodeStep8 &&
                   kVariantFastMinStep == kFastMinCodeStep && kVariantFastMaxLutWords == kFastMaxLutWords &&
                   kVariantChipMinStep == kChipMinCodeStep && kVariantChipMaxStep == kChipMaxCodeStep,
               "epl_variant.h restates the correlator cores' limits");
-constexpr int kLongLutWords = 4096;  // replicas of 16 KB and more (multi-period / BOC half-chip codes): four epochs share a staged copy
 
 // Dynamic LDS: [red: WPW*2*NT doubles][scratch: strips / rotations][lut: lut_words uint32]
 //

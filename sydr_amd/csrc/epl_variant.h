@@ -1,7 +1,8 @@
 // The variant word of an E/P/L plan (sdr_epl_plan_variant) -- how a list's statistics become one (choose_variant), what a
 // word means (decode: the ONLY reader of its bits), and the lists of the compiled forms a word can name: the straight-line
 // kernels of epl.hip and epl_straight.hip, the several-chips-per-lane shapes.  Host arithmetic only, no kernel in sight:
-// tests/csrc/epl_variant_dump.hip compiles it alone (tests/test_epl_variant.py, `make check-sanitize`).
+// tests/csrc/epl_variant_dump.hip compiles it alone (tests/test_epl_variant.py, `make check-sanitize`).  The other decisions of
+// a plan's creation (epl_plan.hip) -- the fold of a list's statistics that feeds choose_variant among them -- are epl_plan.h's.
 #pragma once
 
 #include "../../include/sydr_amd.h"
@@ -19,6 +20,7 @@ constexpr int kVariantC2 = 8192;         // x shape (1 .. 3): several chips per 
 constexpr double kVariantFastMaxStep = 0.06, kVariantFastMaxStep8 = 0.125, kVariantFastMinStep = 1e-4;
 constexpr int kVariantFastMaxLutWords = 1 << 18;
 constexpr double kVariantChipMinStep = 1.0 / 25.9, kVariantChipMaxStep = 1.0 / 15.5;
+constexpr int kLongLutWords = 4096;  // replicas of 16 KB and more (multi-period / BOC half-chip codes): four epochs share a staged copy (decode's wpw = 4)
 
 // ---- the compiled forms.  X(NT, KM, KS, KI): epl_kernel<ci8, NT, kChipMax, KM, 1, KS, KI>, one wave per workgroup, and --
 // where KS or KI is set -- chip_setup<NT, KM, KS, KI> for the plan's ChipSetup<NT> per item.  Each unit instantiates its own

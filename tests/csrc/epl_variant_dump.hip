@@ -55,7 +55,7 @@ void grid(F&& point) {
                                         for (int t = 0; t < 8; ++t) sp[t] = t < 5 ? kSpacings[s][t] : sp[t - 1] + (kSpacings[s][4] - kSpacings[s][3]);
                                         VariantInputs v = {};
                                         v.n_taps = n_taps, v.scale = scale, v.spacing = sp;
-                                        v.s_anchor = scale * sp[n_taps < 5 ? n_taps / 2 : 2];      // (epl.hip: item_rules)
+                                        v.s_anchor = scale * sp[n_taps < 5 ? n_taps / 2 : 2];      // (epl_plan.h: item_rules)
                                         v.max_step = ranges[r].max_step, v.min_step = ranges[r].min_step;
                                         v.m_lo = ranges[r].m_lo, v.m_hi = ranges[r].m_hi, v.all_split = all_split != 0;
                                         v.iq_fmt = fmt, v.lut_stride = stride, v.no_chip = no_chip != 0, v.no_split = no_split != 0;

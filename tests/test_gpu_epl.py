@@ -761,6 +761,32 @@ def test_long_lists_are_checked_on_the_device_like_short_ones_on_the_host(engine
             assert on_dev.fetch().tobytes() == engine.epl_batch(short, spacing, fs).tobytes()
         finally:
             on_dev.close()
+
+        def same_from_both_memories(items, fs, word=None):
+            assert hip.hipMemcpy(d, items.ctypes.data_as(ctypes.c_void_p), items.nbytes, 1) == 0
+            on_dev, on_host = engine.epl_plan_dev(d.value, len(items), spacing, fs), engine.epl_plan(items, spacing, fs)
+            try:
+                assert on_dev.variant == on_host.variant and word in (None, on_dev.variant), (on_dev.variant, on_host.variant)
+                on_dev.run()
+                on_host.run()
+                assert on_dev.fetch().tobytes() == on_host.fetch().tobytes()
+            finally:
+                on_dev.close()
+                on_host.close()
+
+        # two chips per lane (10 MHz): the device list's first item is read back for the shape, its count of strays awaited
+        same_from_both_memories(some_items(10e6, 4160), 10e6, 8 + 8192)
+        same_from_both_memories(some_items(10e6, 100), 10e6, 8 + 8192)
+        # long replicas: epochs of four code periods -- ceil(4092.x + 0.5) + SDR_LUT_PAD + 2 = 4099 words, 4096 and more -- over
+        # two slots in turn: the device list is read back whole for the period of its slots (2), as the host reads its own
+        engine.code_slots(2, 1023, 4)
+        for s in range(2):
+            engine.load_gps_code(s, s + 5)
+        step = (1.023e6 + rng.uniform(-4, 4, 8)) / fs
+        rem_code = rng.uniform(0, step)
+        four = make_items(np.arange(8) % 2, np.ceil((4 * 1023 - rem_code) / step).astype(np.int64), rng.integers(0, cap - 120000, 8),
+                          rng.uniform(-5000, 5000, 8), rng.uniform(0, 6.28, 8), rem_code, step)
+        same_from_both_memories(four, fs)
     finally:
         hip.hipFree(d)
 
